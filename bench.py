@@ -15,7 +15,12 @@ ids over RCCL so that every rank ends up with the whole CSR result of every batc
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0.  Beside the contract's keys it carries
+A plain run sets up, warms up, times exactly K steps (one region; --regions R: R regions, `value` the median) and
+prints the line; --dump-outputs DIR also writes the CSR of the last timed step (ids.npy, offsets.npy) into DIR.
+
+    python bench.py --full ...            the headline as the median of 15 regions, and everything listed below
+
+Prints ONE JSON line on rank 0.  Beside the contract's keys it carries, with --full,
   roofline       HBM roofline of the dominant kernel (algorithmic bytes / its duration in this run)
   roofline_valu  the binding one: VALU issue (counters from the committed rocprofv3 pass it names)
   throughputs    SURVEY 8d's three figures for C2 and C3: kernels only / C ABI host->host / Python surface
@@ -111,6 +116,42 @@ def _packed(texts):
     return np.frombuffer(b"".join(bs), dtype=np.uint8), off
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, batch, gathered, rank, dev, use_dist):
+    """--dump-outputs: what a caller of the timed path holds after its last step, the CSR of the last batch (one GPU: the batch's own
+    ids and offsets; distributed: the global CSR that every rank received, written by rank 0), as float64 (exact: ids < 2**32, offsets
+    < 2**53).  ids.npy, offsets.npy; a result of more than 64 MB is written as a fixed sample of its documents (seed 0), with their
+    indices in doc_index.npy."""
+    from splintr_amd.device import result_csr
+    if gathered is None:
+        ids, off = result_csr(batch)
+    else:
+        nd = torch.tensor([batch.n_docs], dtype=torch.int64, device=dev)
+        if use_dist:
+            dist.all_reduce(nd)
+        g_ids, g_off = gathered
+        off = g_off[:int(nd.item()) + 1].cpu().numpy().astype(np.uint64)
+        ids = g_ids[:int(off[-1])].cpu().numpy().view(np.uint32)
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    doc_index = None
+    if 8 * (len(ids) + len(off)) > DUMP_MAX_BYTES:
+        n_docs = len(off) - 1
+        lens = np.diff(off).astype(np.int64)
+        pick = np.random.default_rng(0).permutation(n_docs)
+        keep = pick[np.cumsum(lens[pick] + 2) * 8 <= DUMP_MAX_BYTES]          # (+1 offset, +1 index per document)
+        doc_index = np.sort(keep)
+        ids = np.concatenate([ids[int(off[d]):int(off[d + 1])] for d in doc_index]) if len(doc_index) else ids[:0]
+        off = np.concatenate([[0], np.cumsum(lens[doc_index])]).astype(np.uint64)
+    np.save(os.path.join(out_dir, "ids.npy"), ids.astype(np.float64))
+    np.save(os.path.join(out_dir, "offsets.npy"), off.astype(np.float64))
+    if doc_index is not None:
+        np.save(os.path.join(out_dir, "doc_index.npy"), doc_index.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -119,8 +160,15 @@ def main():
                          "(\"pipelined\", supplementary: `value` stays one batch at a time; skipped with --no-throughputs so that a profile sees one batch at a time)")
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--regions", type=int, default=15,
-                    help="the timed region of --steps steps is run this many times back to back; `value` is the median region")
+    ap.add_argument("--regions", type=int, default=None,
+                    help="the timed region of --steps steps is run this many times back to back; `value` is the median region "
+                         "(default: 1, so that --steps is the number of timed steps; 15 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the oracle verification passes, the memo-off / c2_wide / pipelined rotations, "
+                         "per-kernel rooflines, throughputs, BASELINE configs 4 and 5, the CPU baseline, the distributed per-rank breakdown "
+                         "and the comparison with the last committed line (the --no-* flags skip parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the CSR of the last timed step (ids.npy, offsets.npy; float64) into DIR")
     ap.add_argument("--docs", type=int, default=1000, help="documents per batch (BASELINE config: 1000)")
     ap.add_argument("--corpus", choices=("c2", "c2_wide"), default="c2",
                     help="c2 = BASELINE config 2 (the headline); c2_wide = the same mix over a >= 20 000-word lexicon (profiles only: the line then says so)")
@@ -138,6 +186,11 @@ def main():
     ap.add_argument("--c5-docs", type=int, default=C5_DOCS, help=argparse.SUPPRESS)
     ap.add_argument("--c5-doc-bytes", type=int, default=C5_DOC_BYTES, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.regions is None:
+        args.regions = 15 if args.full else 1
+    if not args.full:
+        # a plain run measures the headline alone: everything else is --full's
+        args.no_c4 = args.no_c5 = args.no_cpu_baseline = args.no_c2_wide = args.no_throughputs = True
     rehearsal = (args.c4_part_docs, args.c5_docs, args.c5_doc_bytes) != (C4_PART_DOCS, C5_DOCS, C5_DOC_BYTES)
     globals().update(C4_PART_DOCS=args.c4_part_docs, C5_DOCS=args.c5_docs, C5_DOC_BYTES=args.c5_doc_bytes)   # (forked generators read them)
 
@@ -178,7 +231,8 @@ def main():
         dist.barrier()
     from splintr_amd import Tokenizer, corpus, _ffi
     from splintr_amd.device import Comm, DeviceBatch, GatherV, encode_device, reserve, result_csr
-    from oracle.coracle import COracle
+    if args.full:
+        from oracle.coracle import COracle
 
     ncpu = os.cpu_count() or 1
     tok = Tokenizer.from_pretrained("cl100k_base", device=local_rank)
@@ -201,17 +255,18 @@ def main():
             # all-gather of the bucket + one unpack launch, on a stream of their own
             gv.encode_and_submit(b)
 
-    # ---- untimed verification pass: every batch of the rotation bit-exact vs the oracle ------------
-    orc = COracle("cl100k_base")
+    # ---- untimed first pass over every batch of the rotation; with --full: verification, bit-exact vs the oracle ------------
+    orc = COracle("cl100k_base") if args.full else None
     n_tokens, csr = [], []
     for b, texts in zip(batches, text_sets):
         encode_device(tok, b)
         torch.cuda.synchronize()
         ids, off = result_csr(b)
-        text_np, _ = _packed(texts)
-        o_ids, o_off = orc.encode_packed(text_np, b.host_offsets, threads=ncpu)
-        if not (np.array_equal(ids, o_ids) and np.array_equal(off, o_off)):
-            raise SystemExit(f"rank {rank}: HIP result differs from the oracle -- refusing to report a throughput")
+        if orc is not None:
+            text_np, _ = _packed(texts)
+            o_ids, o_off = orc.encode_packed(text_np, b.host_offsets, threads=ncpu)
+            if not (np.array_equal(ids, o_ids) and np.array_equal(off, o_off)):
+                raise SystemExit(f"rank {rank}: HIP result differs from the oracle -- refusing to report a throughput")
         n_tokens.append(int(off[-1]))
         csr.append((ids, off))
     bytes_rot = sum(b.n_bytes for b in batches)
@@ -256,25 +311,26 @@ def main():
         (best_depth, best_form), _ = min(cal.items(), key=lambda kv: kv[1])
         gv = GatherV(tok, dev, max_docs=gv_max_docs, max_tokens=gv_max_tokens, comm=comm, depth=best_depth, collective=best_form.split("+")[0],
                      pack24=best_form.endswith("pack24"))
-        got = []
-        gv.on_bucket = lambda res: got.extend((i.clone(), o.clone()) for i, o in res)
-        for _ in range(N_ROT):
-            step()
-        gv.finish()
-        torch.cuda.synchronize()
-        gv.on_bucket = None
-        assert not gv.overflowed() and len(got) == N_ROT
-        for k, (g_ids, g_off) in enumerate(got):
-            cnt = torch.tensor([n_tokens[k], batches[k].n_docs], dtype=torch.int64, device=dev)
-            allc = [torch.zeros_like(cnt) for _ in range(world)]
-            dist.all_gather(allc, cnt)
-            allc = torch.stack(allc).cpu().numpy()
-            t_before, d_before = int(allc[:rank, 0].sum()), int(allc[:rank, 1].sum())
-            assert int(g_off[int(allc[:, 1].sum())].item()) == int(allc[:, 0].sum())
-            ids, off = csr[k]
-            assert np.array_equal(g_ids[t_before:t_before + n_tokens[k]].cpu().numpy().view(np.uint32), ids)
-            assert np.array_equal((g_off[d_before:d_before + batches[k].n_docs + 1] - t_before).cpu().numpy().astype(np.uint64), off)
-        state["i"] = 0
+        if args.full:
+            got = []
+            gv.on_bucket = lambda res: got.extend((i.clone(), o.clone()) for i, o in res)
+            for _ in range(N_ROT):
+                step()
+            gv.finish()
+            torch.cuda.synchronize()
+            gv.on_bucket = None
+            assert not gv.overflowed() and len(got) == N_ROT
+            for k, (g_ids, g_off) in enumerate(got):
+                cnt = torch.tensor([n_tokens[k], batches[k].n_docs], dtype=torch.int64, device=dev)
+                allc = [torch.zeros_like(cnt) for _ in range(world)]
+                dist.all_gather(allc, cnt)
+                allc = torch.stack(allc).cpu().numpy()
+                t_before, d_before = int(allc[:rank, 0].sum()), int(allc[:rank, 1].sum())
+                assert int(g_off[int(allc[:, 1].sum())].item()) == int(allc[:, 0].sum())
+                ids, off = csr[k]
+                assert np.array_equal(g_ids[t_before:t_before + n_tokens[k]].cpu().numpy().view(np.uint32), ids)
+                assert np.array_equal((g_off[d_before:d_before + batches[k].n_docs + 1] - t_before).cpu().numpy().astype(np.uint64), off)
+            state["i"] = 0
 
     # ---- timed region ----------------------------------------------------------------------------
     # The contract's region -- W warm-up steps, then EXACTLY K steps between barrier + synchronize on both sides, the MAX
@@ -291,10 +347,14 @@ def main():
         if gv is not None:
             gv.finish()
         torch.cuda.synchronize()
+    # (the ramp's step count depends on the clock: the rotation starts over, so that which batch every warm-up and timed step
+    #  encodes -- and with it what --dump-outputs writes -- depends on the arguments alone)
+    state["i"] = 0
     for _ in range(args.warmup):
         step()
     reg_t, reg_b = [], []
     i0 = state["i"]
+    gv_last = None
     for _ in range(max(1, args.regions)):
         if gv is not None:
             gv.finish()
@@ -306,12 +366,14 @@ def main():
         for _ in range(args.steps):
             step()
         if gv is not None:
-            gv.finish()                   # the last batch's exchange completes inside the timed region
+            gv_last = gv.finish()         # the last batch's exchange completes inside the timed region
         torch.cuda.synchronize()
         if use_dist:
             dist.barrier()
         reg_t.append(time.perf_counter() - t0)
         reg_b.append(sum(batches[(i0 + j) % N_ROT].n_bytes for j in range(args.steps)))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, batches[(state["i"] - 1) % N_ROT], gv_last, rank, dev, use_dist)
     local_t = list(reg_t)
     if use_dist:
         et = torch.tensor(reg_t, dtype=torch.float64, device=dev)
@@ -337,7 +399,7 @@ def main():
     # collective + unpack, per step; exposed = step - encode-only.  Per rank, so that a first N-GPU curve says whether a
     # rank is encode-bound, link-bound, or waiting for a slower peer.
     dist_info = None
-    if use_dist:
+    if use_dist and args.full:
         local_ms = elapsed_local / args.steps * 1e3
         torch.cuda.synchronize()
         dist.barrier()
@@ -378,7 +440,7 @@ def main():
 
     # ---- the chunk memo: the same rotation with it OFF (what a batch costs cold), and what it holds ------------------------------
     memo_info = None
-    if rank == 0 and world == 1 and not use_dist:
+    if args.full and rank == 0 and world == 1 and not use_dist:
         ms_ = (ctypes.c_uint64 * 4)()
         L.spl_memo_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
         L.spl_memo_stats(tok.handle, ms_)
@@ -473,7 +535,7 @@ def main():
     # ---- per-kernel durations: measured live over the same rotation (separate pass) ---------------------
     roofline = roofline_valu = None
     kernels = {}
-    if rank == 0:
+    if args.full and rank == 0:
         L.spl_profile_enable(tok.handle, 1)
         L.spl_profile_reset(tok.handle)
         for j in range(13 * N_ROT):
@@ -704,7 +766,7 @@ def main():
     # (two surfaces had become 9 % and 37 % slower without anybody noticing.)  vs_prev = this / previous for rates, previous /
     # this for latencies; anything at or below 0.95 (0.90 for host <-> device figures, 0.75 for the figures that are the host cores') is listed in `regressions`.
     vs_prev = regressions = prev_name = None
-    if rank == 0 and world == 1 and not use_dist:
+    if args.full and rank == 0 and world == 1 and not use_dist:
         import glob
         import re
         cands_ = sorted((int(re.search(r"r(\d+)_bench\.json$", f).group(1)), f) for f in glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_bench.json")))
@@ -756,13 +818,14 @@ def main():
             "data": "synthetic",
             "config": {"workload": f"cl100k_base, {args.docs} x ~1 KB mixed English/code per batch and GPU, {N_ROT} distinct batches in rotation "
                                    f"(splintr_amd.corpus.{args.corpus}, seeds {seed0_} + 100 rank + k{'' if args.corpus == 'c2' else '; NOT the BASELINE corpus: the lexically wide variant'}); KERNEL-ONLY: corpus HBM-resident, CSR left in HBM "
-                                   f"(the host->host and Python-surface rates of the same batch are in `throughputs`); chunk memo warm (`memo.value_memo_off`: the same rotation without it)"
+                                   f"(with --full: the host->host and Python-surface rates of the same batch are in `throughputs`); chunk memo warm (with --full, `memo.value_memo_off`: the same rotation without it)"
                                    + (f"; the same mix over a >= 20 000-word lexicon (c2_wide, in rotation, same timing): {c2_wide_rot['value']} MB/s" if c2_wide_rot else "")
-                                   + (f"; + RCCL all-gatherv of the ragged ids (slab written by the encoder's last kernel, ONE exchange per bucket of {gv.depth} batches on its own stream -- {'ncclAllGather' if gv.collective == 'allgather' else 'grouped ncclSend / ncclRecv'}, chosen by the start-up calibration in `dist` --, overlapped with the following encodes; every rank gets every batch's global CSR, handed to the consumer per bucket)" if use_dist else ""),
+                                   + (f"; + RCCL all-gatherv of the ragged ids (slab written by the encoder's last kernel, ONE exchange per bucket of {gv.depth} batches on its own stream -- {'ncclAllGather' if gv.collective == 'allgather' else 'grouped ncclSend / ncclRecv'}, chosen by the start-up calibration, in `dist` with --full --, overlapped with the following encodes; every rank gets every batch's global CSR, handed to the consumer per bucket)" if use_dist else ""),
                        "vocab": "cl100k_base", "docs_per_batch": args.docs, "bytes_per_batch": round(bytes_rot / N_ROT),
                        "tokens_per_batch": round(sum(n_tokens) / N_ROT), "distinct_batches": N_ROT,
                        "parallelism": f"doc-shard x{world}"},
-            "parity": "bit-exact vs oracle (untimed verification pass over every batch of the rotation)",
+            "parity": "bit-exact vs oracle (untimed verification pass over every batch of the rotation)" if args.full
+                      else "not checked by this run (bench.py --full: bit-exact vs oracle over every batch of the rotation)",
             "roofline": roofline, "roofline_valu": roofline_valu, "throughputs": throughputs, "c4_strong": c4, "c5_strong": c5,
             "cpu_baseline": cpu, "pipelined": pipelined, "dist": dist_info, "timing": region_stats, "c2_wide_rotation": c2_wide_rot,
             "memo": memo_info, "vs_prev": vs_prev, "vs_prev_source": prev_name, "regressions": regressions,

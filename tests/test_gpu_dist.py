@@ -215,7 +215,7 @@ def test_bench_distributed_branch_rehearsal_world_1():
                RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--docs", "200", "--steps", "24", "--warmup", "8", "--regions", "3",
            "--c4-steps", "3", "--c5-steps", "3", "--c4-part-docs", "12000", "--c5-docs", "8", "--c5-doc-bytes", "1000000",
-           "--no-cpu-baseline", "--no-throughputs", "--no-c2-wide"]
+           "--no-cpu-baseline", "--no-throughputs", "--no-c2-wide", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, (p.returncode, p.stdout[-1500:], p.stderr[-3000:])
     line = json.loads(p.stdout.strip().splitlines()[-1])

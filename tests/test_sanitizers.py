@@ -5,6 +5,8 @@
     several threads -- as tests/san/host_san.cpp, built with g++ -fsanitize=address,undefined and -fsanitize=thread.
 (The host pipeline of spl_encode_batch needs a GPU: tests/test_gpu_sanitizers.py runs it under ThreadSanitizer.)"""
 import os
+import platform
+import shutil
 import subprocess
 
 import numpy as np
@@ -30,9 +32,18 @@ def corpus_file(tmp_path_factory):
     return str(p)
 
 
+def _launch(exe):
+    """gcc's ThreadSanitizer runtime stops with "unexpected memory mapping" on a kernel that randomises mmap with more bits than
+    its fixed layout allows (vm.mmap_rnd_bits = 32); newer runtimes re-exec themselves without address randomisation when they
+    see that.  A ThreadSanitizer binary is started that way from the outset."""
+    if exe.endswith("_tsan") and shutil.which("setarch"):
+        return ["setarch", platform.machine(), "-R", exe]
+    return [exe]
+
+
 def _run(exe, corpus_file, env_extra):
     env = dict(os.environ, **env_extra)
-    p = subprocess.run([exe, os.path.join(DATA, "cl100k_base.splv"), os.path.join(DATA, "unicode_classes.bin"), corpus_file],
+    p = subprocess.run(_launch(exe) + [os.path.join(DATA, "cl100k_base.splv"), os.path.join(DATA, "unicode_classes.bin"), corpus_file],
                        capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, (p.returncode, p.stdout[-1500:], p.stderr[-3000:])
     for word in ("ERROR: AddressSanitizer", "WARNING: ThreadSanitizer", "runtime error:", "LeakSanitizer"):

@@ -14,5 +14,5 @@ if [ ! -f $B/libsplintr_hip_tsan.so ] || [ "$(cat $B/tsan.srchash 2>/dev/null)" 
         || { tail -40 $B/tsan_build.log; exit 1; }
   echo "$H" > $B/tsan.srchash
 fi
-hipcc -O1 -g -std=c++17 -fsanitize=thread -x c++ tests/san/hostpath_driver.cpp -o $B/hostpath_tsan -L$B -lsplintr_hip_tsan -Wl,-rpath,'$ORIGIN' -pthread
+hipcc -O1 -g -std=c++17 -fsanitize=thread -fno-gpu-sanitize -x c++ tests/san/hostpath_driver.cpp -o $B/hostpath_tsan -L$B -lsplintr_hip_tsan -Wl,-rpath,'$ORIGIN' -pthread
 ls -la $B

@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out/tlb; rm -rf $O; mkdir -p $O
-SPL_BENCH_FORCE_DIST=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 timeout 600 rocprofv3 --kernel-trace -d $O/kt -o p -- python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-throughputs --no-c2-wide --regions 1 --c4-part-docs 15600 --no-c5 > $O/log.txt 2>&1
+SPL_BENCH_FORCE_DIST=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29533 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 timeout 600 rocprofv3 --kernel-trace -d $O/kt -o p -- python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-throughputs --no-c2-wide --regions 1 --c4-part-docs 15600 --no-c5 > $O/log.txt 2>&1
 python - <<'PY'
 import sqlite3, glob
 db = sqlite3.connect(glob.glob('gpurun_out/tlb/kt/**/*.db', recursive=True)[0])

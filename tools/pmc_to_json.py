@@ -33,7 +33,7 @@ for k, v in vals.items():
                   "TCC_HIT_sum": round(hit), "TCC_MISS_sum": round(miss), "l2_hit_rate": round(hit / (hit + miss), 3) if hit + miss else None,
                   "launches": v["_launches"]}
 json.dump(hbm, open(f"{out}/{TAG}_hbm_traffic.json", "w"), indent=1)
-sq = {"_how": "rocprofv3 --pmc <one group per run> --kernel-trace -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-throughputs "
+sq = {"_how": "rocprofv3 --pmc <one group per run> --kernel-trace -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-throughputs "
               "--no-c4 --no-c5 --no-c2-wide --regions 1 (tools/profile_round5.sh); per-dispatch averages over the rotating 1000 x ~1 KB cl100k bench batches; raw "
               f"numbers in {TAG}_pmc_passes.txt; kernel_us from the kernel trace of the bench command ({TAG}_kernel_stats.txt). kernel_cycles = "
               "kernel_us x 2400 MHz. valu_issue_frac = SQ_ACTIVE_INST_VALU x 4 cycles / (1024 SIMDs x kernel_cycles); lane_utilisation = "

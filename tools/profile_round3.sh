@@ -6,8 +6,8 @@ cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R
 O=gpurun_out/r03; rm -rf $O; mkdir -p $O
-CMD="python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-throughputs --no-c4 --no-c5"
-timeout 1500 python bench.py > $O/bench.json 2> $O/bench.err
+CMD="python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-throughputs --no-c4 --no-c5"
+timeout 1500 python bench.py --full > $O/bench.json 2> $O/bench.err
 timeout 300 rocprofv3 --kernel-trace --stats -d $O/kt -o p -- $CMD > $O/kt.log 2>&1
 python tools/rocpd_summary.py $(find $O/kt -name "*.db" | head -1) > $O/kernel_stats.txt 2>&1
 i=0
@@ -16,7 +16,7 @@ for c in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "SQ_INSTS_VALU SQ_
          "SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY" \
          "SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_BUSY_CYCLES GRBM_GUI_ACTIVE"; do
   i=$((i+1)); d=$O/pmc_$i; mkdir -p $d
-  timeout 300 rocprofv3 --pmc $c --kernel-trace -d $d -o p -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-throughputs --no-c4 --no-c5 > $d/log.txt 2>&1
+  timeout 300 rocprofv3 --pmc $c --kernel-trace -d $d -o p -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-throughputs --no-c4 --no-c5 > $d/log.txt 2>&1
   echo "== pass $i ($c) rc=$?" >> $O/pmc.txt
   python tools/pmc_summary.py $(find $d -name "*.db" | head -1) 2>&1 | grep -E "k_pretok|k_tile_out" >> $O/pmc.txt
 done
