@@ -351,7 +351,13 @@ int spl_is_byte_level(const spl_tokenizer* t);
 
 /* Per-kernel timing (HIP events on the launch stream).  While enabled every encode call records
  * events around each kernel; spl_profile_read returns the accumulated milliseconds and launch
- * counts per kernel since the last spl_profile_reset and synchronises the stream. */
+ * counts per kernel since the last spl_profile_reset and synchronises the stream.
+ * Slot order (spl_kernel_name gives the same names; a slot counts the CALLS in which its kernels ran, not the launches of a ranged call):
+ *   0 memset + k_mark_docs   1 k_special_scan   2 k_pretok (every device call, an empty batch included)   3 k_deferred_wave
+ *   4 k_bpe_segments   5 k_bpe_long   6 k_range_count   7 unused   8 k_range_out (queue mode) | k_tile_out (tile-owned mode); 9..15 unused.
+ * Tile-owned mode fills slots 2 and 8 (0 and 1 too with SPL_WITH_SPECIAL).  Slot 8 tells the two forms of that mode apart: a call that ran
+ * as ONE launch (option "fuse", splintr_amd/csrc/spl_k_fuse.h) leaves it alone, the two-launch form (k_pretok + k_tile_out) adds one -- and so does an
+ * empty batch, which launches neither. */
 #define SPL_MAX_KERNELS 16
 int spl_profile_enable(spl_tokenizer* t, int on);
 int spl_profile_reset(spl_tokenizer* t);
