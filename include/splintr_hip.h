@@ -90,7 +90,7 @@ int spl_device_count(void);
  * line, parsed as load_tiktoken_bpe does (src/core/vocab.rs:57-89: last space separates, rank
  * trimmed, a later duplicate key replaces the earlier one) -- or this repo's packed SPLV container
  * (tools/pack_vocab.py), told apart by the container's magic.
- * Restrictions (refused with SPL_EINVAL): ids must be < 2^21; two different keys must not share an id; a ByteLevel vocabulary must hold
+ * Restrictions (refused with SPL_EINVAL): ids must be < 2^21 - 1 (2 097 150 at most; the pseudo ids of missing single bytes, max id + 1 + k, included); two different keys must not share an id; a ByteLevel vocabulary must hold
  * all 256 alphabet characters, each ranking below every longer token.  A vocabulary that LACKS single bytes is taken as the reference
  * takes it (src/core/bpe.rs:73-75, 99-111, 182-191: pairs are ranked by their concatenated bytes, a node whose bytes are no token is
  * dropped from the result): the missing bytes get pseudo ids behind the vocabulary's for the merge loops and are never emitted.

@@ -963,6 +963,13 @@ __device__ __forceinline__ void bpe_wave(const DeviceTables& T, const Batch& b, 
 // minimum, a workgroup min-reduction picks the leftmost one, one thread relinks while two others
 // (in other wavefronts) re-rank the two affected pairs.  Three barriers and one memory round trip
 // per merge.
+// The reduction keys of the merge loops in this file pack (rank << B | node index) into 32 bits, all-ones = "nothing left".  The builder
+// accepts ids (= ranks) up to 2^21 - 2 (spl_tables.cpp: 2^21 - 1 stays free), so with r <= 0x1FFFFE:
+//   << 6 | lane   (wave64_merge,  index <= 63)                      <= 0x7FFFFFBF
+//   << 8 | index  (group merges <= 127, wave_tab_merge <= 255)      <= 0x1FFFFEFF   (SPL_NO_RANK << 8 in group_merge_near: 0xFFFFFF00, above them all)
+//   << 9 | index  (bpe_wave,      index <= WAVE_NMAX - 1 = 511)     <= 0x3FFFFDFF
+//   << 11 | index (bpe_block_lds, index <= BLOCK_LDS_NMAX - 1)      <= 0xFFFFF7FF
+// none reaches 0xFFFFFFFF, and no shift drops a rank bit (21 + 11 = 32).  Only r = 2^21 - 1 with i = 2047 would have equalled the sentinel.
 constexpr int BLOCK_LDS_NMAX = 2048;      // index bits in the reduction key
 template <class Emit>
 __device__ __forceinline__ void bpe_block_lds(const DeviceTables& T, const Batch& b, uint32_t pos, int n, uint32_t* s_id,

@@ -249,6 +249,9 @@ int build_tables(const uint8_t* splv, size_t splv_len, const uint8_t* ucls, size
     }
     for (const auto& kv : enc) max_rank_seen = std::max(max_rank_seen, kv.second);   // vocab_size: max id of the map as loaded
     if (max_rank_seen > SPL_ID_MASK) { err = "token id does not fit 21 bits"; return 1; }
+    // The id 2^21 - 1 stays free: the pair (2^21 - 1, 2^21 - 1) has a 42-bit key of all ones, which is what an EMPTY pair slot holds
+    // (SPL_PAIR_EMPTY) -- pair_rank would "find" it there and return the slot's upper 22 bits, 4194303, as the merged id.
+    if (max_rank_seen == SPL_ID_MASK) { err = "token ids must be < 2^21 - 1 (the id 2097151 is kept free: it marks an empty pair-table slot)"; return 1; }
     enc.erase(std::string());          // an empty key can never match a chunk
     // decoder side (build_decoder, src/core/vocab.rs:146-148, + Tokenizer::decode_bytes,
     // src/core/tokenizer.rs:877-897): id -> the bytes decode_bytes emits for it.  ByteLevel: the key
@@ -324,7 +327,7 @@ int build_tables(const uint8_t* splv, size_t splv_len, const uint8_t* ucls, size
     if (!out.all_bytes) {
         uint32_t next = max_rank_seen + 1;
         for (int b = 0; b < 256; b++) if (out.byte_id[b] == SPL_NO_RANK) out.byte_id[b] = next++;
-        if (next - 1 > SPL_ID_MASK) { err = "token ids must be < 2^21 (with the pseudo ids of the single bytes the vocabulary lacks)"; return 1; }
+        if (next - 1 >= SPL_ID_MASK) { err = "token ids must be < 2^21 - 1 (with the pseudo ids of the single bytes the vocabulary lacks)"; return 1; }
         out.id_limit = max_rank_seen + 1;
     }
 

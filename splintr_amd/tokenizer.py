@@ -114,7 +114,7 @@ class Tokenizer:
       \p{Han}-style patterns are accepted as they are) and merged on the GPU; a pattern with anything else in it (binary
       properties, script extensions, look-behind, back-references, \p{Lu} under (?i)) or one that can match the empty string
       raises the reference's "Regex error" ValueError naming the construct;
-    * the vocabulary must contain all 256 single bytes and ids below 2**21;
+    * the vocabulary must contain all 256 single bytes and ids below 2**21 - 1;
     * every key of up to 8 bytes gets a table slot of its own by hash-and-displace (csrc/spl_tables.cpp): a vocabulary in
       which so many such keys share one two-byte prefix (keys of 1..4 bytes: 16-bit salt) or one four-byte-prefix filter slot
       (keys of 5..8 bytes: 10-bit salt) that no salt separates them even after the table was doubled three times is refused
