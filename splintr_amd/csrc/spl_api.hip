@@ -1,6 +1,7 @@
-// spl_api.hip -- the C ABI (include/splintr_hip.h): handle, per-GPU contexts (tables, workspace,
-// streams), launch order, and the host pipeline of spl_encode_batch (pinned staging, chunked
-// H2D -> kernels -> D2H over private streams, document shards over several GPUs).
+// spl_api.hip -- the C ABI (include/splintr_hip.h): the root of the library's one HIP translation unit.  It includes the kernels
+// (spl_kernels.hip) and the host side, one file per concern and each building on the ones before it -- spl_host_res.h (resource owners,
+// pinned pool), spl_ctx.h (per-GPU context, handle, uploads), spl_streams.h (stream probe), spl_launch.h (memo, launch order, device
+// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h -- and holds the entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -30,2123 +31,14 @@
 
 using namespace spl;
 
-namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const std::string& msg) {
-    g_err = msg;
-    return code;
-}
-#define HIP_TRY(expr)                                                                      \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return fail(SPL_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-    } while (0)
-
-constexpr size_t QCOUNT_WORDS = 16;      // Batch::qcount
-enum { KI_MARK = 0, KI_SPECIAL, KI_PRETOK, KI_DEFER, KI_BPELANES, KI_BPELONG, KI_COUNT, KI_SCAN, KI_COMPACT, KI_N };
-const char* const k_names[KI_N] = {"memset+k_mark_docs", "k_special_scan", "k_pretok", "k_deferred_wave", "k_bpe_segments",
-                                   "k_bpe_long", "k_range_count", "(unused)", "k_range_out|k_tile_out"};
-
-template <class T> int dev_upload(const std::vector<T>& v, const T** out) {
-    void* p = nullptr;
-    const size_t bytes = v.size() * sizeof(T);
-    HIP_TRY(hipMalloc(&p, bytes ? bytes : 16));
-    *out = (const T*)p;                        // (owned by the context from here on: freed by its destructor)
-    if (bytes) HIP_TRY(hipMemcpy(p, v.data(), bytes, hipMemcpyHostToDevice));
-    return SPL_OK;
-}
-
-struct Special { std::string lit; uint32_t id; };
-
-// Pinned host buffers are expensive to create (the driver pins and maps every page), so result and
-// staging buffers are recycled.  Shared by the handle and by the results it gave out: a result
-// may outlive its handle.
-struct PinnedPool {
-    std::mutex mu;
-    std::vector<std::pair<size_t, void*>> free_;
-    size_t held = 0;
-    static constexpr size_t HELD_MAX = 8ull << 30;
-    void* get(size_t need, size_t& cap) {
-        need = std::max<size_t>(need, 4096);
-        {
-            std::lock_guard<std::mutex> g(mu);
-            int best = -1;
-            // (no buffer is smaller than 64 KiB: a request below that must still find the one it returned last
-            //  time -- it did not, and every call with a small offsets array paid a hipHostMalloc, 20 us)
-            const size_t lim = 4 * std::max<size_t>(need, (size_t)1 << 16);
-            for (int i = 0; i < (int)free_.size(); i++)
-                if (free_[i].first >= need && free_[i].first <= lim && (best < 0 || free_[i].first < free_[best].first)) best = i;
-            if (best >= 0) {
-                void* p = free_[best].second;
-                cap = free_[best].first;
-                held -= cap;
-                free_.erase(free_.begin() + best);
-                return p;
-            }
-        }
-        size_t c = 1 << 16;
-        while (c < need) c <<= 1;
-        if (c > (64u << 20)) c = (need + (32u << 20) - 1) / (32u << 20) * (32u << 20);     // big ones: 32 MiB steps
-        void* p = nullptr;
-        if (hipHostMalloc(&p, c, hipHostMallocPortable) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        cap = c;
-        return p;
-    }
-    void put(void* p, size_t cap) {
-        if (!p) return;
-        {
-            std::lock_guard<std::mutex> g(mu);
-            if (held + cap <= HELD_MAX) { free_.emplace_back(cap, p); held += cap; return; }
-        }
-        (void)hipHostFree(p);
-    }
-    ~PinnedPool() { for (auto& f : free_) (void)hipHostFree(f.second); }
-};
-
-// One pinned buffer from the pool, returned on scope exit.
-struct Pinned {
-    std::shared_ptr<PinnedPool> pool;
-    void* p = nullptr;
-    size_t cap = 0;
-    bool ensure(const std::shared_ptr<PinnedPool>& pl, size_t need) {
-        if (p && cap >= need) return true;
-        release();
-        pool = pl;
-        p = pool->get(need, cap);
-        return p != nullptr;
-    }
-    void release() { if (p && pool) pool->put(p, cap); p = nullptr; cap = 0; }
-    ~Pinned() { release(); }
-};
-
-// Pinned buffers handed to the caller as plain pointers (spl_decode_batch's outputs): spl_free finds the pool
-// they go back to here; a pointer it does not know is malloc'd memory.
-struct LooseBuffers {
-    std::mutex mu;
-    std::unordered_map<void*, std::pair<std::shared_ptr<PinnedPool>, size_t>> m;
-    void add(void* p, const std::shared_ptr<PinnedPool>& pool, size_t cap) { std::lock_guard<std::mutex> g(mu); m[p] = {pool, cap}; }
-    bool release(void* p) {
-        std::pair<std::shared_ptr<PinnedPool>, size_t> e;
-        {
-            std::lock_guard<std::mutex> g(mu);
-            auto it = m.find(p);
-            if (it == m.end()) return false;
-            e = it->second;
-            m.erase(it);
-        }
-        e.first->put(p, e.second);
-        return true;
-    }
-};
-LooseBuffers& loose() { static LooseBuffers* l = new LooseBuffers(); return *l; }   // (never destroyed: results may outlive every handle)
-
-// The DMA engines driven directly (VERDICT r04 #5a): hipMemcpyAsync device -> pinned host runs as a SHADER copy on this stack
-// (__amd_rocclr_copyBuffer: 7 % of the GPU time of the C3 pipeline, and it slows the next chunk's tile kernel while it runs);
-// hsa_amd_memory_async_copy hands the same copy to an SDMA engine.  libhsa-runtime64 is the runtime HIP itself sits on (already in
-// the process); its entry points are bound with dlsym so that the library gains no link dependency.  Option "sdma_d2h".
-struct HsaDma {
-    bool ok = false;
-    std::string err;
-    hsa_agent_t cpu{};
-    std::vector<hsa_agent_t> gpus;
-    decltype(&hsa_init) Init = nullptr;
-    decltype(&hsa_iterate_agents) IterateAgents = nullptr;
-    decltype(&hsa_agent_get_info) AgentGetInfo = nullptr;
-    decltype(&hsa_signal_create) SignalCreate = nullptr;
-    decltype(&hsa_signal_destroy) SignalDestroy = nullptr;
-    decltype(&hsa_signal_store_relaxed) SignalStore = nullptr;
-    decltype(&hsa_signal_wait_scacquire) SignalWait = nullptr;
-    decltype(&hsa_amd_memory_async_copy) AsyncCopy = nullptr;
-    static hsa_status_t on_agent(hsa_agent_t a, void* self) {
-        HsaDma* h = (HsaDma*)self;
-        hsa_device_type_t ty;
-        if (h->AgentGetInfo(a, HSA_AGENT_INFO_DEVICE, &ty) != HSA_STATUS_SUCCESS) return HSA_STATUS_SUCCESS;
-        if (ty == HSA_DEVICE_TYPE_GPU) h->gpus.push_back(a);
-        else if (ty == HSA_DEVICE_TYPE_CPU && h->cpu.handle == 0) h->cpu = a;
-        return HSA_STATUS_SUCCESS;
-    }
-    void load() {
-        void* lib = dlopen("libhsa-runtime64.so.1", RTLD_NOW | RTLD_GLOBAL);
-        if (!lib) { const char* e = dlerror(); err = std::string("libhsa-runtime64 not found: ") + (e ? e : ""); return; }
-        auto sym = [&](const char* n) { void* p = dlsym(lib, n); if (!p && err.empty()) err = std::string("libhsa-runtime64 lacks ") + n; return p; };
-        Init = (decltype(Init))sym("hsa_init");
-        IterateAgents = (decltype(IterateAgents))sym("hsa_iterate_agents");
-        AgentGetInfo = (decltype(AgentGetInfo))sym("hsa_agent_get_info");
-        SignalCreate = (decltype(SignalCreate))sym("hsa_signal_create");
-        SignalDestroy = (decltype(SignalDestroy))sym("hsa_signal_destroy");
-        SignalStore = (decltype(SignalStore))sym("hsa_signal_store_relaxed");
-        SignalWait = (decltype(SignalWait))sym("hsa_signal_wait_scacquire");
-        AsyncCopy = (decltype(AsyncCopy))sym("hsa_amd_memory_async_copy");
-        if (!err.empty()) return;
-        if (Init() != HSA_STATUS_SUCCESS) { err = "hsa_init failed"; return; }          // (reference counted: HIP has initialised it already)
-        if (IterateAgents(&HsaDma::on_agent, this) != HSA_STATUS_SUCCESS || gpus.empty() || cpu.handle == 0) { err = "no HSA agents"; return; }
-        ok = true;
-    }
-};
-HsaDma& hsa_dma() { static HsaDma* h = [] { auto* p = new HsaDma(); p->load(); return p; }(); return *h; }
-// the HSA agent of a HIP device: matched by PCI bus / device / function (HIP_VISIBLE_DEVICES may reorder or hide devices); false if none
-bool hsa_agent_of(int hip_device, hsa_agent_t* out) {
-    HsaDma& H = hsa_dma();
-    if (!H.ok) return false;
-    int bus = -1, dev = -1, dom = 0;
-    if (hipDeviceGetAttribute(&bus, hipDeviceAttributePciBusId, hip_device) != hipSuccess ||
-        hipDeviceGetAttribute(&dev, hipDeviceAttributePciDeviceId, hip_device) != hipSuccess) { (void)hipGetLastError(); return false; }
-    if (hipDeviceGetAttribute(&dom, hipDeviceAttributePciDomainID, hip_device) != hipSuccess) { (void)hipGetLastError(); dom = 0; }
-    for (hsa_agent_t a : H.gpus) {
-        uint32_t bdf = 0, adom = 0;
-        if (H.AgentGetInfo(a, (hsa_agent_info_t)HSA_AMD_AGENT_INFO_BDFID, &bdf) != HSA_STATUS_SUCCESS) continue;
-        (void)H.AgentGetInfo(a, (hsa_agent_info_t)HSA_AMD_AGENT_INFO_DOMAIN, &adom);
-        if ((int)((bdf >> 8) & 0xFFu) == bus && (int)((bdf >> 3) & 0x1Fu) == dev && (int)adom == dom) { *out = a; return true; }
-    }
-    return false;
-}
-
-constexpr int NSLOT = 3;                      // staging slots of the host pipeline per GPU
-
-// SPL_TRACE=1: progress of the host pipeline on stderr (development aid)
-bool trace_on() { static const bool on = getenv("SPL_TRACE") != nullptr; return on; }
-#ifdef SPL_HOST_TIMING   /* dev build: average host time between marks of the one-chunk path, printed every 256 calls */
-#include <chrono>
-static double g_ht[8]; static int g_htn;
-#define HT_T(v) const auto v = std::chrono::steady_clock::now()
-#define HT_ACC(i, a, b_) g_ht[i] += std::chrono::duration<double, std::micro>((b_) - (a)).count()
-#else
-#define HT_T(v) do { } while (0)
-#define HT_ACC(i, a, b_) do { } while (0)
-#endif
-inline double mono_us() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec * 1e6 + (double)ts.tv_nsec * 1e-3; }
-inline double trace_us() { timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)(ts.tv_sec % 1000) * 1e6 + (double)ts.tv_nsec * 1e-3; }
-#define TRACE(...) do { if (trace_on()) { fprintf(stderr, "[spl %12.1f] ", trace_us()); fprintf(stderr, __VA_ARGS__); fputc('\n', stderr); fflush(stderr); } } while (0)
-
-// Everything that lives on ONE GPU: lookup tables, workspace, and the host pipeline's streams and
-// staging.  A handle has one context per device of spl_set_devices (one by default).
-struct Ctx {
-    int device = 0;
-    DeviceTables dt{};
-    const uint32_t* d_tok_off = nullptr;       // decode table (vocabulary + specials), rebuilt after spl_add_special
-    const uint8_t* d_tok_bytes = nullptr;
-    uint32_t dec_max_id = 0;
-    const uint32_t* d_dec_sp_ids = nullptr; const uint32_t* d_dec_sp_off = nullptr; uint32_t dec_n_sp = 0;   // specials beyond the vocabulary's ids
-    bool dec_uploaded = false;
-    uint8_t* d_sp_lits = nullptr;              // uploaded lazily; invalidated by spl_add_special
-    bool sp_uploaded = false;
-    // workspace
-    uint64_t cap_bytes = 0, cap_docs = 0;
-    uint32_t* d_zero = nullptr;    // [tbits | tstart | skip | qcount]
-    size_t zero_words = 0, bitmap_words = 0;
-    uint32_t* d_stage = nullptr;
-    uint32_t* d_rank = nullptr;
-    uint32_t* d_aux = nullptr;    // inside d_rank's allocation
-    uint2* d_q64 = nullptr; uint2* d_qlong = nullptr; uint32_t* d_qdefer = nullptr;
-    uint32_t qcap64 = 0, qcaplong = 0, qcapdefer = 0;
-    unsigned long long* d_dbg = nullptr;
-    uint32_t* d_blk = nullptr;
-    // tile-owned mode: tile records, the tiles' token slots, group sums; and whether the token bitmap may hold
-    // stale bits (after hipMalloc or a multi-pass call) -- the single-pass kernel needs it all-zero
-    TileDesc* d_tdesc = nullptr;
-    uint32_t* d_tile_bits = nullptr; uint32_t* d_tcnt = nullptr;     // queue mode
-    uint32_t* d_tile_ids = nullptr;
-    uint32_t* d_tctl = nullptr;
-    uint32_t tgroups = 0, tpar = 0;
-    // fused mode (spl_k_fuse.h): per parity the tiles' published token counts (FUSE_REPL copies of u16[FUSE_STRIDE], then the 32-bit side
-    // array u32[FUSE_STRIDE]); a fused launch uses parity fpar and zeroes what the previous fused launch (fprev tiles) left in the other one
-    uint8_t* d_fctl = nullptr;
-    uint32_t fpar = 0, fprev = 0;
-    // chunk memo (spl_k_memo.h): the table, the tiles' log of what it did not hold, one claim word per slot for k_memo_fill, the pinned flag
-    MemoEnt* d_memo = nullptr; MemoExt* d_memo_ext = nullptr; uint32_t* d_mlog = nullptr; uint32_t* d_mlog_cnt = nullptr; uint32_t* d_mclaim = nullptr;
-    uint8_t* d_memo2 = nullptr;               // the second table (chunks of 33..64 bytes), ONE allocation: entries | second lines | key bytes 32..63 | claim words | log
-    uint32_t memo2_mask = 0, memo2_cap = 0;
-    unsigned long long* d_mstats = nullptr;
-    uint32_t* h_mflag = nullptr; uint32_t* dh_mflag = nullptr;
-    uint32_t memo_round = 0, memo_cap = 0, memo_mask = 0;
-    uint64_t memo_fills = 0, memo_since = 0;
-    bool fuse_off = false;                    // set by the caller of launch_all for this call: the two-launch form (text read in place over PCIe, below)
-    uint64_t* off_host = nullptr;             // set by the caller of launch_all: where k_tile_out also stores the offsets (one-chunk host batches)
-    bool off_host_written = false;            // launch_all: the tile-owned mode did so
-    // latency path (encode_small): text and offsets read where they lie in pinned host memory, completion by a word k_tile_out stores there
-    uint32_t* done_arm = nullptr;             // set by the caller of launch_all: device pointer of the completion word (this call only)
-    uint32_t done_seq = 0;
-    bool done_armed = false;                  // launch_all: k_tile_out will store it
-    uint8_t* h_small = nullptr; uint8_t* dh_small = nullptr;       // pinned: [text 4096 + 64 | offsets 8 * 257 | completion word], and its device pointer
-    uint32_t small_calls = 0;
-    const void* dp_host[2] = {nullptr, nullptr}; void* dp_dev[2] = {nullptr, nullptr};   // device pointers of the last two pinned result buffers
-    const uint8_t* solo_text = nullptr; const uint64_t* solo_off = nullptr;
-    hsa_agent_t hsa_agent{}; int hsa_state = 0;    // this device's HSA agent for the SDMA copies (0 not looked for yet, 1 found, 2 none: hipMemcpyAsync)
-    bool bitmap_dirty = true;
-    // host pipeline (spl_encode_batch / spl_decode_batch)
-    hipStream_t s_cmp = nullptr, s_h2d = nullptr, s_d2h = nullptr;
-    uint8_t* d_text[NSLOT] = {nullptr, nullptr, nullptr};
-    uint64_t* d_off[NSLOT] = {nullptr, nullptr, nullptr};
-    uint64_t slot_cap_bytes = 0, slot_cap_docs = 0;
-    uint32_t* d_ids = nullptr; uint64_t ids_cap = 0;         // the lane's ids, chunk c at its byte offset
-    uint64_t* d_oo = nullptr; uint64_t oo_cap = 0;           // chunk-local output offsets, chunk after chunk
-    // pipeline: the kernels of consecutive chunks alternate between this context and a TWIN on the same GPU -- a workspace and a compute
-    // stream of its own, the tables shared -- so that chunk k + 1's tile kernel starts while the stragglers of chunk k's finish
-    std::unique_ptr<Ctx> twin;
-    bool owns_tables = true;
-    bool streams_picked = false;              // the pipeline's copy streams have been chosen by measurement (pick_stream_beside)
-    Pinned h_text[NSLOT], h_off[NSLOT], h_oo;          // h_oo: the pipeline chunks' local output offsets (k_tile_out writes them there: no copy, no count to fetch)
-    uint64_t* dh_oo = nullptr;                          // its device-side address
-    // custom split patterns: the chunk's boundary bitmaps (starts | gaps, back to back) and the special tokens the
-    // host splitter found (positions | ids), per staging slot
-    Pinned h_ext[NSLOT], h_extsp[NSLOT];
-    uint32_t* d_ext[NSLOT] = {nullptr, nullptr, nullptr}; uint64_t ext_cap_words = 0;
-    uint32_t* d_extsp[NSLOT] = {nullptr, nullptr, nullptr}; uint64_t extsp_cap = 0;
-    // custom split patterns on the device (spl_rx_split.h): the program image, general categories, workspace, status word
-    const uint32_t* d_rx_image = nullptr; const uint16_t* d_gc1 = nullptr; const uint8_t* d_gc2 = nullptr;
-    uint8_t* d_rx_ws = nullptr; uint64_t rx_ws_cap = 0, rx_cap_blk = 0; uint32_t rx_gen = 0xFFFFu;
-    uint32_t* d_rx_status = nullptr;                                // RX_STATUS_SLOTS words, one per batch in rotation: a batch's k_rx_mark clears the next one's
-    uint32_t rx_slot = 0;
-    bool rx_next_clean = true;                                      // the next word of the rotation has been cleared (fresh memory; a k_rx_mark that ran)
-    uint32_t* dh_rx_status = nullptr;                               // (its device pointer)
-    uint32_t* h_rx_status = nullptr;                                // pinned copy: written behind every chunk's split, read when the batch is done
-    uint32_t* d_rx_bits = nullptr; uint64_t rx_bits_cap = 0;       // the two bitmaps of a device-text call (spl_encode_batch_device)
-    uint32_t* d_rx_patch = nullptr; uint64_t rx_patch_cap = 0;     // per-document fallback: the patch of one split (grow-only)
-    uint32_t* d_rx_bad = nullptr;                                   // [0] count, [1 .. RX_BAD_CAP] blocks the matcher gave up on (device list of one split)
-    uint32_t* h_rx_bad = nullptr; uint32_t* dh_rx_bad = nullptr;    // ... where k_rx_mark leaves it for the host (pinned), and its device pointer
-    hipEvent_t ev_split = nullptr;                                  // host pipeline: a chunk's split is through (the producer waits for it: per-document fallback)
-    hipEvent_t ev_h2d[NSLOT] = {nullptr, nullptr, nullptr}, ev_cmp[NSLOT] = {nullptr, nullptr, nullptr};
-    std::vector<hipEvent_t> ev_chunk;
-    // decode scratch (grow-only)
-    uint32_t* d_dec_ids = nullptr; uint64_t* d_dec_blk = nullptr; uint64_t* d_dec_idoff = nullptr; uint8_t* d_dec_out = nullptr;
-    uint64_t* d_dec_first = nullptr; uint64_t* d_dec_docoff = nullptr;
-    uint64_t dec_cap_ids = 0, dec_cap_out = 0, dec_cap_docs = 0;
-    // decode pipeline (large batches): two slots of the same scratch, a second compute stream, events per slot
-    struct DecSlot {
-        uint32_t* ids = nullptr; uint64_t* blk = nullptr; uint64_t* idoff = nullptr; uint64_t* first = nullptr; uint64_t* docoff = nullptr;
-        uint8_t* out = nullptr; uint64_t cap_ids = 0, cap_docs = 0, cap_out = 0;
-        hipEvent_t ev_in = nullptr, ev_len = nullptr, ev_cp = nullptr, ev_out = nullptr;
-    } dslot[2];
-    hipStream_t s_dec2 = nullptr;
-    Pinned h_dtot;
-    // profiling
-    bool prof = false;
-    hipEvent_t ev[KI_N + 1]{};
-    // a large device batch as ranges of its tiles (launch_all): a second stream beside the caller's, one event per range (grow-only), the hand-overs
-    hipStream_t s_rng = nullptr, s_rng_for = nullptr; std::vector<hipEvent_t> ev_rng; hipEvent_t ev_rng_in = nullptr, ev_rng_out = nullptr;
-    bool ev_ready = false;
-    double prof_ms[SPL_MAX_KERNELS]{};
-    uint64_t prof_n[SPL_MAX_KERNELS]{};
-    uint32_t* last_qcount = nullptr;
-    bool dbg_on = false;
-    int stop_phase = 0;     // spl_debug_phases bits 4..6 (profiling builds of the instruction mix per phase)
-    int force_tile = 0;     // 0 auto, 1 small tiles, 2 large tiles, 3 multi-pass, 4 queue mode, 5 tile-owned geometry B (spl_debug_phases bits 1..3)
-
-    void free_workspace() {
-        hipFree(d_zero); hipFree(d_stage); hipFree(d_rank);
-        hipFree(d_q64); hipFree(d_qlong); hipFree(d_qdefer); hipFree(d_blk); hipFree(d_dbg);
-        hipFree(d_tdesc); hipFree(d_tile_ids); hipFree(d_tctl); hipFree(d_tile_bits); hipFree(d_tcnt); hipFree(d_fctl);
-        d_fctl = nullptr; d_tdesc = nullptr; d_tile_ids = nullptr; d_tctl = nullptr; d_tile_bits = nullptr; d_tcnt = nullptr;
-        d_zero = nullptr; d_stage = nullptr; d_rank = nullptr;
-        d_q64 = nullptr; d_qlong = nullptr; d_qdefer = nullptr; d_blk = nullptr; d_dbg = nullptr;
-        cap_bytes = cap_docs = 0;
-    }
-    void memo_drop() {                        // (a new geometry: the next launch builds an empty memo)
-        if (!d_memo) return;
-        if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return; }
-        (void)hipDeviceSynchronize();
-        hipFree(d_memo); hipFree(d_memo_ext); hipFree(d_mlog); hipFree(d_mlog_cnt); hipFree(d_mclaim); hipFree(d_mstats); hipFree(d_memo2);
-        d_memo = nullptr; d_memo_ext = nullptr; d_mlog = nullptr; d_mlog_cnt = nullptr; d_mclaim = nullptr; d_mstats = nullptr; d_memo2 = nullptr;
-        dt.memo = nullptr; dt.memo_mask = 0; dt.memo2 = nullptr; dt.memo2_mask = 0;
-    }
-    void free_slots() {
-        for (int i = 0; i < NSLOT; i++) {
-            hipFree(d_text[i]); hipFree(d_off[i]); hipFree(d_ext[i]); hipFree(d_extsp[i]);
-            d_text[i] = nullptr; d_off[i] = nullptr; d_ext[i] = nullptr; d_extsp[i] = nullptr;
-        }
-        slot_cap_bytes = slot_cap_docs = 0; ext_cap_words = 0; extsp_cap = 0;
-    }
-    ~Ctx() {
-        if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return; }
-        (void)hipDeviceSynchronize();
-        twin.reset();
-        free_workspace();
-        free_slots();
-        if (!owns_tables) dt = DeviceTables{};
-        hipFree((void*)dt.ucls_stage1); hipFree((void*)dt.ucls_stage2); hipFree((void*)dt.short_tab);
-        hipFree((void*)dt.tiny_tab); hipFree((void*)dt.t8_tab);
-        hipFree((void*)dt.long_tab); hipFree((void*)dt.key_blob); hipFree((void*)dt.pair_tab);
-        hipFree((void*)dt.byte_id); hipFree((void*)dt.p8_tab); hipFree((void*)dt.len_mask);
-        hipFree((void*)dt.pfx); hipFree((void*)dt.filt4); hipFree((void*)dt.akind);
-        hipFree((void*)d_tok_off); hipFree((void*)d_tok_bytes); hipFree(d_sp_lits);
-        hipFree((void*)d_dec_sp_ids); hipFree((void*)d_dec_sp_off);
-        hipFree(d_ids); hipFree(d_oo);
-        hipFree((void*)d_rx_image); hipFree((void*)d_gc1); hipFree((void*)d_gc2); hipFree(d_rx_ws); hipFree(d_rx_status); hipFree(d_rx_bits); if (h_rx_status) (void)hipHostFree(h_rx_status);
-        if (h_small) (void)hipHostFree(h_small);
-        hipFree(d_memo); hipFree(d_memo_ext); hipFree(d_mlog); hipFree(d_mlog_cnt); hipFree(d_mclaim); hipFree(d_mstats); hipFree(d_memo2); if (h_mflag) (void)hipHostFree(h_mflag);
-        hipFree(d_rx_patch); hipFree(d_rx_bad); if (h_rx_bad) (void)hipHostFree(h_rx_bad); if (ev_split) (void)hipEventDestroy(ev_split);
-        hipFree(d_dec_ids); hipFree(d_dec_blk); hipFree(d_dec_idoff); hipFree(d_dec_out); hipFree(d_dec_first); hipFree(d_dec_docoff);
-        for (auto& ds : dslot) {
-            hipFree(ds.ids); hipFree(ds.blk); hipFree(ds.idoff); hipFree(ds.first); hipFree(ds.docoff); hipFree(ds.out);
-            for (hipEvent_t e : {ds.ev_in, ds.ev_len, ds.ev_cp, ds.ev_out}) if (e) (void)hipEventDestroy(e);
-        }
-        if (s_dec2) (void)hipStreamDestroy(s_dec2);
-        if (ev_ready) for (auto& e : ev) (void)hipEventDestroy(e);
-        for (int i = 0; i < NSLOT; i++) { if (ev_h2d[i]) (void)hipEventDestroy(ev_h2d[i]); if (ev_cmp[i]) (void)hipEventDestroy(ev_cmp[i]); }
-        for (auto e : ev_chunk) (void)hipEventDestroy(e);
-        if (s_cmp) (void)hipStreamDestroy(s_cmp);
-        if (s_rng) (void)hipStreamDestroy(s_rng);
-        for (hipEvent_t e : ev_rng) (void)hipEventDestroy(e);
-        if (ev_rng_in) (void)hipEventDestroy(ev_rng_in);
-        if (ev_rng_out) (void)hipEventDestroy(ev_rng_out);
-        if (s_h2d) (void)hipStreamDestroy(s_h2d);
-        if (s_d2h) (void)hipStreamDestroy(s_d2h);
-    }
-};
-
-}  // namespace
-
-struct spl_tokenizer {
-    HostTables ht;
-    std::vector<Special> specials;
-    uint32_t max_special_id = 0;
-    bool special_newline = false;             // a literal contains '\n': no sub-document cuts with SPL_WITH_SPECIAL
-    bool special_general = false;             // occurrences can overlap, or a literal exceeds SP_MAXLEN: the two-launch general matcher
-    RegexPtr regex;                           // SPL_PATTERN_CUSTOM: the host splitter's program (null: one of the GPU scanner's patterns)
-    std::vector<uint32_t> rx_image;           // ... and its image for the device splitter (empty: the program does not fit, the split stays on the host)
-    int rx_device = 1;                        // spl_set_option("device_split"): 0 keeps a custom pattern's split on the host cores
-    uint64_t rx_fallbacks = 0;                // DOCUMENTS the device splitter gave up on and the host split instead (spl_device_split_fallbacks)
-    std::vector<std::unique_ptr<Ctx>> ctx;
-    std::shared_ptr<PinnedPool> pool = std::make_shared<PinnedPool>();
-    // host pipeline tuning (spl_set_option)
-    uint64_t chunk_bytes = 5ull << 20;        // upper bound of one pipeline chunk (with the kernels of consecutive chunks on two streams 4 .. 6 MiB are best: C3 28.8 GB/s, 26.8 at 8 MiB)
-    uint64_t single_max = 4ull << 20;         // batches up to this size run as ONE chunk
-    uint32_t est_div = 2;                     // first guess of the token count: n_bytes / est_div
-    int subdoc = 1;                           // cut documents at context-free boundaries to balance the GPUs
-    int direct_write = 1;                     // one-chunk batches: the last kernel writes the ids straight into the pinned result
-    int small_path = 1;                       // batches of up to 4 KB take the latency path (encode_small)
-    int slab_pack24 = 0;                      // the ids of the all-gather slabs travel three bytes each (spl_set_option "slab_pack24": every rank alike)
-    int sdma_d2h = 0;                         // (measured, +0.5..3 %: not the default) pipeline chunks: their ids leave through hsa_amd_memory_async_copy (an SDMA engine) instead of hipMemcpyAsync
-    uint64_t dec_chunk_ids = 2ull << 20;      // decode pipeline: ids per chunk (batches of fewer than three such chunks are decoded in one piece; C3: 28.3 GB/s at 1 M, 30.5 at 2 M, 29.6 at 3 M)
-    int copy_threads = 4;                     // pipeline, pageable input: threads that copy a chunk into pinned staging
-    int memo = 1;                             // the chunk memo (spl_k_memo.h); "memo_bits": log2 of its entries (64 bytes each), "memo_log_cap": logged misses per region and fill
-    uint32_t memo_bits = 20, memo_log_cap = 1024, memo_long_bits = 16;          // "memo_long_bits": log2 of the entries for chunks of 33..64 bytes (160 bytes each; 0: none)
-    uint32_t range_tiles = 0;                 // "range_tiles" (measured, +2 % on the 215 MB configurations, -2 % on C3 in the bench line: not the default): batches of more than 1.25 x this many tiles go out as ranges of this many (k_pretok + k_tile_out per range; 0: one launch pair)
-    uint32_t group_scan_min = 256;            // "group_scan_min": batches of more than this many groups of 64 tiles get the groups' prefix sums from k_group_scan (0: never)
-    int range_streams = 2;                    // "range_streams": ... on the caller's stream alone (1) or alternating with a second one (2)
-    int fuse = 1;                             // tile-owned mode as ONE launch (spl_k_fuse.h) for batches of up to fuse_max_tiles tiles; 0: k_pretok + k_tile_out
-    uint32_t fuse_max_tiles = FUSE_MAX_TILES; // (every tile of such a launch is resident at once -- 256 CUs x 6 workgroups: a tile that waits for its base holds nobody up)
-    int pick_streams = 1;                     // pipeline: its streams chosen by measurement so that they run side by side (pick_stream_beside)
-    int twin_streams = 1;                     // pipeline: consecutive chunks' kernels on two streams / workspaces (Ctx::twin)
-    int chunk_ramp = 0;                       // pipeline: a lane's first and last chunk are a quarter of the others (a shorter first H2D and last D2H)
-    int direct_read = 1;                      // one-chunk batches from pinned memory: the tile kernel reads text and offsets where they lie (no H2D copy)
-    uint64_t small_calls = 0;                 // ... and how many did (spl_small_path_calls)
-};
-
-// One rank of a node-wide communicator (one process per GPU; RCCL over xGMI).
-struct spl_comm {
-    ncclComm_t comm = nullptr;
-    int rank = 0, world = 1, device = 0;
-    uint64_t* d_cnt = nullptr;        // [4] this rank's {T, N, capacity of its all_ids, of its all_off}
-    uint64_t* d_cnts = nullptr;       // [4 * world] every rank's
-    uint64_t* h_cnts = nullptr;       // pinned copy
-};
-
-struct spl_result {
-    std::shared_ptr<PinnedPool> pool;
-    uint32_t* ids = nullptr; size_t ids_cap = 0;       // capacities in BYTES of the pinned buffers
-    uint64_t* off = nullptr; size_t off_cap = 0;
-    uint64_t n_tokens = 0, n_docs = 0;
-    ~spl_result() { if (pool) { pool->put(ids, ids_cap); pool->put(off, off_cap); } }
-};
-
-namespace {
-
-int upload_tables(Ctx& c, const HostTables& ht) {
-    HIP_TRY(hipSetDevice(c.device));
-    int rc;
-    if ((rc = dev_upload(ht.ucls_stage1, &c.dt.ucls_stage1))) return rc;
-    if ((rc = dev_upload(ht.ucls_stage2, &c.dt.ucls_stage2))) return rc;
-    if ((rc = dev_upload(ht.short_tab, &c.dt.short_tab))) return rc;
-    if ((rc = dev_upload(ht.tiny_tab, &c.dt.tiny_tab))) return rc;
-    if ((rc = dev_upload(ht.t8_tab, &c.dt.t8_tab))) return rc;
-    if ((rc = dev_upload(ht.long_tab, &c.dt.long_tab))) return rc;
-    if ((rc = dev_upload(ht.key_blob, &c.dt.key_blob))) return rc;
-    if ((rc = dev_upload(ht.pair_tab, &c.dt.pair_tab))) return rc;
-    if ((rc = dev_upload(ht.byte_id, &c.dt.byte_id))) return rc;
-    if ((rc = dev_upload(ht.p8_tab, reinterpret_cast<const uint32_t**>(&c.dt.p8_tab)))) return rc;
-    if ((rc = dev_upload(ht.len_mask, &c.dt.len_mask))) return rc;
-    if ((rc = dev_upload(ht.pfx, &c.dt.pfx))) return rc;
-    if ((rc = dev_upload(ht.filt4, &c.dt.filt4))) return rc;
-    c.dt.filt4_shift = ht.filt4_shift;
-    c.dt.ucls_shift = ht.ucls_shift;
-    c.dt.ascii_base = (uint32_t)ht.ucls_stage1[0] << ht.ucls_shift;
-    {
-        std::vector<uint32_t> ak(256);
-        for (uint32_t ch = 0; ch < 128; ch++) {
-            const KindEnt e = ascii_entry(ht.pattern, ch, ht.ucls_stage2[c.dt.ascii_base + ch]);
-            ak[2 * ch] = e.x; ak[2 * ch + 1] = e.y;
-        }
-        if ((rc = dev_upload(ak, &c.dt.akind))) return rc;
-    }
-    c.dt.cjk_fast = ht.cjk_fast ? 1u : 0u;
-    c.dt.short_mask = (uint32_t)(ht.short_tab.size() / SPL_SHORT_BUCKET) - 1;
-    c.dt.tiny_mask = (uint32_t)((ht.tiny_tab.size() - 4) / SPL_TINY_WORDS) - 1;      // (slots; 4 words of padding behind them)
-    c.dt.t8_mask = (uint32_t)((ht.t8_tab.size() - 4) / SPL_T8_WORDS) - 1;
-    c.dt.long_mask = (uint32_t)ht.long_tab.size() - 1;
-    c.dt.pair_mask = (uint32_t)(ht.pair_tab.size() / SPL_PAIR_BUCKET) - 1;
-    c.dt.p8_mask = (uint32_t)(ht.p8_tab.size() / 2) - 1;
-    c.dt.tiny_free = ht.tiny_free; c.dt.t8_free = ht.t8_free;
-    c.dt.max_key_len = ht.max_key_len;
-    c.dt.pattern = (uint32_t)ht.pattern;
-    c.dt.all_bytes = ht.all_bytes ? 1u : 0u;
-    c.dt.id_limit = ht.id_limit;
-    return SPL_OK;
-}
-
-// ---- streams that really run side by side -----------------------------------------------------------------------------------------------
-// HIP gives a stream a hardware queue of its own only up to GPU_MAX_HW_QUEUES per priority (4 by default; streams beyond share one and run
-// one behind the other), and the n-th hardware queue a process creates sits on pipe n mod 4 of the command processor: two busy queues on one
-// pipe take turns -- every kernel of either waits tens of microseconds (kernel traces: profiles/r05_wave_exchange.txt, r05_host_pipeline.txt).
-// Which queue a stream gets depends on what else the process has created; the API neither tells nor sets it.  It can be MEASURED: a kernel
-// that spins for 150 us on one stream, a few empty kernels on the other -- 14 us until they are through when the two run side by side, 22 - 55
-// on one pipe, 165 in one queue (tools/dev/queue_probe.hip).  The pipeline's streams are picked that way, once per context.
-__global__ void k_probe_spin(unsigned long long ticks) {
-    const unsigned long long t0 = wall_clock64();
-    while (wall_clock64() - t0 < ticks) { }
-}
-__global__ void k_probe_nop() { }
-double probe_us(hipStream_t spin, hipStream_t other) {       // `spin` busy, four empty kernels on `other`: us until they are through (min of 3; spin null: alone)
-    double best = 1e30;
-    for (int rep = 0; rep < 3; rep++) {
-        if (spin) (void)hipStreamSynchronize(spin);
-        (void)hipStreamSynchronize(other);
-        if (spin) hipLaunchKernelGGL(k_probe_spin, dim3(8), dim3(64), 0, spin, 12000ull);       // wall_clock64: 100 MHz
-        const double t0 = mono_us();
-        for (int k = 0; k < 4; k++) hipLaunchKernelGGL(k_probe_nop, dim3(1), dim3(64), 0, other);
-        (void)hipStreamSynchronize(other);
-        best = std::min(best, mono_us() - t0);
-        if (spin) (void)hipStreamSynchronize(spin);
-    }
-    return best;
-}
-// A new stream that runs beside every stream of `busy` (each of which may be the one that is busy): up to 12 candidates over the three
-// priorities (a priority has queues of its own); the first without a conflict, else the least bad.  *conflict_us: what was left.
-int pick_stream_beside(const std::vector<hipStream_t>& busy, hipStream_t* out, double* conflict_us) {
-    int lo = 0, hi = 0;
-    HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
-    hipStream_t best_s = nullptr;
-    double best_v = 1e30;
-    for (int k = 0; k < 12; k++) {
-        hipStream_t s = nullptr;
-        HIP_TRY(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, k % 3 == 0 ? 0 : (k % 3 == 1 ? hi : lo)));
-        hipLaunchKernelGGL(k_probe_nop, dim3(1), dim3(64), 0, s);            // (its queue is created with its first use)
-        (void)hipStreamSynchronize(s);
-        const double alone = probe_us(nullptr, s);
-        double worst = 0;
-        for (hipStream_t b : busy) worst = std::max(worst, std::max(probe_us(b, s), probe_us(s, b)) - alone);
-        if (worst < best_v) { if (best_s) (void)hipStreamDestroy(best_s); best_s = s; best_v = worst; }
-        else (void)hipStreamDestroy(s);
-        if (best_v < 5.0) break;
-    }
-    *out = best_s;
-    if (conflict_us) *conflict_us = best_v;
-    return SPL_OK;
-}
-
-int ensure_streams(Ctx& c) {
-    if (c.s_cmp) return SPL_OK;
-    HIP_TRY(hipStreamCreateWithFlags(&c.s_cmp, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&c.s_h2d, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&c.s_d2h, hipStreamNonBlocking));
-    for (int i = 0; i < NSLOT; i++) {
-        HIP_TRY(hipEventCreateWithFlags(&c.ev_h2d[i], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&c.ev_cmp[i], hipEventDisableTiming));
-    }
-    return SPL_OK;
-}
-
-int reserve(Ctx* t, uint64_t max_bytes, uint64_t max_docs) {
-    if (max_bytes <= t->cap_bytes && max_docs <= t->cap_docs) return SPL_OK;
-    HIP_TRY(hipSetDevice(t->device));
-    HIP_TRY(hipDeviceSynchronize());
-    const uint64_t nb = std::max<uint64_t>(max_bytes, t->cap_bytes), nd = std::max<uint64_t>(max_docs, t->cap_docs);
-    t->free_workspace();
-    const size_t nblk = (size_t)(nb / RANK_BLK) + 2;
-    t->bitmap_words = nblk * 32 + 64;
-    t->zero_words = 4 * t->bitmap_words + QCOUNT_WORDS;      // tbits | tstart | skip | spcand, then the queue counters
-    HIP_TRY(hipMalloc((void**)&t->d_zero, t->zero_words * 4));
-    HIP_TRY(hipMalloc((void**)&t->d_stage, (nb + 8192) * 4));
-    HIP_TRY(hipMalloc((void**)&t->d_rank, (nb + 8192) * 12));   // ranks + two words of aux per byte
-    t->d_aux = t->d_rank + (nb + 8192);
-    const size_t tiles_s = (size_t)(nb / TileGeom<SPL_TILE_SMALL>::TBv) + 2;
-    t->qcaplong = (uint32_t)(nb / 2 + 64);          // long chunks AND every miss of a deferred segment
-    t->qcapdefer = (uint32_t)(2 * tiles_s + 64);
-    t->qcap64 = (uint32_t)(nb / 17 + 64);
-    HIP_TRY(hipMalloc((void**)&t->d_q64, (size_t)t->qcap64 * 8));
-    HIP_TRY(hipMalloc((void**)&t->d_dbg, (16 + 4 * SPL_DEBUG_BLOCKS) * 8));
-    HIP_TRY(hipMalloc((void**)&t->d_qlong, (size_t)t->qcaplong * 8));
-    HIP_TRY(hipMalloc((void**)&t->d_qdefer, (size_t)t->qcapdefer * 4));
-    HIP_TRY(hipMalloc((void**)&t->d_blk, (nblk + 2) * 4));
-    {
-        const size_t dbytes = (size_t)std::min<uint64_t>(nb, std::max<uint64_t>(SPL_DIRECT_MAX_BYTES, SPL_QUEUE_MAX_BYTES));
-        const size_t tiles = dbytes / TileGeom<SPL_TILE_SMALL>::TBv + 2;
-        t->tgroups = (uint32_t)(tiles / 64 + 2);
-        HIP_TRY(hipMalloc((void**)&t->d_tdesc, tiles * sizeof(TileDesc)));
-        HIP_TRY(hipMalloc((void**)&t->d_tile_ids, tiles * (size_t)(TileGeom<SPL_TILE_SMALL>::Wv + 1) * 4));
-        HIP_TRY(hipMalloc((void**)&t->d_tile_bits, tiles * (size_t)TILE_BITS_W * 4));
-        HIP_TRY(hipMalloc((void**)&t->d_tcnt, tiles * 4));
-        HIP_TRY(hipMalloc((void**)&t->d_tctl, (16 + 2 * (size_t)t->tgroups + 2 + 2 * (size_t)t->tgroups) * 4));      // (control words, two parities of group sums, their prefix sums as u64)
-        HIP_TRY(hipMemset(t->d_tctl, 0, (16 + 2 * (size_t)t->tgroups + 2 + 2 * (size_t)t->tgroups) * 4));
-        t->tpar = 0;
-        HIP_TRY(hipMalloc((void**)&t->d_fctl, 2 * FUSE_PARITY_BYTES));
-        HIP_TRY(hipMemset(t->d_fctl, 0, 2 * FUSE_PARITY_BYTES));
-        t->fpar = 0; t->fprev = 0;
-    }
-    t->bitmap_dirty = true;
-    t->cap_bytes = nb;
-    t->cap_docs = nd;
-    return SPL_OK;
-}
-
-int upload_specials(spl_tokenizer* tk, Ctx* t) {
-    if (t->sp_uploaded) return SPL_OK;
-    std::vector<uint8_t> recs;
-    if (!tk->special_general) {
-        // 32-byte header: the set of FIRST bytes (256 bits); then one record per literal
-        recs.assign(SP_HDR + tk->specials.size() * SP_REC + 16, 0);
-        for (size_t k = 0; k < tk->specials.size(); k++) {
-            const uint8_t c0 = (uint8_t)tk->specials[k].lit[0];
-            recs[c0 >> 3] |= (uint8_t)(1u << (c0 & 7));
-            uint8_t* r = recs.data() + SP_HDR + k * SP_REC;
-            r[0] = (uint8_t)tk->specials[k].lit.size();
-            memcpy(r + 4, &tk->specials[k].id, 4);
-            memcpy(r + 8, tk->specials[k].lit.data(), tk->specials[k].lit.size());
-        }
-    } else {
-        // general sets (k_special_ends / k_special_select): header = set of LAST bytes, records
-        // {len, id, blob offset, last byte}, then the literal bytes
-        const size_t n = tk->specials.size();
-        recs.assign(SP_HDR + n * SPG_REC, 0);
-        for (size_t k = 0; k < n; k++) {
-            const std::string& lit = tk->specials[k].lit;
-            const uint8_t cl = (uint8_t)lit.back();
-            recs[cl >> 3] |= (uint8_t)(1u << (cl & 7));
-            const uint32_t rec[4] = {(uint32_t)lit.size(), tk->specials[k].id, (uint32_t)(recs.size() - (SP_HDR + n * SPG_REC)), cl};
-            memcpy(recs.data() + SP_HDR + k * SPG_REC, rec, 16);
-            recs.insert(recs.end(), lit.begin(), lit.end());
-        }
-        recs.resize(recs.size() + 16, 0);
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    hipFree(t->d_sp_lits);
-    t->d_sp_lits = nullptr;
-    HIP_TRY(hipMalloc((void**)&t->d_sp_lits, recs.size()));
-    HIP_TRY(hipMemcpy(t->d_sp_lits, recs.data(), recs.size(), hipMemcpyHostToDevice));
-    t->sp_uploaded = true;
-    return SPL_OK;
-}
-
-// id -> bytes for decode: the vocabulary's decoder, then special_tokens_decoder for ids it lacks
-// (Tokenizer::decode_bytes, src/core/tokenizer.rs:877-897).
-int upload_decode(spl_tokenizer* tk, Ctx* t) {
-    if (t->dec_uploaded) return SPL_OK;
-    // dense id -> bytes table over the VOCABULARY's id range (special tokens fill the ids it lacks there);
-    // special tokens beyond it go into a small sorted side table
-    const uint32_t max_id = tk->ht.max_id;
-    std::vector<const Special*> sp(max_id + 1, nullptr);
-    std::vector<const Special*> far;
-    for (const auto& s : tk->specials) {                      // (two literals with one id: the later one, as a map insert)
-        if (s.id <= max_id) sp[s.id] = &s;
-        else {
-            bool seen = false;
-            for (auto& f : far) if (f->id == s.id) { f = &s; seen = true; }
-            if (!seen) far.push_back(&s);
-        }
-    }
-    std::sort(far.begin(), far.end(), [](const Special* a, const Special* b) { return a->id < b->id; });
-    std::vector<uint32_t> off(max_id + 2, 0);
-    std::vector<uint8_t> bytes;
-    bytes.reserve(tk->ht.tok_bytes.size() + 4096);
-    for (uint32_t id = 0; id <= max_id; id++) {
-        off[id] = (uint32_t)bytes.size();
-        const bool in_vocab = tk->ht.tok_present[id];
-        if (in_vocab) bytes.insert(bytes.end(), tk->ht.tok_bytes.begin() + tk->ht.tok_off[id], tk->ht.tok_bytes.begin() + tk->ht.tok_off[id + 1]);
-        else if (sp[id]) bytes.insert(bytes.end(), sp[id]->lit.begin(), sp[id]->lit.end());
-    }
-    off[max_id + 1] = (uint32_t)bytes.size();
-    std::vector<uint32_t> sp_ids, sp_off;
-    for (const Special* f : far) {
-        sp_ids.push_back(f->id);
-        sp_off.push_back((uint32_t)bytes.size());
-        bytes.insert(bytes.end(), f->lit.begin(), f->lit.end());
-    }
-    sp_off.push_back((uint32_t)bytes.size());
-    HIP_TRY(hipDeviceSynchronize());
-    hipFree((void*)t->d_tok_off); hipFree((void*)t->d_tok_bytes); hipFree((void*)t->d_dec_sp_ids); hipFree((void*)t->d_dec_sp_off);
-    t->d_tok_off = nullptr; t->d_tok_bytes = nullptr; t->d_dec_sp_ids = nullptr; t->d_dec_sp_off = nullptr;
-    int rc;
-    if ((rc = dev_upload(off, &t->d_tok_off))) return rc;
-    if ((rc = dev_upload(bytes, &t->d_tok_bytes))) return rc;
-    if ((rc = dev_upload(sp_ids, &t->d_dec_sp_ids))) return rc;
-    if ((rc = dev_upload(sp_off, &t->d_dec_sp_off))) return rc;
-    t->dec_n_sp = (uint32_t)sp_ids.size();
-    t->dec_max_id = max_id;
-    t->dec_uploaded = true;
-    return SPL_OK;
-}
-
-struct SlabOut { uint32_t* d_slab = nullptr; uint64_t cap_words = 0, max_docs = 0; };
-// chunk boundaries given from outside (host splitter): device bitmaps, and the special tokens found on the host
-constexpr uint32_t RX_STATUS_SLOTS = 8;
-struct ExtIn {
-    const uint32_t* d_starts = nullptr; const uint32_t* d_gaps = nullptr; const uint32_t* d_sp_pos = nullptr; const uint32_t* d_sp_id = nullptr; uint32_t n_sp = 0;
-    // the two bitmaps are still to be made, by the device splitter, inside launch_all (behind the special-token kernels, whose bitmaps it reads):
-    uint32_t* d_status = nullptr;          // non-null: yes; the status word it reports to
-    uint32_t* d_status_host = nullptr;     // ... and (device pointer of) its pinned host copy, written by k_rx_mark itself
-};
-int rx_launch(spl_tokenizer* tk, Ctx* c, const uint8_t* d_text, uint64_t n_bytes, const uint64_t* d_doc_off, uint64_t n_docs,
-              uint32_t* d_starts, uint32_t* d_gaps, uint32_t* d_status, hipStream_t s, const Batch* sp = nullptr, uint32_t sp_words = 0,
-              uint32_t* d_status_host = nullptr, bool bad_sets_status = false);
-
-// The chunk memo of a context (spl_k_memo.h): built empty at the first launch; the tiles log what it did not hold and raise the pinned
-// flag; a launch that finds the flag raised first runs k_memo_fill on its stream -- encode the logged chunks, put them in -- and then
-// its own kernels: the memo is only ever written between two launches of the stream that reads it.
-// (the parts of the second table's one allocation)
-struct Memo2Parts { MemoEnt* ent; MemoExt* ext; MemoHi* hi; uint32_t* claim; uint32_t* log; };
-Memo2Parts memo2_parts(Ctx* t) {
-    const size_t s2 = (size_t)t->memo2_mask + 1;
-    Memo2Parts m;
-    m.ent = (MemoEnt*)t->d_memo2; m.ext = (MemoExt*)(m.ent + s2); m.hi = (MemoHi*)(m.ext + s2); m.claim = (uint32_t*)(m.hi + s2); m.log = m.claim + s2;
-    return m;
-}
-void memo_tables(Ctx* t) {
-    t->dt.memo = t->d_memo; t->dt.memo_mask = t->memo_mask; t->dt.memo_ext = t->d_memo_ext;
-    t->dt.memo2 = nullptr; t->dt.memo2_mask = 0; t->dt.memo2_ext = nullptr; t->dt.memo2_hi = nullptr;
-    if (t->d_memo2) { const Memo2Parts m = memo2_parts(t); t->dt.memo2 = m.ent; t->dt.memo2_mask = t->memo2_mask; t->dt.memo2_ext = m.ext; t->dt.memo2_hi = m.hi; }
-}
-int memo_ensure(spl_tokenizer* tk, Ctx* t) {
-    if (t->d_memo) return SPL_OK;
-    const size_t slots = (size_t)1 << tk->memo_bits;
-    HIP_TRY(hipMalloc((void**)&t->d_memo, slots * sizeof(MemoEnt)));
-    HIP_TRY(hipMemset(t->d_memo, 0, slots * sizeof(MemoEnt)));
-    HIP_TRY(hipMalloc((void**)&t->d_memo_ext, slots * sizeof(MemoExt)));      // (only hits of seven to fourteen tokens ever touch it)
-    HIP_TRY(hipMalloc((void**)&t->d_mclaim, slots * 4));
-    HIP_TRY(hipMemset(t->d_mclaim, 0, slots * 4));
-    // (the log of a context that takes LARGE batches is larger: a cold pass over 200 MB misses the vocabulary three million times, and at 65 536
-    //  logged chunks a fill -- duplicates among them -- the memo needed a dozen passes to hold them all; one entry per 192 bytes of capacity, 16 384 a region at most)
-    t->memo_cap = (uint32_t)std::min<uint64_t>(16384, std::max<uint64_t>(tk->memo_log_cap, t->cap_bytes / ((uint64_t)SPL_MEMO_LOG_REGIONS * 192)));
-    HIP_TRY(hipMalloc((void**)&t->d_mlog, (size_t)SPL_MEMO_LOG_REGIONS * t->memo_cap * SPL_MEMO_LOG_WORDS * 4));
-    HIP_TRY(hipMalloc((void**)&t->d_mlog_cnt, 2 * SPL_MEMO_LOG_REGIONS * 4));              // (the second half: the log of chunks of 33..64 bytes)
-    HIP_TRY(hipMemset(t->d_mlog_cnt, 0, 2 * SPL_MEMO_LOG_REGIONS * 4));
-    t->memo2_mask = 0; t->memo2_cap = 0;
-    if (tk->memo_long_bits) {
-        const size_t s2 = (size_t)1 << tk->memo_long_bits;
-        t->memo2_cap = std::max<uint32_t>(t->memo_cap / 8, 16);
-        const size_t bytes = s2 * (sizeof(MemoEnt) + sizeof(MemoExt) + sizeof(MemoHi) + 4) + (size_t)SPL_MEMO_LOG_REGIONS * t->memo2_cap * SPL_MEMO_LOG_WORDS2 * 4;
-        HIP_TRY(hipMalloc((void**)&t->d_memo2, bytes));
-        HIP_TRY(hipMemset(t->d_memo2, 0, s2 * (sizeof(MemoEnt) + sizeof(MemoExt) + sizeof(MemoHi) + 4)));
-        t->memo2_mask = (uint32_t)(s2 - 1);
-    }
-    HIP_TRY(hipMalloc((void**)&t->d_mstats, 16));
-    HIP_TRY(hipMemset(t->d_mstats, 0, 16));
-    if (!t->h_mflag) {
-        HIP_TRY(hipHostMalloc((void**)&t->h_mflag, 64, hipHostMallocPortable));
-        t->h_mflag[0] = 0;
-        void* dp = nullptr;
-        HIP_TRY(hipHostGetDevicePointer(&dp, t->h_mflag, 0));
-        t->dh_mflag = (uint32_t*)dp;
-    }
-    t->h_mflag[0] = 0;
-    t->memo_mask = (uint32_t)(slots - 1);
-    memo_tables(t);
-    t->memo_round = 0; t->memo_fills = 0; t->memo_since = 0;
-    return SPL_OK;
-}
-int memo_before_launch(spl_tokenizer* tk, Ctx* t, hipStream_t s) {
-    if (!tk->memo) { t->dt.memo = nullptr; t->dt.memo2 = nullptr; return SPL_OK; }
-    int rc = memo_ensure(tk, t);
-    if (rc) return rc;
-    memo_tables(t);
-    t->memo_since++;
-    // (the flag was raised by an EARLIER launch's tiles, when one of the log's regions became half full)
-    if (*(volatile uint32_t*)t->h_mflag) {
-        *(volatile uint32_t*)t->h_mflag = 0;
-        t->memo_round++;
-        hipLaunchKernelGGL(k_memo_fill<false>, dim3((t->memo_cap + MEMO_FILL_NT - 1) / MEMO_FILL_NT, SPL_MEMO_LOG_REGIONS), dim3(MEMO_FILL_NT), 0, s, t->dt, t->d_memo, t->d_memo_ext,
-                           (MemoHi*)nullptr, (const uint32_t*)t->d_mlog, (const uint32_t*)t->d_mlog_cnt, t->memo_cap, t->d_mclaim, t->memo_round, t->d_mstats);
-        if (t->d_memo2) {
-            const Memo2Parts m = memo2_parts(t);
-            hipLaunchKernelGGL(k_memo_fill<true>, dim3((t->memo2_cap + MEMO_FILL_NT2 - 1) / MEMO_FILL_NT2, SPL_MEMO_LOG_REGIONS), dim3(MEMO_FILL_NT2), 0, s, t->dt, m.ent, m.ext, m.hi,
-                               (const uint32_t*)m.log, (const uint32_t*)(t->d_mlog_cnt + SPL_MEMO_LOG_REGIONS), t->memo2_cap, m.claim, t->memo_round, t->d_mstats);
-        }
-        HIP_TRY(hipMemsetAsync(t->d_mlog_cnt, 0, 2 * SPL_MEMO_LOG_REGIONS * 4, s));
-        t->memo_fills++;
-        t->memo_since = 0;
-    }
-    return SPL_OK;
-}
-
-int launch_all(spl_tokenizer* tk, Ctx* t, const uint8_t* d_utf8, uint64_t n_bytes, const uint64_t* d_doc_off, uint64_t n_docs,
-               uint32_t flags, uint32_t* d_ids, uint64_t ids_cap, uint64_t* d_out_off, hipStream_t s,
-               const SlabOut* so = nullptr, const ExtIn* ext = nullptr, int phase = 0) {
-    // phase (tile-owned mode with the device splitter, per-document fallback): 0 = everything; 1 = only what comes in FRONT of the tile kernel
-    // (bitmap fills, special-token scan, the device splitter); 2 = only the tile kernel and k_tile_out, on bitmaps the caller may have patched
-    if (((uintptr_t)d_utf8 & 15) != 0) return fail(SPL_EINVAL, "text buffer must be 16-byte aligned");
-    if (ext && n_bytes > SPL_DIRECT_MAX_BYTES) return fail(SPL_EINVAL, "external chunk boundaries: at most 256 MB per device call");
-    // (external boundaries from the HOST splitter: the special tokens -- if any -- were found there; the GPU's literal scan stays off)
-    const bool special = (!ext || ext->d_status) && (flags & SPL_WITH_SPECIAL) && !tk->specials.empty();
-    if (special) { int rc0 = upload_specials(tk, t); if (rc0) return rc0; }
-    if (n_bytes > 0x7FFF0000ull) return fail(SPL_EINVAL, "n_bytes per device call must be < 2^31 - 65536 (split the corpus at document boundaries; spl_encode_batch does that by itself)");
-    if (n_docs > 0xFFFFFFF0ull) return fail(SPL_EINVAL, "n_docs per device call must be < 2^32 - 16");
-    int rc = reserve(t, n_bytes, n_docs);
-    if (rc) return rc;
-    if (t->prof && !t->ev_ready) {
-        for (auto& e : t->ev) HIP_TRY(hipEventCreate(&e));
-        t->ev_ready = true;
-    }
-    Batch b{};
-    b.text = d_utf8; b.n_bytes = (uint32_t)n_bytes; b.doc_off = d_doc_off; b.n_docs = (uint32_t)n_docs;
-    b.n_blk = (uint32_t)(n_bytes / RANK_BLK + 1);
-    const size_t uw = (size_t)b.n_blk * 32 + 32;
-    // bitmaps and queue counters packed back to back for THIS batch size: one memset clears them
-    b.tbits = t->d_zero; b.tstart = t->d_zero + uw;
-    const bool general = special && tk->special_general;
-    const size_t nbm = special ? (general ? 4 : 3) : 2;             // bitmaps in use for THIS call
-    b.skip = special ? t->d_zero + 2 * uw : nullptr;
-    b.spcand = general ? t->d_zero + 3 * uw : nullptr;
-    b.qcount = t->d_zero + nbm * uw;
-    t->last_qcount = b.qcount;
-    b.sp_lits = t->d_sp_lits; b.n_special = special ? (uint32_t)tk->specials.size() : 0u;
-    b.stage = t->d_stage; b.rank_scr = t->d_rank; b.aux = t->d_aux;
-    b.q64 = t->d_q64; b.qlong = t->d_qlong; b.qdefer = t->d_qdefer;
-    b.qcap64 = t->qcap64; b.qcaplong = t->qcaplong; b.qcapdefer = t->qcapdefer;
-    b.dbg = (t->dbg_on || t->prof) ? t->d_dbg : nullptr;
-    b.stop_phase = (uint32_t)t->stop_phase;
-    { static const uint32_t dbg_wg = [] { const char* e = getenv("SPL_DEBUG_WG"); return e ? (uint32_t)strtoul(e, nullptr, 10) : 0xFFFFFFFFu; }(); b.dbg_wg = dbg_wg; }
-    if (t->prof) {
-        const unsigned long long init[2] = {~0ull, 0ull};
-        HIP_TRY(hipMemcpyAsync(t->d_dbg + 14, init, 16, hipMemcpyHostToDevice, s));
-    }
-    b.blk_base = t->d_blk;
-    b.id_limit = t->dt.id_limit;
-    b.ids_out = d_ids; b.ids_cap = ids_cap; b.off_out = d_out_off;
-    if (phase != 1) {                                        // (the chunk memo: a fill, if the earlier launches left something to put in)
-        int rcm = memo_before_launch(tk, t, s);
-        if (rcm) return rcm;
-        if (t->dt.memo) { b.mlog = t->d_mlog; b.mlog_cnt = t->d_mlog_cnt; b.mlog_cap = t->memo_cap; b.mflag = t->dh_mflag; }
-        if (t->dt.memo && t->d_memo2) { b.mlog2 = memo2_parts(t).log; b.mlog2_cap = t->memo2_cap; }
-    }
-
-    const bool pf = t->prof;
-#define MARK(i) do { if (pf) HIP_TRY(hipEventRecord(t->ev[i], s)); } while (0)
-    // small batches: small tiles (occupancy hides latency); large batches: 4 KiB tiles
-    // queue mode: tile-owned tiles + global queues for what is long, for batches beyond the two-launch limit
-    const bool queue_mode = !ext && !special && (t->force_tile == 4 || (t->force_tile == 0 && n_bytes > SPL_DIRECT_MAX_BYTES)) &&
-                            n_bytes <= SPL_QUEUE_MAX_BYTES;
-    const bool small_tiles = ext || queue_mode || t->force_tile == 1 || t->force_tile == 3 || t->force_tile == 5 ||
-                             (t->force_tile == 4 && special) ||          // (queue mode has no special-token form: tile-owned)
-                             (t->force_tile == 0 && n_bytes <= SPL_DIRECT_MAX_BYTES);
-    const bool direct = ext || (!queue_mode && small_tiles && t->force_tile != 3 && n_bytes <= SPL_DIRECT_MAX_BYTES);
-    // tile-owned mode: two geometries of the same window (spl_kernels.hip SPL_TILE_DIRECT_A / _B; force 5: B at any size)
-    static_assert(TileGeom<SPL_TILE_DIRECT_A>::Wv == TileGeom<SPL_TILE_SMALL>::Wv && TileGeom<SPL_TILE_DIRECT_B>::Wv == TileGeom<SPL_TILE_SMALL>::Wv &&
-                  TileGeom<SPL_TILE_DIRECT_A>::TBv >= TileGeom<SPL_TILE_SMALL>::TBv && TileGeom<SPL_TILE_DIRECT_B>::TBv >= TileGeom<SPL_TILE_SMALL>::TBv,
-                  "the workspace is sized for SPL_TILE_SMALL's window and tile count");
-    const bool direct_b = direct && (t->force_tile == 5 || n_bytes > SPL_DIRECT_A_MAX_BYTES);
-    const uint32_t tile_bytes = direct ? (direct_b ? TileGeom<SPL_TILE_DIRECT_B>::TBv : TileGeom<SPL_TILE_DIRECT_A>::TBv)
-                              : TileGeom<SPL_TILE_SMALL>::TBv;
-    const uint32_t ntiles = (uint32_t)((n_bytes + tile_bytes - 1) / tile_bytes);
-    // (A/B on the 1 MB bench batch: folding these launches together -- clean-after-use bitmaps, one
-    //  tail kernel with a grid barrier and a last-workgroup scan -- was SLOWER than this plain
-    //  sequence: back-to-back launches overlap their dispatch with the previous kernel, while
-    //  single-workgroup tails and agent-scope fences sit on the critical path.)
-    // Single pass: small batches without special tokens are finished by ONE kernel.
-    bool fused_scan_used = false;
-    bool fused_launch = false;               // tile-owned mode as ONE launch: no k_tile_out
-    if (queue_mode) {
-        t->bitmap_dirty = true;
-        HIP_TRY(hipMemsetAsync(t->d_zero, 0, (2 * uw + QCOUNT_WORDS) * 4, s));
-        b.tdesc = t->d_tdesc; b.tile_ids = t->d_tile_ids; b.tctl = t->d_tctl; b.tile_bits = t->d_tile_bits; b.tcnt = t->d_tcnt;
-        b.tgroups = t->tgroups; b.tpar = t->tpar; b.tslot = (uint32_t)TileGeom<SPL_TILE_SMALL>::Wv + 1u;
-        t->tpar ^= 1u;
-        MARK(KI_MARK);
-        if (n_docs) hipLaunchKernelGGL(k_mark_docs, dim3((uint32_t)((n_docs + 255) / 256)), dim3(256), 0, s, b);
-        MARK(KI_SPECIAL); MARK(KI_PRETOK);
-        hipLaunchKernelGGL((k_pretok<SPL_TILE_SMALL>), dim3(ntiles), dim3(NT), 0, s, PRETOK_EARLY(t->dt, b), t->dt, b);
-        MARK(KI_DEFER);
-        hipLaunchKernelGGL(k_deferred_wave, dim3(256), dim3(64), 0, s, t->dt, b);
-        MARK(KI_BPELANES);
-        hipLaunchKernelGGL(k_bpe_segments, dim3(std::min<uint32_t>(2048, ntiles / 4 + 8)), dim3(NT), 0, s, t->dt, b);
-        MARK(KI_BPELONG);
-        hipLaunchKernelGGL(k_bpe_long, dim3(std::min<uint32_t>(2048, ntiles / 4 + 8)), dim3(NT), 0, s, t->dt, b, 1);
-        MARK(KI_COUNT);
-        hipLaunchKernelGGL((k_range_count<SPL_TILE_SMALL>), dim3(ntiles), dim3(64), 0, s, b);
-        MARK(KI_SCAN); MARK(KI_COMPACT);
-        hipLaunchKernelGGL((k_range_out<SPL_TILE_SMALL>), dim3(ntiles), dim3(64), 0, s, b);
-        MARK(KI_N);
-    } else if (direct) {
-        const bool ext_sp = ext && ext->n_sp > 0;
-        if (phase == 2) {
-        } else if (special) {
-            // the three bitmaps are cleared per call; documents and literals are marked by the
-            // multi-pass kernels, the tile kernel reads the bitmaps on top of its document search
-            HIP_TRY(hipMemsetAsync(t->d_zero, 0, (nbm * uw + QCOUNT_WORDS) * 4, s));
-            t->bitmap_dirty = true;
-        } else if (ext_sp) {                   // the token bitmap takes the host-found literals: cleared per call
-            HIP_TRY(hipMemsetAsync(t->d_zero, 0, uw * 4, s));
-            t->bitmap_dirty = true;
-        } else if (t->bitmap_dirty) {
-            HIP_TRY(hipMemsetAsync(t->d_zero, 0, t->zero_words * 4, s));
-            t->bitmap_dirty = false;
-        }
-        b.tdesc = t->d_tdesc; b.tile_ids = t->d_tile_ids; b.tctl = t->d_tctl;
-        b.tgroups = t->tgroups; b.tpar = t->tpar; b.tslot = (uint32_t)TileGeom<SPL_TILE_SMALL>::Wv + 1u;
-        if (so && ntiles) { b.slab = so->d_slab; b.slab_cap = (uint32_t)so->cap_words; b.slab_max_docs = (uint32_t)so->max_docs; b.slab_p24 = tk->slab_pack24 ? 1u : 0u; }
-        // (The latency path as ONE launch -- the last workgroup of the tile kernel turning every tile's record into the CSR by itself, no
-        //  k_tile_out -- was built and measured in round 5: 33.6 us per 1 KB call against 31.2 with the two launches, 23.9 against 22.8 for 13
-        //  bytes.  Two back-to-back launches overlap the second one's dispatch with the first kernel; the fused epilogue's device-scope fences,
-        //  L1-bypassing loads and serial walk over the tiles cost more than that launch.  Dropped.)
-        // ONE launch (spl_k_fuse.h): every tile resident at once, each learns its base from the others' published counts and writes its
-        // part of the CSR itself
-        const bool fuse = tk->fuse && !t->fuse_off && ntiles && ntiles <= tk->fuse_max_tiles && phase != 1;
-        if (fuse) {
-            uint8_t* const mine = t->d_fctl + (size_t)t->fpar * FUSE_PARITY_BYTES, * const other = t->d_fctl + (size_t)(t->fpar ^ 1u) * FUSE_PARITY_BYTES;
-            b.ftc = (uint16_t*)mine; b.ftb = (uint32_t*)(mine + (size_t)FUSE_REPL * FUSE_STRIDE * 2);
-            b.fzc = (uint16_t*)other; b.fzb = (uint32_t*)(other + (size_t)FUSE_REPL * FUSE_STRIDE * 2); b.fz_n = t->fprev;
-            t->fpar ^= 1u;
-            t->fprev = ntiles;
-            fused_launch = true;
-        }
-        if (ntiles && phase != 1 && !fuse) t->tpar ^= 1u;     // k_tile_out zeroes the other parity's sums for the next call
-        if (ntiles && t->off_host && phase != 1) { b.off_out2 = t->off_host; t->off_host_written = true; }
-        if (ntiles && t->done_arm && phase != 1) { b.done = t->done_arm; b.done_seq = t->done_seq; t->done_armed = true; }
-        if (!special) b.tstart = nullptr;
-        b.qcount = nullptr;
-        t->last_qcount = nullptr;
-        if (ext) {
-            b.ext_starts = ext->d_starts; b.ext_gaps = ext->d_gaps;
-            if (ext_sp) {
-                b.skip = const_cast<uint32_t*>(ext->d_gaps);     // (read-only here: the spans the literals' tokens lie in)
-                if (phase != 2) hipLaunchKernelGGL(k_ext_specials, dim3((ext->n_sp + 255) / 256), dim3(256), 0, s, b, ext->d_sp_pos, ext->d_sp_id, ext->n_sp);
-            }
-        }
-        MARK(KI_MARK);
-        if (special && n_docs && phase != 2) hipLaunchKernelGGL(k_mark_docs, dim3((uint32_t)((n_docs + 255) / 256)), dim3(256), 0, s, b);
-        MARK(KI_SPECIAL);
-        if (special && n_bytes && phase != 2) {
-            if (!general) hipLaunchKernelGGL(k_special_scan, dim3((uint32_t)((n_bytes + 255) / 256)), dim3(256), 0, s, b);
-            else {
-                hipLaunchKernelGGL(k_special_ends, dim3((uint32_t)((n_bytes + 255) / 256)), dim3(256), 0, s, b);
-                hipLaunchKernelGGL(k_special_select, dim3((uint32_t)((n_docs + 255) / 256)), dim3(256), 0, s, b);
-            }
-        }
-        if (ext && ext->d_status && phase != 2) {            // the device splitter, behind the literal scan whose bitmaps it reads
-            int rcx = rx_launch(tk, t, d_utf8, n_bytes, d_doc_off, n_docs, const_cast<uint32_t*>(ext->d_starts), const_cast<uint32_t*>(ext->d_gaps),
-                                ext->d_status, s, special ? &b : nullptr, (uint32_t)uw, ext->d_status_host);
-            if (rcx) return rcx;
-        }
-        if (phase == 1) {
-            const hipError_t le1 = hipGetLastError();
-            if (le1 != hipSuccess) return fail(SPL_EDEVICE, std::string("kernel launch: ") + hipGetErrorString(le1));
-            return SPL_OK;
-        }
-        MARK(KI_PRETOK);
-        // A LARGE batch goes out as ranges of its tiles -- k_pretok and k_tile_out of range k, then of range k + 1, ...: what k_pretok leaves for
-        // k_tile_out (the tiles' ids and records) is still in the caches when k_tile_out reads it (one launch pair over 215 MB: 42 GB/s; its
-        // 27 MB ranges: 50), and on two streams the slow last tiles of one range run beside the next range's first.  A tile's base is the sum
-        // of the counts of the tiles in front of it: k_tile_out of range k needs k_pretok of the ranges 0 .. k, nothing else.
-        const bool ranged = ntiles && !fuse && tk->range_tiles && ntiles > tk->range_tiles + tk->range_tiles / 4 && !so && !pf && !b.done && !b.off_out2 &&
-                            phase == 0 && direct_b;
-        if (ranged) {
-            // (ranges of equal size, a multiple of 64 tiles: the tiles' counts are summed per group of 64)
-            const uint32_t nr = (ntiles + tk->range_tiles - 1) / tk->range_tiles, R = (((ntiles + nr - 1) / nr) + 63u) & ~63u;
-            const bool two = tk->range_streams == 2;
-            if (two && t->s_rng && t->s_rng_for != s && tk->pick_streams) { (void)hipStreamSynchronize(t->s_rng); (void)hipStreamDestroy(t->s_rng); t->s_rng = nullptr; }
-            if (two && !t->s_rng) {
-                // (a stream MEASURED to run beside the caller's: which hardware queue a stream gets is the runtime's choice -- pick_stream_beside)
-                if (tk->pick_streams) { double cf = 0; int rcp = pick_stream_beside({s}, &t->s_rng, &cf); if (rcp) return rcp; }
-                else HIP_TRY(hipStreamCreateWithFlags(&t->s_rng, hipStreamNonBlocking));
-                t->s_rng_for = s;
-                if (!t->ev_rng_in) {
-                HIP_TRY(hipEventCreateWithFlags(&t->ev_rng_in, hipEventDisableTiming));
-                HIP_TRY(hipEventCreateWithFlags(&t->ev_rng_out, hipEventDisableTiming));
-                }
-            }
-            while (two && t->ev_rng.size() < nr) { hipEvent_t e; HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming)); t->ev_rng.push_back(e); }
-            if (two) { HIP_TRY(hipEventRecord(t->ev_rng_in, s)); HIP_TRY(hipStreamWaitEvent(t->s_rng, t->ev_rng_in, 0)); }     // (what the caller's stream holds comes first)
-            for (uint32_t k = 0; k < nr; k++) {
-                hipStream_t st = (two && (k & 1u)) ? t->s_rng : s;
-                if (k * R >= ntiles) break;
-                const uint32_t n = std::min(R, ntiles - k * R);
-                b.tile0 = k * R;
-                hipLaunchKernelGGL((k_pretok<SPL_TILE_DIRECT_B>), dim3(n), dim3(NT), 0, st, PRETOK_EARLY(t->dt, b), t->dt, b);
-                if (two) {
-                    HIP_TRY(hipEventRecord(t->ev_rng[k], st));
-                    if (k) HIP_TRY(hipStreamWaitEvent(st, t->ev_rng[k - 1], 0));        // (k_pretok of range k - 1, on the other stream; the ranges before it: in order)
-                }
-                hipLaunchKernelGGL(k_tile_out, dim3(n), dim3(TOUT_NT), 0, st, tile_out_args(b));
-            }
-            b.tile0 = 0;
-            if (two) { HIP_TRY(hipEventRecord(t->ev_rng_out, t->s_rng)); HIP_TRY(hipStreamWaitEvent(s, t->ev_rng_out, 0)); }
-        }
-        else if (ntiles && direct_b) hipLaunchKernelGGL((k_pretok<SPL_TILE_DIRECT_B>), dim3(ntiles), dim3(NT), 0, s, PRETOK_EARLY(t->dt, b), t->dt, b);
-        else if (ntiles) hipLaunchKernelGGL((k_pretok<SPL_TILE_DIRECT_A>), dim3(ntiles), dim3(NT), 0, s, PRETOK_EARLY(t->dt, b), t->dt, b);
-        else HIP_TRY(hipMemsetAsync(d_out_off, 0, (n_docs + 1) * 8, s));
-        MARK(KI_DEFER); MARK(KI_BPELANES); MARK(KI_BPELONG); MARK(KI_COUNT); MARK(KI_SCAN); MARK(KI_COMPACT);
-        if (ntiles && !fuse && !ranged) {
-            const uint32_t ng = (ntiles + 63u) / 64u;
-            if (ng > tk->group_scan_min && tk->group_scan_min) {
-                unsigned long long* const gpre = reinterpret_cast<unsigned long long*>(t->d_tctl + ((16 + 2 * (size_t)t->tgroups + 1) & ~(size_t)1));
-                hipLaunchKernelGGL(k_group_scan, dim3(1), dim3(256), 0, s, (const uint32_t*)(t->d_tctl + 16 + b.tpar * t->tgroups), ng, gpre);
-                b.gpre = gpre;
-            }
-            hipLaunchKernelGGL(k_tile_out, dim3(ntiles), dim3(TOUT_NT), 0, s, tile_out_args(b));
-        }
-        MARK(KI_N);
-    } else {
-        (void)fused_scan_used;
-        return fail(SPL_EINVAL, (flags & SPL_WITH_SPECIAL) && !tk->specials.empty()
-                                    ? "a device call with SPL_WITH_SPECIAL takes at most 256 MB: split the call at document boundaries -- spl_encode_batch does that by itself"
-                                    : "this device call fits neither the tile-owned mode (256 MB) nor queue mode (2047 MiB, no forced geometry): split it at document boundaries");
-    }
-#undef MARK
-    {
-        const hipError_t le = hipGetLastError();
-        if (le != hipSuccess) {
-            return fail(SPL_EDEVICE, std::string("kernel launch: ") + hipGetErrorString(le));
-        }
-    }
-    if (so && !(direct && ntiles))          // the slab copy of the result, where k_tile_out did not write it
-        hipLaunchKernelGGL(k_gatherv_pack, dim3(256), dim3(256), 0, s, d_ids, d_out_off, (uint32_t)n_docs, so->d_slab,
-                           (uint32_t)so->cap_words, (uint32_t)so->max_docs, tk->slab_pack24 ? 1u : 0u);
-    if (pf) {
-        HIP_TRY(hipEventSynchronize(t->ev[KI_N]));
-        for (int i = 0; i < KI_N; i++) {
-            // slots whose kernels were not launched in this mode would only show the event overhead
-            const bool launched = queue_mode ? (i != KI_SPECIAL && i != KI_SCAN) : direct ? (i == KI_PRETOK || (i == KI_COMPACT && !fused_launch) || (special && (i == KI_MARK || i == KI_SPECIAL)))
-                                         : !((i == KI_SPECIAL && !special) ||
-                                             (i == KI_COUNT && fused_scan_used));
-            if (!launched) continue;
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, t->ev[i], t->ev[i + 1]));
-            if (i == KI_PRETOK && ntiles) {
-                // the dominant kernel is timed on the device's wall clock instead (see k_pretok)
-                unsigned long long span[2];
-                HIP_TRY(hipMemcpy(span, t->d_dbg + 14, 16, hipMemcpyDeviceToHost));
-#ifndef SPL_DEBUG_STAMPS
-                {   // the end: the latest of the workgroups' own words (spl_k_pretok.h)
-                    static thread_local std::vector<unsigned long long> ends;
-                    ends.resize(std::min<size_t>(ntiles, 4 * (size_t)SPL_DEBUG_BLOCKS));
-                    HIP_TRY(hipMemcpy(ends.data(), t->d_dbg + 16, ends.size() * 8, hipMemcpyDeviceToHost));
-                    span[1] = 0;
-                    for (unsigned long long e : ends) span[1] = std::max(span[1], e);
-                }
-#endif
-                int khz = 0;
-                HIP_TRY(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, t->device));
-                if (khz > 0 && span[1] > span[0]) ms = (float)((double)(span[1] - span[0]) / (double)khz);
-            }
-            t->prof_ms[i] += ms;
-            t->prof_n[i] += 1;
-        }
-    }
-    return SPL_OK;
-}
-
-// ---- custom split patterns on the device (spl_rx_split.h) ---------------------------------------------------------
-// Uploads the program image (and the general-category table if a class set tests one) to this context once, grows the
-// workspace, and launches the two kernels on `s`: d_starts / d_gaps (n_bytes / 32 + 2 words each, at least) are zeroed here;
-// *d_status collects RXS_* bits (not cleared here: a batch of several chunks shares one word).
-bool rx_applies(const spl_tokenizer* tk, uint32_t flags) {
-    (void)flags;                           // (SPL_WITH_SPECIAL too: the literals are found by the GPU's own scan, as for the built-in patterns)
-    return tk->regex && tk->rx_device && !tk->rx_image.empty();
-}
-int rx_ensure(spl_tokenizer* tk, Ctx* c) {
-    if (c->d_rx_image) return SPL_OK;
-    int rc;
-    // (every piece only if it is not there yet: a call that failed half-way is repeated without leaking what it had allocated)
-    if (tk->rx_image[7] && !tk->ht.gc_stage1.empty()) {
-        if (!c->d_gc1 && (rc = dev_upload(tk->ht.gc_stage1, &c->d_gc1))) return rc;
-        if (!c->d_gc2 && (rc = dev_upload(tk->ht.gc_stage2, &c->d_gc2))) return rc;
-    }
-    if (!c->d_rx_status) {
-        HIP_TRY(hipMalloc((void**)&c->d_rx_status, 64));
-        HIP_TRY(hipMemset(c->d_rx_status, 0, 64));
-    }
-    if (!c->h_rx_status) {
-        HIP_TRY(hipHostMalloc((void**)&c->h_rx_status, 64, hipHostMallocPortable));
-        c->h_rx_status[0] = 0;
-        void* dp = nullptr;
-        HIP_TRY(hipHostGetDevicePointer(&dp, c->h_rx_status, 0));
-        c->dh_rx_status = (uint32_t*)dp;
-    }
-    if (!c->d_rx_bad) {
-        HIP_TRY(hipMalloc((void**)&c->d_rx_bad, (1 + RX_BAD_CAP) * 4));
-        HIP_TRY(hipMemset(c->d_rx_bad, 0, (1 + RX_BAD_CAP) * 4));
-    }
-    if (!c->h_rx_bad) {
-        HIP_TRY(hipHostMalloc((void**)&c->h_rx_bad, (1 + 2 * RX_BAD_CAP) * 4, hipHostMallocPortable));
-        c->h_rx_bad[0] = 0;
-        void* dp = nullptr;
-        HIP_TRY(hipHostGetDevicePointer(&dp, c->h_rx_bad, 0));
-        c->dh_rx_bad = (uint32_t*)dp;
-    }
-    if (!c->ev_split) HIP_TRY(hipEventCreateWithFlags(&c->ev_split, hipEventDisableTiming));
-    return dev_upload(tk->rx_image, &c->d_rx_image);
-}
-// This batch's status word: the next one of the context's rotation -- cleared by the previous batch's k_rx_mark, or here if that batch launched none
-int rx_next_status(Ctx* c, hipStream_t s) {
-    c->rx_slot = (c->rx_slot + 1) % RX_STATUS_SLOTS;
-    if (!c->rx_next_clean) HIP_TRY(hipMemsetAsync(c->d_rx_status + c->rx_slot, 0, 4, s));
-    c->rx_next_clean = false;
-    return SPL_OK;
-}
-int rx_launch(spl_tokenizer* tk, Ctx* c, const uint8_t* d_text, uint64_t n_bytes, const uint64_t* d_doc_off, uint64_t n_docs,
-              uint32_t* d_starts, uint32_t* d_gaps, uint32_t* d_status, hipStream_t s, const Batch* sp, uint32_t sp_words, uint32_t* d_status_host,
-              bool bad_sets_status) {
-    if (n_bytes > SPL_DIRECT_MAX_BYTES) return fail(SPL_EINVAL, "device split: at most 256 MB per call");
-    if (((uintptr_t)d_text & 15) != 0) return fail(SPL_EINVAL, "text buffer must be 16-byte aligned");
-    int rc = rx_ensure(tk, c);
-    if (rc) return rc;
-    const uint64_t words = n_bytes / 32 + 2;
-    if (!n_bytes) {                                    // (no block, no kernel: the two closing words by a fill)
-        HIP_TRY(hipMemsetAsync(d_starts, 0, words * 4, s));
-        HIP_TRY(hipMemsetAsync(d_gaps, 0, words * 4, s));
-        return SPL_OK;
-    }
-    const uint64_t nblk = (n_bytes + RXB - 1) / RXB;
-    // workspace, laid out by its CAPACITY in blocks (the per-block entries must stay where they are from call to call -- they are
-    // told apart by generation, not cleared): blk | bskip | bad_hi | bad_lo | dstart | nx | gx
-    if (nblk > c->rx_cap_blk) {
-        HIP_TRY(hipDeviceSynchronize());
-        hipFree(c->d_rx_ws); c->d_rx_ws = nullptr; c->rx_ws_cap = 0; c->rx_cap_blk = 0;
-        const uint64_t cb = nblk + nblk / 4 + 16;
-        const uint64_t cap = 16 * cb + 4 * (8 * cb + 2) + 4 * cb * RXB + 256;
-        HIP_TRY(hipMalloc((void**)&c->d_rx_ws, cap));
-        c->rx_ws_cap = cap; c->rx_cap_blk = cb;
-        c->rx_gen = 0xFFFFu;                           // (fresh memory: cleared below)
-    }
-    // the per-block entries carry the call's generation instead of being cleared per call (two fills of ~5 us each in front of the
-    // kernels of a 1 MB batch); every 65 535 calls -- and on fresh memory -- the workspace is cleared once
-    if (++c->rx_gen > 0xFFFFu) {
-        HIP_TRY(hipMemsetAsync(c->d_rx_ws, 0, c->rx_ws_cap, s));
-        c->rx_gen = 1;
-    }
-    RxArgs a{};
-    a.image = c->d_rx_image; a.image_words = (uint32_t)tk->rx_image.size();
-    a.text = d_text; a.doc_off = d_doc_off; a.n_bytes = (uint32_t)n_bytes; a.n_docs = (uint32_t)n_docs;
-    a.ucls1 = c->dt.ucls_stage1; a.ucls2 = c->dt.ucls_stage2; a.shift = c->dt.ucls_shift;
-    a.gc1 = c->d_gc1; a.gc2 = c->d_gc2;
-    a.blk = (uint32_t*)c->d_rx_ws; a.bskip = a.blk + c->rx_cap_blk; a.bad_hi = a.bskip + c->rx_cap_blk; a.bad_lo = a.bad_hi + c->rx_cap_blk;
-    a.dstart = a.bad_lo + c->rx_cap_blk;
-    a.bad_list = c->d_rx_bad; a.bad_host = c->dh_rx_bad; a.bad_sets_status = bad_sets_status ? 1u : 0u;
-    a.nx = (uint16_t*)(a.dstart + 8 * c->rx_cap_blk + 2); a.gx = a.nx + c->rx_cap_blk * RXB;
-    a.gen = c->rx_gen; a.bm_words = (uint32_t)words;
-    a.starts = d_starts; a.gaps = d_gaps; a.status = d_status; a.status_host = d_status_host;
-    if (d_status >= c->d_rx_status && d_status < c->d_rx_status + RX_STATUS_SLOTS)          // (one of the context's own words: the next one in the rotation)
-    {
-        a.status_next = c->d_rx_status + ((uint32_t)(d_status - c->d_rx_status) + 1) % RX_STATUS_SLOTS;
-        c->rx_next_clean = true;
-    }
-    if (sp) { a.sp_tstart = sp->tstart; a.sp_tbits = sp->tbits; a.sp_words = sp_words; }
-    hipLaunchKernelGGL(k_rx_match, dim3((uint32_t)nblk), dim3(RXT), (a.image_words * 4 + 15) & ~15u, s, a);
-    hipLaunchKernelGGL(k_rx_mark, dim3((uint32_t)nblk), dim3(RXB), 0, s, a);
-    HIP_TRY(hipGetLastError());
-    return SPL_OK;
-}
-
-// ---- custom split patterns: the host splitter over the documents of one pipeline chunk ------------------------
-// Special-token literals on the host, with the reference matcher's semantics (Aho-Corasick, MatchKind::Standard,
-// non-overlapping find_iter, tokenizer.rs:849-869; the same rule k_special_select implements): from the end of the
-// previous match, the occurrence that ENDS first, the longest one on a tie.
-struct SpHit { uint32_t start, len, id; };
-void host_special_find(const spl_tokenizer* tk, const uint8_t* text, size_t n, std::vector<SpHit>& out) {
-    uint8_t last_set[32] = {0};
-    for (const auto& sp : tk->specials) { const uint8_t c = (uint8_t)sp.lit.back(); last_set[c >> 3] |= (uint8_t)(1u << (c & 7)); }
-    size_t last = 0;
-    for (size_t e = 1; e <= n; e++) {
-        const uint8_t c = text[e - 1];
-        if (!((last_set[c >> 3] >> (c & 7)) & 1u)) continue;
-        const Special* best = nullptr;
-        for (const auto& sp : tk->specials) {
-            const size_t len = sp.lit.size();
-            if ((uint8_t)sp.lit.back() != c || len > e - last || (best && len <= best->lit.size())) continue;
-            if (memcmp(text + e - len, sp.lit.data(), len) == 0) best = &sp;
-        }
-        if (!best) continue;
-        out.push_back(SpHit{(uint32_t)(e - best->lit.size()), (uint32_t)best->lit.size(), best->id});
-        last = e;
-    }
-}
-
-inline void host_or_bit(uint32_t* bm, uint64_t pos) { __atomic_fetch_or(&bm[pos >> 5], 1u << (pos & 31), __ATOMIC_RELAXED); }
-
-// One document [lo, hi) of `text` (positions relative to the bitmaps' origin): chunk starts and gaps; with
-// `special`, the literals first -- each a gap with a start bit at either end, its token on `hits` -- and the
-// pattern over the stretches between them (encode_with_special, tokenizer.rs:842-874).
-bool host_split_doc(const spl_tokenizer* tk, const uint8_t* text, uint64_t lo, uint64_t hi, bool special, uint32_t* starts,
-                    uint32_t* gaps, std::vector<SpHit>* hits) {
-    if (hi <= lo) return true;
-    if (!special) return regex_split_bits(*tk->regex, text + lo, (size_t)(hi - lo), lo, starts, gaps);
-    std::vector<SpHit> found;
-    host_special_find(tk, text + lo, (size_t)(hi - lo), found);
-    uint64_t at = lo;
-    for (const SpHit& h : found) {
-        const uint64_t a = lo + h.start, e = a + h.len;
-        if (a > at && !regex_split_bits(*tk->regex, text + at, (size_t)(a - at), at, starts, gaps)) return false;
-        host_or_bit(starts, a);
-        for (uint64_t q = a; q < e; q++) host_or_bit(gaps, q);
-        if (e < hi) host_or_bit(starts, e);
-        hits->push_back(SpHit{(uint32_t)a, h.len, h.id});
-        at = e;
-    }
-    if (hi > at && !regex_split_bits(*tk->regex, text + at, (size_t)(hi - at), at, starts, gaps)) return false;
-    return true;
-}
-
-// Worker threads of the host splitter, kept: a 1 MB batch is 60 pieces of 16 KiB, and starting 59 threads for it took longer
-// than the matching (1.7 ms against 0.2).  One parallel-for at a time (callers queue on run_mu: every caller uses all the
-// workers anyway).  Process-wide, never destroyed (the workers are detached and idle on a condition variable).
-struct WorkPool {
-    std::mutex run_mu, mu;
-    std::condition_variable cv_work, cv_done;
-    unsigned n_threads = 0, want = 0, started = 0, done = 0, gen = 0;
-    const std::function<void(unsigned)>* job = nullptr;
-    void loop() {
-        unsigned seen = 0;
-        std::unique_lock<std::mutex> lk(mu);
-        for (;;) {
-            cv_work.wait(lk, [&] { return gen != seen && started < want; });
-            seen = gen;
-            const unsigned k = ++started;
-            const std::function<void(unsigned)>* f = job;
-            lk.unlock();
-            (*f)(k);
-            lk.lock();
-            if (++done == want) cv_done.notify_one();
-        }
-    }
-    void run(unsigned nt, const std::function<void(unsigned)>& fn) {      // fn(0 .. nt - 1), fn(0) on the calling thread
-        if (nt <= 1) { fn(0); return; }
-        std::lock_guard<std::mutex> one(run_mu);
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            while (n_threads < nt - 1) { std::thread(&WorkPool::loop, this).detach(); n_threads++; }
-            job = &fn; want = nt - 1; started = 0; done = 0; gen++;
-        }
-        cv_work.notify_all();
-        fn(0);
-        std::unique_lock<std::mutex> lk(mu);
-        cv_done.wait(lk, [&] { return done == want; });
-        job = nullptr; want = 0;
-    }
-};
-WorkPool& work_pool() { static WorkPool* p = new WorkPool(); return *p; }
-
-// All documents of a packed text (offsets relative to `text`), on up to `max_threads` threads pulling documents
-// off a shared counter.  The bitmaps must be zeroed and hold n_bytes / 32 + 2 words.
-int host_split_docs(const spl_tokenizer* tk, const uint8_t* text, const uint64_t* off, uint64_t nd, bool special, uint32_t* starts,
-                    uint32_t* gaps, std::vector<SpHit>* hits, unsigned max_threads) {
-    const uint64_t n_bytes = nd ? off[nd] - off[0] : 0;
-    unsigned nt = std::max(1u, std::min<unsigned>(max_threads, std::thread::hardware_concurrency()));
-    nt = (unsigned)std::min<uint64_t>(nt, std::max<uint64_t>(1, std::min<uint64_t>(nd, n_bytes >> 14)));    // >= 16 KiB of text per thread
-    std::atomic<uint64_t> next{0};
-    std::atomic<int> bad{0};
-    std::vector<std::vector<SpHit>> part(nt);
-    const std::function<void(unsigned)> work = [&](unsigned k) {
-        try {
-            for (;;) {
-                const uint64_t d0 = next.fetch_add(16, std::memory_order_relaxed);      // documents in runs of 16
-                if (d0 >= nd || bad.load(std::memory_order_relaxed)) return;
-                for (uint64_t d = d0; d < std::min(nd, d0 + 16); d++)
-                    if (!host_split_doc(tk, text, off[d] - off[0], off[d + 1] - off[0], special, starts, gaps, &part[k])) { bad.store(1); return; }
-            }
-        } catch (...) { bad.store(2); }                                 // (std::bad_alloc on a worker: reported, never thrown across the pool)
-    };
-    work_pool().run(nt, work);
-    if (bad.load() == 2) return fail(SPL_EDEVICE, "the host splitter ran out of memory");
-    if (bad.load()) return fail(SPL_EINVAL, "the split pattern ran out of its matching budget on this text (catastrophic backtracking)");
-    if (hits) {
-        for (auto& p : part) hits->insert(hits->end(), p.begin(), p.end());
-        std::sort(hits->begin(), hits->end(), [](const SpHit& a, const SpHit& b) { return a.start < b.start; });
-    }
-    return SPL_OK;
-}
-
-// ---- per-document fallback of the device splitter ------------------------------------------------------------------
-// The blocks k_rx_mark left in the context's pinned list (h_rx_bad: [0] count, then per block two words: the 256-byte block, first << 8 | last position in it
-// that the matcher gave up on -- a match longer than ~1 KB, a runaway attempt): the documents those stretches touch are split HERE, on the calling thread,
-// and their stretch of the two device bitmaps is patched (k_rx_patch, on `s`, behind the device split whose completion the caller has
-// waited for); every other document keeps what the device splitter made.  `rel[0 .. nd]`: the documents' offsets relative to the
-// bitmaps' origin; text_of(d): the first byte of document d on the host.  Up to round 4 ONE such position sent the whole batch through
-// the host splitter ("a 5x cliff triggered by a single base64 blob").  Reference semantics: tokenizer.rs:729-808.
-template <class TextOf>
-int rx_patch_docs(spl_tokenizer* tk, Ctx* c, const uint64_t* rel, uint64_t nd, bool special, uint32_t* d_starts, uint32_t* d_gaps,
-                  hipStream_t s, TextOf text_of, uint64_t* n_patched) {
-    const uint32_t nb = std::min<uint32_t>(c->h_rx_bad[0], RX_BAD_CAP);
-    std::vector<uint64_t> docs;
-    for (uint32_t i = 0; i < nb; i++) {
-        // the (non-empty) documents that overlap [first, last] -- the positions of the listed block at which the matcher gave up
-        const uint32_t blk = c->h_rx_bad[1 + 2 * i], e = c->h_rx_bad[2 + 2 * i];
-        const uint64_t lo = (uint64_t)blk * RXB + ((e >> 8) & 255u), hi = (uint64_t)blk * RXB + (e & 255u) + 1;
-        uint64_t d = (uint64_t)(std::upper_bound(rel + 1, rel + nd + 1, lo) - (rel + 1));      // first d with rel[d + 1] > lo
-        for (; d < nd && rel[d] < hi; d++)
-            if (rel[d + 1] > rel[d]) docs.push_back(d);
-    }
-    std::sort(docs.begin(), docs.end());
-    docs.erase(std::unique(docs.begin(), docs.end()), docs.end());
-    *n_patched = docs.size();
-    if (docs.empty()) return SPL_OK;
-    std::vector<uint32_t> patch, at;
-    std::vector<SpHit> hits;
-    for (uint64_t d : docs) {
-        const uint64_t lo = rel[d], hi = rel[d + 1];
-        const uint64_t w0 = lo >> 5, n = ((hi - 1) >> 5) - w0 + 1;
-        TRACE("device split gave up inside document %llu [%llu, %llu): split on the host, %llu bitmap words patched", (unsigned long long)d,
-              (unsigned long long)lo, (unsigned long long)hi, (unsigned long long)n);
-        at.push_back((uint32_t)patch.size());
-        const size_t h = patch.size();
-        patch.resize(h + 4 + 2 * n + 2, 0u);                     // (+ 2: the bit of position hi may fall into the word behind)
-        patch[h] = (uint32_t)w0; patch[h + 1] = (uint32_t)n;
-        patch[h + 2] = 0xFFFFFFFFu << (lo & 31);
-        patch[h + 3] = (hi & 31) ? (1u << (hi & 31)) - 1u : 0xFFFFFFFFu;
-        std::vector<uint32_t> st(n + 1, 0u), gp(n + 1, 0u);
-        const uint64_t lo_b = lo - w0 * 32;                      // the document's first bit in these words
-        const uint8_t* base = text_of(d) - lo_b;                 // (indexed by bit position: base + lo_b is the document's first byte)
-        if (!host_split_doc(tk, base, lo_b, lo_b + (hi - lo), special, st.data(), gp.data(), &hits))
-            return fail(SPL_EINVAL, "the split pattern ran out of its matching budget on this text (catastrophic backtracking)");
-        memcpy(&patch[h + 4], st.data(), n * 4);
-        memcpy(&patch[h + 4 + n], gp.data(), n * 4);
-    }
-    const size_t need = patch.size() + at.size();
-    if (need > c->rx_patch_cap) {
-        HIP_TRY(hipStreamSynchronize(s));
-        hipFree(c->d_rx_patch); c->d_rx_patch = nullptr; c->rx_patch_cap = 0;
-        HIP_TRY(hipMalloc((void**)&c->d_rx_patch, (need + need / 2 + 1024) * 4));
-        c->rx_patch_cap = need + need / 2 + 1024;
-    }
-    // (pageable -> device, blocking: the stream's earlier work -- the device split -- is through, the patch kernel follows on it)
-    HIP_TRY(hipMemcpy(c->d_rx_patch, patch.data(), patch.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->d_rx_patch + patch.size(), at.data(), at.size() * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_rx_patch, dim3((uint32_t)docs.size()), dim3(256), 0, s, d_starts, d_gaps, (const uint32_t*)c->d_rx_patch,
-                       (const uint32_t*)(c->d_rx_patch + patch.size()));
-    HIP_TRY(hipGetLastError());
-    return SPL_OK;
-}
-
-// A custom-pattern handle with its text in HBM (spl_encode_batch_device / _packed): the device splitter and the tile kernel in one go,
-// then ONE stream synchronisation to read the splitter's status word; when the matcher gave up (rare: a match longer than ~1 KB) the text
-// goes to the host once, is split there (special-token literals included) and the encode runs again on those boundaries.
-int encode_device_custom(spl_tokenizer* t, Ctx* c, const uint8_t* d_utf8, uint64_t n_bytes, const uint64_t* d_doc_off, uint64_t n_docs,
-                         uint32_t flags, uint32_t* d_ids, uint64_t ids_cap, uint64_t* d_out_off, hipStream_t s, const SlabOut* so) {
-    if (n_bytes > SPL_DIRECT_MAX_BYTES) return fail(SPL_EINVAL, "spl_encode_batch_device: a custom split pattern takes at most 256 MB per device call");
-    const uint64_t bw = n_bytes / 32 + 4;
-    if (2 * bw > c->rx_bits_cap) {
-        HIP_TRY(hipDeviceSynchronize());
-        hipFree(c->d_rx_bits); c->d_rx_bits = nullptr; c->rx_bits_cap = 0;
-        const uint64_t cap = 2 * bw + bw / 2;
-        HIP_TRY(hipMalloc((void**)&c->d_rx_bits, cap * 4));
-        c->rx_bits_cap = cap;
-    }
-    ExtIn ext;
-    ext.d_starts = c->d_rx_bits; ext.d_gaps = c->d_rx_bits + bw;
-    if (t->rx_device && !t->rx_image.empty()) {
-        int rc = rx_ensure(t, c);
-        if (rc) return rc;
-        rc = rx_next_status(c, s);
-        if (rc) return rc;
-        ext.d_status = c->d_rx_status + c->rx_slot;
-        // optimistic: splitter and tile kernel go out together, ONE synchronisation to read what the splitter gave up on -- except with special
-        // tokens (the literal scan's bitmap would keep the first tile pass's bits): there the splitter goes first, the tile kernel behind the check
-        const bool two_phase = (flags & SPL_WITH_SPECIAL) && !t->specials.empty();
-        rc = launch_all(t, c, d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_cap, d_out_off, s, so, &ext, two_phase ? 1 : 0);
-        if (rc) return rc;
-        uint32_t gave_up = 1;
-        HIP_TRY(hipMemcpyAsync(&gave_up, c->d_rx_status + c->rx_slot, 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (!gave_up && c->h_rx_bad[0] == 0) {
-            if (two_phase) { rc = launch_all(t, c, d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_cap, d_out_off, s, so, &ext, 2); if (rc) return rc; HIP_TRY(hipStreamSynchronize(s)); }
-            return SPL_OK;
-        }
-        if (!gave_up) {
-            // a few documents hold something the device matcher gives up on: THEIR text comes to the host, is split there, their stretch of
-            // the bitmaps is patched and the tile kernel runs again on the patched bitmaps (the device split itself is not repeated)
-            std::vector<uint64_t> off(n_docs + 1);
-            HIP_TRY(hipMemcpy(off.data(), d_doc_off, (n_docs + 1) * 8, hipMemcpyDeviceToHost));
-            std::vector<std::vector<uint8_t>> keep;
-            hipError_t cerr = hipSuccess;
-            auto text_of = [&](uint64_t d) -> const uint8_t* {
-                keep.emplace_back((size_t)(off[d + 1] - off[d]) + 16);
-                const hipError_t e = hipMemcpy(keep.back().data(), d_utf8 + off[d], (size_t)(off[d + 1] - off[d]), hipMemcpyDeviceToHost);
-                if (e != hipSuccess) cerr = e;
-                return keep.back().data();
-            };
-            uint64_t n_patched = 0;
-            const bool special = (flags & SPL_WITH_SPECIAL) && !t->specials.empty();
-            rc = rx_patch_docs(t, c, off.data(), n_docs, special, c->d_rx_bits, c->d_rx_bits + bw, s, text_of, &n_patched);
-            if (rc) return rc;
-            if (cerr != hipSuccess) return fail(SPL_EDEVICE, std::string("hipMemcpy: ") + hipGetErrorString(cerr));
-            t->rx_fallbacks += n_patched;
-            rc = launch_all(t, c, d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_cap, d_out_off, s, so, &ext, 2);
-            if (rc) return rc;
-            HIP_TRY(hipStreamSynchronize(s));
-            return SPL_OK;
-        }
-        t->rx_fallbacks += n_docs;              // the whole batch (the list of blocks overflowed, or walks that never fall into step)
-        ext.d_status = nullptr;
-    }
-    const bool special = (flags & SPL_WITH_SPECIAL) && !t->specials.empty();
-    std::vector<uint8_t> text(n_bytes + 16);
-    std::vector<uint64_t> off(n_docs + 1);
-    if (n_bytes) HIP_TRY(hipMemcpyAsync(text.data(), d_utf8, n_bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(off.data(), d_doc_off, (n_docs + 1) * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    std::vector<uint32_t> bits(2 * bw, 0u);
-    std::vector<SpHit> hits;
-    int rc = host_split_docs(t, text.data(), off.data(), n_docs, special, bits.data(), bits.data() + bw, &hits, 128);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(c->d_rx_bits, bits.data(), 2 * bw * 4, hipMemcpyHostToDevice, s));
-    uint32_t* d_hits = nullptr;
-    std::vector<uint32_t> hp;
-    if (!hits.empty()) {
-        const uint64_t n = hits.size();
-        hp.resize(2 * n);
-        for (uint64_t i = 0; i < n; i++) { hp[i] = hits[i].start; hp[n + i] = hits[i].id; }
-        HIP_TRY(hipMalloc((void**)&d_hits, n * 8));
-        if (hipMemcpyAsync(d_hits, hp.data(), n * 8, hipMemcpyHostToDevice, s) != hipSuccess) { hipFree(d_hits); return fail(SPL_EDEVICE, "hipMemcpyAsync failed"); }
-        ext.d_sp_pos = d_hits; ext.d_sp_id = d_hits + n; ext.n_sp = (uint32_t)n;
-    }
-    rc = launch_all(t, c, d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_cap, d_out_off, s, so, &ext);
-    const hipError_t se = hipStreamSynchronize(s);           // (the vectors and the list die with this frame)
-    if (d_hits) hipFree(d_hits);
-    if (rc) return rc;
-    if (se != hipSuccess) return fail(SPL_EDEVICE, std::string("hipStreamSynchronize: ") + hipGetErrorString(se));
-    return SPL_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Host pipeline.
-//
-// A batch is cut into LANES (one per GPU context: contiguous byte ranges of about equal size, cut at
-// document boundaries or -- inside a large document -- behind a newline that is followed by an ASCII
-// letter or digit, a context-free match boundary of every supported pattern, see is_sync rule (d))
-// and every lane into CHUNKS of whole documents.  Per chunk: [host copy into pinned staging unless
-// the caller's buffer is pinned] -> H2D on the copy stream -> kernels on the compute stream -> its
-// token count back to the host.  The consumer walks the chunks in global order: as soon as a chunk's
-// count is known its place in the result is known, and its ids and (rebased) offsets are copied
-// straight into the pinned result on the D2H stream.  Three slots per GPU keep H2D, kernels and D2H
-// of consecutive chunks in flight together.
-struct Chunk {
-    uint64_t lo, hi;             // byte range in the caller's text
-    uint64_t dlo, dhi;           // caller's documents [dlo, dhi) have bytes in it (or start at its end, last chunk of the batch)
-    bool cont;                   // the first of them started before `lo` (continuation piece: contributes no offset entry)
-    uint64_t oo_at;              // first entry of its local output offsets in the lane's d_oo
-};
-struct Lane {
-    Ctx* c = nullptr;
-    uint64_t lo = 0, hi = 0;
-    std::vector<Chunk> chunks;
-    std::atomic<uint32_t> submitted{0};
-    std::atomic<int> rc{0};
-    std::string err;
-    bool host_split = true;      // custom pattern: the split of this lane's chunks runs on the host cores (false: k_rx_match / k_rx_mark)
-    uint64_t patched = 0;        // documents of this lane that the device splitter gave up on and the host split instead
-};
-
-bool is_pinned_host(const void* p) {
-    if (!p) return false;
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeHost;
-}
-
-bool ascii_alnum(uint8_t c) { return (c >= '0' && c <= '9') || ((c | 0x20) >= 'a' && (c | 0x20) <= 'z'); }
-
-// documents that have bytes in [lo, hi): first and one-past-last; `last` = the batch's last range also
-// takes the (empty) documents that start at its end
-void doc_range(const uint64_t* doc_off, uint64_t n_docs, uint64_t lo, uint64_t hi, bool last, uint64_t& dlo, uint64_t& dhi, bool& cont) {
-    // first document that starts at or after lo; if the one before it reaches beyond lo, that one is first
-    const uint64_t* b = std::lower_bound(doc_off, doc_off + n_docs, lo);
-    dlo = (uint64_t)(b - doc_off);
-    cont = false;
-    if (dlo > 0 && doc_off[dlo] > lo) { dlo--; cont = true; }        // doc_off[dlo] < lo < doc_off[dlo + 1]
-    if (last) dhi = n_docs;
-    else dhi = (uint64_t)(std::lower_bound(doc_off, doc_off + n_docs, hi) - doc_off);      // documents starting at hi belong to the next range
-    if (dhi < dlo) dhi = dlo;
-}
-
-int lane_prepare(spl_tokenizer* tk, Lane& ln, const uint64_t* doc_off, uint64_t n_docs, bool last_lane, uint64_t chunk_target,
-                 bool src_pinned) {
-    Ctx* c = ln.c;
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = ensure_streams(*c);
-    if (rc) return rc;
-    // chunks of whole documents (the lane's first and last document may be pieces)
-    uint64_t dlo, dhi; bool cont;
-    doc_range(doc_off, n_docs, ln.lo, ln.hi, last_lane, dlo, dhi, cont);
-    auto start_of = [&](uint64_t d) { return std::max(doc_off[d], ln.lo); };
-    auto end_of = [&](uint64_t d) { return std::min(doc_off[d + 1], ln.hi); };
-    uint64_t max_bytes = 0, max_docs = 0, oo_words = 0;
-    const uint64_t small = std::max<uint64_t>(chunk_target / 4, 512ull << 10);
-    const bool ramp = tk->chunk_ramp && ln.hi - ln.lo >= 2 * chunk_target && chunk_target >= (2ull << 20);
-    uint64_t d = dlo;
-    do {
-        Chunk ch{};
-        ch.dlo = d;
-        ch.lo = d < dhi ? start_of(d) : ln.lo;
-        ch.cont = (d == dlo) && cont;
-        uint64_t e = d;
-        // (the lane's first and last chunk are a quarter of the others: what nothing overlaps is the first chunk's H2D and the
-        //  last one's D2H -- 153 + 164 us of a 1.7 ms call on C3 with five equal chunks, profiles/r05_host_timeline.txt.  Round 2
-        //  had measured such a ramp as no better, when a chunk cost ~80 us of host-side API work and the kernels were half as fast.)
-        uint64_t lim = chunk_target;
-        if (ramp && d < dhi) {
-            const uint64_t rem = ln.hi - ch.lo;
-            if (d == dlo) lim = small;
-            else if (rem <= small + small / 2) lim = rem;
-            else if (rem <= chunk_target + small) lim = rem - small;
-        }
-        while (e < dhi && (e == d || end_of(e) - ch.lo <= lim)) e++;
-        ch.dhi = e;
-        ch.hi = e > d ? end_of(e - 1) : ch.lo;
-        if (e == dhi) ch.hi = ln.hi;
-        if (ch.hi - ch.lo > 0x7FFF0000ull) return fail(SPL_EINVAL, "spl_encode_batch: a single document exceeds 2^31 bytes");
-        ch.oo_at = oo_words;
-        oo_words += (ch.dhi - ch.dlo) + 1;
-        max_bytes = std::max(max_bytes, ch.hi - ch.lo);
-        max_docs = std::max(max_docs, ch.dhi - ch.dlo);
-        ln.chunks.push_back(ch);
-        d = e;
-    } while (d < dhi);
-    // device staging and the lane's result buffers
-    if (max_bytes > c->slot_cap_bytes || max_docs > c->slot_cap_docs || !c->d_text[0]) {
-        HIP_TRY(hipDeviceSynchronize());
-        c->free_slots();
-        const uint64_t nb = std::max(max_bytes, c->slot_cap_bytes), nd = std::max(max_docs, c->slot_cap_docs);
-        for (int i = 0; i < NSLOT; i++) {
-            HIP_TRY(hipMalloc((void**)&c->d_text[i], nb + 64));
-            HIP_TRY(hipMalloc((void**)&c->d_off[i], (nd + 1) * 8));
-        }
-        c->slot_cap_bytes = nb; c->slot_cap_docs = nd;
-    }
-    const uint64_t lane_bytes = ln.hi - ln.lo;
-    if (lane_bytes + 16 > c->ids_cap) {
-        HIP_TRY(hipDeviceSynchronize());
-        hipFree(c->d_ids); c->d_ids = nullptr;
-        c->ids_cap = lane_bytes + lane_bytes / 8 + 4096;
-        HIP_TRY(hipMalloc((void**)&c->d_ids, c->ids_cap * 4));
-    }
-    if (oo_words > c->oo_cap) {
-        HIP_TRY(hipDeviceSynchronize());
-        hipFree(c->d_oo); c->d_oo = nullptr;
-        c->oo_cap = oo_words + oo_words / 8 + 1024;
-        HIP_TRY(hipMalloc((void**)&c->d_oo, c->oo_cap * 8));
-    }
-    for (int i = 0; i < NSLOT && (size_t)i < ln.chunks.size(); i++) {
-        if (!src_pinned && !c->h_text[i].ensure(tk->pool, max_bytes + 64)) return fail(SPL_EDEVICE, "pinned staging allocation failed");
-        if (!c->h_off[i].ensure(tk->pool, (max_docs + 1) * 8)) return fail(SPL_EDEVICE, "pinned staging allocation failed");
-    }
-    {
-        if (!c->h_oo.ensure(tk->pool, oo_words * 8)) return fail(SPL_EDEVICE, "pinned staging allocation failed");
-        void* dp = nullptr;
-        HIP_TRY(hipHostGetDevicePointer(&dp, c->h_oo.p, 0));
-        c->dh_oo = (uint64_t*)dp;
-    }
-    if (tk->regex) {                                         // boundary bitmaps of a chunk: starts | gaps
-        const uint64_t words = 2 * (max_bytes / 32 + 4);
-        if (words > c->ext_cap_words) {
-            HIP_TRY(hipDeviceSynchronize());
-            for (int i = 0; i < NSLOT; i++) { hipFree(c->d_ext[i]); c->d_ext[i] = nullptr; HIP_TRY(hipMalloc((void**)&c->d_ext[i], words * 4)); }
-            c->ext_cap_words = words;
-        }
-        for (int i = 0; i < NSLOT && (size_t)i < ln.chunks.size(); i++)
-            if (!c->h_ext[i].ensure(tk->pool, words * 4)) return fail(SPL_EDEVICE, "pinned staging allocation failed");
-    }
-    while (c->ev_chunk.size() < ln.chunks.size()) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        c->ev_chunk.push_back(e);
-    }
-    if (ln.chunks.size() >= 2 && !c->streams_picked && tk->pick_streams) {
-        // the pipeline's first use on this context: copy streams that run beside the compute stream (and each other) instead of whatever
-        // the runtime handed out -- a D2H of ids that shares the compute stream's pipe slows both
-        HIP_TRY(hipDeviceSynchronize());
-        hipStream_t d2h = nullptr, h2d = nullptr;
-        double cf = 0;
-        if ((rc = pick_stream_beside({c->s_cmp}, &d2h, &cf))) return rc;
-        TRACE("picked the D2H stream (conflict %.1f us)", cf);
-        if ((rc = pick_stream_beside({c->s_cmp, d2h}, &h2d, &cf))) return rc;
-        TRACE("picked the H2D stream (conflict %.1f us)", cf);
-        (void)hipStreamDestroy(c->s_d2h); (void)hipStreamDestroy(c->s_h2d);
-        c->s_d2h = d2h; c->s_h2d = h2d;
-        c->streams_picked = true;
-    }
-    // (not while per-kernel profiling is on: spl_profile_read reports this context's kernels -- with the twin it would cover every other chunk)
-    if (tk->twin_streams && !tk->regex && ln.chunks.size() >= 3 && !c->prof) {
-        if (!c->twin) {
-            c->twin.reset(new Ctx());
-            c->twin->device = c->device;
-            c->twin->dt = c->dt;
-            c->twin->owns_tables = false;
-            if (tk->pick_streams) {
-                HIP_TRY(hipDeviceSynchronize());
-                double cf = 0;
-                if ((rc = pick_stream_beside({c->s_cmp, c->s_d2h, c->s_h2d}, &c->twin->s_cmp, &cf))) return rc;
-                TRACE("picked the twin's compute stream (conflict %.1f us)", cf);
-            } else if ((rc = ensure_streams(*c->twin))) return rc;
-        }
-        if ((rc = reserve(c->twin.get(), max_bytes, max_docs))) return rc;
-    }
-    return reserve(c, max_bytes, max_docs);
-}
-
-// producer: every chunk of one lane, in order (runs in the caller's thread for a single chunk)
-int lane_submit(spl_tokenizer* tk, Lane& ln, const uint8_t* utf8, const uint64_t* doc_off, uint32_t flags, bool src_pinned,
-                bool solo = false, uint32_t* ids_direct = nullptr, bool mapped = false) {
-    Ctx* c = ln.c;
-    HIP_TRY(hipSetDevice(c->device));
-    for (size_t k = 0; k < ln.chunks.size(); k++) {
-        const Chunk& ch = ln.chunks[k];
-        const int sl = (int)(k % NSLOT);
-        Ctx* const w = (!solo && c->twin && !c->prof && (k & 1)) ? c->twin.get() : c;     // whose workspace and compute stream run this chunk's kernels
-        const uint64_t nb = ch.hi - ch.lo, nd = ch.dhi - ch.dlo;
-        TRACE("submit dev %d chunk %zu/%zu bytes %llu docs %llu", c->device, k, ln.chunks.size(), (unsigned long long)nb, (unsigned long long)nd);
-        if (k >= NSLOT) HIP_TRY(hipEventSynchronize(c->ev_h2d[sl]));     // the slot's pinned staging has been read
-        uint64_t* rel = (uint64_t*)c->h_off[sl].p;               // the chunk's documents, clipped to its byte range
-        for (uint64_t i = 0; i < nd; i++) rel[i] = std::min(std::max(doc_off[ch.dlo + i], ch.lo), ch.hi) - ch.lo;
-        rel[nd] = nb;
-        const uint8_t* src = utf8 + ch.lo;
-        if (!src_pinned && nb) {
-            // pageable text into pinned staging: one core copies ~20 GB/s, less than the pipeline behind it takes -- a few of the pool's threads
-            uint8_t* const dst = (uint8_t*)c->h_text[sl].p;
-            const unsigned nt = tk->copy_threads > 1 && nb >= (2ull << 20) ? (unsigned)std::min<uint64_t>(std::min<unsigned>((unsigned)tk->copy_threads, std::max(1u, std::thread::hardware_concurrency())), nb >> 19) : 1u;
-            if (nt <= 1) memcpy(dst, src, nb);
-            else {
-                const uint64_t part = ((nb + nt - 1) / nt + 4095) & ~4095ull;
-                const std::function<void(unsigned)> cp = [&](unsigned q) {
-                    const uint64_t a = std::min<uint64_t>(nb, q * part), e = std::min<uint64_t>(nb, a + part);
-                    if (e > a) memcpy(dst + a, src + a, e - a);
-                };
-                work_pool().run(nt, cp);
-            }
-            src = dst;
-        }
-        if (k >= NSLOT) HIP_TRY(hipStreamWaitEvent(c->s_h2d, c->ev_cmp[sl], 0));   // the slot's device text has been consumed
-        // (a batch of ONE chunk has nothing to overlap: its copies go on the compute stream, no event in between)
-        hipStream_t hs = solo ? c->s_cmp : c->s_h2d;
-        // ("direct_read": the one chunk of a batch whose text is pinned is not copied at all -- the tile kernel reads text and offsets over PCIe)
-        const uint8_t* text_arg = c->d_text[sl];
-        const uint64_t* off_arg = c->d_off[sl];
-        if (mapped && solo && nb) {
-            void *tp = nullptr, *op = nullptr;
-            HIP_TRY(hipHostGetDevicePointer(&tp, (void*)src, 0));
-            HIP_TRY(hipHostGetDevicePointer(&op, rel, 0));
-            text_arg = (const uint8_t*)tp; off_arg = (const uint64_t*)op;
-            // (text that arrives over PCIe while the kernel runs: the tiles of the fused mode would wait for the last of it, polling -- 94 against 86 us
-            //  per 1 MB call; with the text copied first it is 92 fused against 95.  profiles/r06_surface_bisect.txt)
-            c->fuse_off = true;
-        } else {
-        if (nb) HIP_TRY(hipMemcpyAsync(c->d_text[sl], src, nb, hipMemcpyHostToDevice, hs));
-        HIP_TRY(hipMemcpyAsync(c->d_off[sl], rel, (nd + 1) * 8, hipMemcpyHostToDevice, hs));
-        }
-        if (!solo) {
-            HIP_TRY(hipEventRecord(c->ev_h2d[sl], c->s_h2d));
-            HIP_TRY(hipStreamWaitEvent(w->s_cmp, c->ev_h2d[sl], 0));
-        }
-        uint64_t* oo = c->d_oo + ch.oo_at;
-        if (!solo) { w->off_host = c->dh_oo + ch.oo_at; w->off_host_written = false; }
-        c->solo_text = text_arg; c->solo_off = off_arg;          // (a one-chunk batch: where its tile kernel read text and offsets -- the per-document redo reads them again)
-        ExtIn ext;
-        if (tk->regex) {
-            // custom pattern: the chunk's boundaries from the host splitter (this lane's producer thread plus helpers,
-            // while the previous chunks are on the GPU), uploaded behind the text
-            const uint64_t bw = nb / 32 + 4;
-            ext.d_starts = c->d_ext[sl]; ext.d_gaps = c->d_ext[sl] + bw;
-            const bool special = (flags & SPL_WITH_SPECIAL) && !tk->specials.empty();
-            std::vector<SpHit> hits;
-            if (!ln.host_split) {
-                // ... or from the device splitter, on the compute stream behind the text's arrival; what it gives up on is
-                // on the context's status word when the batch is done (encode_host then runs the batch again, split on the host)
-                ext.d_status = c->d_rx_status + c->rx_slot;    // (launch_all runs the splitter, behind the special-token scan)
-                ext.d_status_host = c->dh_rx_status;           // (k_rx_mark leaves what was given up on in the pinned word: no copy back)
-            } else {
-            uint32_t* hb = (uint32_t*)c->h_ext[sl].p;
-            memset(hb, 0, 2 * bw * 4);
-            int rcs = host_split_docs(tk, utf8 + ch.lo, rel, nd, special, hb, hb + bw, &hits, 128);
-            if (rcs) return rcs;
-            HIP_TRY(hipMemcpyAsync(c->d_ext[sl], hb, 2 * bw * 4, hipMemcpyHostToDevice, hs));
-            }
-            if (!hits.empty()) {
-                const uint64_t n = hits.size();
-                if (n > c->extsp_cap) {
-                    HIP_TRY(hipDeviceSynchronize());
-                    const uint64_t cap = n + n / 2 + 1024;
-                    for (int i = 0; i < NSLOT; i++) { hipFree(c->d_extsp[i]); c->d_extsp[i] = nullptr; HIP_TRY(hipMalloc((void**)&c->d_extsp[i], cap * 8)); }
-                    c->extsp_cap = cap;
-                }
-                if (!c->h_extsp[sl].ensure(tk->pool, c->extsp_cap * 8)) return fail(SPL_EDEVICE, "pinned staging allocation failed");
-                uint32_t* hp = (uint32_t*)c->h_extsp[sl].p;
-                for (uint64_t i = 0; i < n; i++) { hp[i] = hits[i].start; hp[n + i] = hits[i].id; }
-                HIP_TRY(hipMemcpyAsync(c->d_extsp[sl], hp, n * 8, hipMemcpyHostToDevice, hs));
-                ext.d_sp_pos = c->d_extsp[sl]; ext.d_sp_id = c->d_extsp[sl] + n; ext.n_sp = (uint32_t)n;
-            }
-            if (!solo) {                                         // (the bitmaps went out behind the text's event: a second one)
-                HIP_TRY(hipEventRecord(c->ev_h2d[sl], c->s_h2d));
-                HIP_TRY(hipStreamWaitEvent(c->s_cmp, c->ev_h2d[sl], 0));
-            }
-        }
-        int rc;
-        const bool sp_flag = (flags & SPL_WITH_SPECIAL) && !tk->specials.empty();
-        if (tk->regex && !ln.host_split && (!solo || sp_flag)) {
-            // (a one-chunk batch runs optimistically instead -- splitter and tile kernel out together, one more tile pass if a document needs
-            //  it: encode_host --, except with special tokens: the first tile pass would leave token bits in the bitmap the literal scan has
-            //  written, which only a fill per call clears)
-            // device split of a pipeline chunk, per-document fallback: the splitter first; the producer waits for it (the GPU has the
-            // previous chunk's tile kernel to run meanwhile), has the documents of the listed blocks split on the host -- normally none --
-            // and their bits patched, then the tile kernel follows
-            rc = launch_all(tk, c, text_arg, nb, off_arg, nd, flags, ids_direct ? ids_direct : c->d_ids + (ch.lo - ln.lo), nb + 16, oo, c->s_cmp,
-                            nullptr, &ext, 1);
-            if (rc) return rc;
-            HIP_TRY(hipEventRecord(c->ev_split, c->s_cmp));
-            HIP_TRY(hipEventSynchronize(c->ev_split));
-            if (c->h_rx_status[0] == 0 && c->h_rx_bad[0] != 0) {
-                const uint64_t bw = nb / 32 + 4;
-                const uint8_t* const ctext = utf8 + ch.lo;
-                uint64_t n_patched = 0;
-                rc = rx_patch_docs(tk, c, rel, nd, (flags & SPL_WITH_SPECIAL) && !tk->specials.empty(), c->d_ext[sl], c->d_ext[sl] + bw, c->s_cmp,
-                                   [&](uint64_t d) { return ctext + rel[d]; }, &n_patched);
-                if (rc) return rc;
-                ln.patched += n_patched;
-                c->h_rx_bad[0] = 0;                          // (dealt with: the one-chunk caller looks at it again)
-            }
-            rc = launch_all(tk, c, text_arg, nb, off_arg, nd, flags, ids_direct ? ids_direct : c->d_ids + (ch.lo - ln.lo), nb + 16, oo, c->s_cmp,
-                            nullptr, &ext, 2);
-        } else
-            rc = launch_all(tk, w, text_arg, nb, off_arg, nd, flags, ids_direct ? ids_direct : c->d_ids + (ch.lo - ln.lo),
-                            nb + 16, oo, w->s_cmp, nullptr, tk->regex ? &ext : nullptr);
-        c->fuse_off = false;
-        if (rc) return rc;
-        if (solo) break;                                   // (the batch is ONE chunk: the caller finishes on the compute stream itself)
-        HIP_TRY(hipEventRecord(c->ev_cmp[sl], w->s_cmp));
-        // (the chunk's local offsets -- the last one is its token count -- are in pinned memory when the event fires: k_tile_out has written
-        //  them there beside the device copy; up to round 4 an 8-byte copy fetched the count, a kernel rebased the offsets on the device and
-        //  a second copy brought them back: three small operations and their launch gaps per chunk on the streams the kernels wait behind)
-        if (!w->off_host_written) HIP_TRY(hipMemcpyAsync((uint64_t*)c->h_oo.p + ch.oo_at, oo, (nd + 1) * 8, hipMemcpyDeviceToHost, w->s_cmp));
-        w->off_host = nullptr;
-        HIP_TRY(hipEventRecord(c->ev_chunk[k], w->s_cmp));
-        ln.submitted.store((uint32_t)k + 1, std::memory_order_release);
-    }
-    return SPL_OK;
-}
-
-// ---- the latency path: a batch of a few KB (Tokenizer.encode(text), src/python/bindings.rs:254-256 -> tokenizer.rs:729-808) ----------
-// A 1 KB text through the pipeline below cost 47 us, of which the tile kernel's chain of phases is 17: two H2D copies (text, offsets), two
-// launches, a stream synchronisation and ~10 us of host-side set-up around them.  Here: the text and its offsets are copied by the CPU
-// into ONE small pinned buffer that the tile kernel reads where it lies (over PCIe: a handful of cache lines), k_tile_out writes ids and
-// offsets straight into the pinned result and -- its last workgroup, behind a system-scope fence -- a completion word the host spins on.
-// No copy engine, no event, no hipStreamSynchronize (every 256th call synchronises the stream so that the runtime retires its signals).
-constexpr uint64_t SMALL_MAX_BYTES = 4096, SMALL_MAX_DOCS = 256;
-constexpr size_t SMALL_TEXT = SMALL_MAX_BYTES + 64, SMALL_OFF = (SMALL_MAX_DOCS + 1) * 8;
-void* dev_ptr_cached(Ctx* c, void* host) {
-    for (int i = 0; i < 2; i++) if (c->dp_host[i] == host) return c->dp_dev[i];
-    void* d = nullptr;
-    if (hipHostGetDevicePointer(&d, host, 0) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-    c->dp_host[1] = c->dp_host[0]; c->dp_dev[1] = c->dp_dev[0];
-    c->dp_host[0] = host; c->dp_dev[0] = d;
-    return d;
-}
-int encode_small(spl_tokenizer* tk, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, uint32_t flags, spl_result* r) {
-    Ctx* c = tk->ctx[0].get();
-    const uint64_t n_bytes = doc_off[n_docs];
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = ensure_streams(*c);
-    if (rc) return rc;
-    if (!c->h_small) {
-        HIP_TRY(hipHostMalloc((void**)&c->h_small, SMALL_TEXT + SMALL_OFF + 64, hipHostMallocPortable | hipHostMallocCoherent | hipHostMallocMapped));   // (coherent: the completion word must become visible while the kernel runs)
-        void* dp = nullptr;
-        HIP_TRY(hipHostGetDevicePointer(&dp, c->h_small, 0));
-        c->dh_small = (uint8_t*)dp;
-        memset(c->h_small, 0, SMALL_TEXT + SMALL_OFF + 64);
-    }
-    volatile uint32_t* const done = (volatile uint32_t*)(c->h_small + SMALL_TEXT + SMALL_OFF);
-    memcpy(c->h_small, utf8, n_bytes);
-    memcpy(c->h_small + SMALL_TEXT, doc_off, (n_docs + 1) * 8);
-    if ((rc = reserve(c, std::max<uint64_t>(n_bytes, SMALL_MAX_BYTES), std::max<uint64_t>(n_docs, SMALL_MAX_DOCS)))) return rc;
-    if (n_docs + 1 > c->oo_cap) {
-        HIP_TRY(hipDeviceSynchronize());
-        hipFree(c->d_oo); c->d_oo = nullptr;
-        c->oo_cap = SMALL_MAX_DOCS + 1 + 1024;
-        HIP_TRY(hipMalloc((void**)&c->d_oo, c->oo_cap * 8));
-    }
-    r->pool = tk->pool;
-    r->n_docs = n_docs;
-    r->off = (uint64_t*)tk->pool->get((n_docs + 1) * 8, r->off_cap);
-    r->ids = (uint32_t*)tk->pool->get((n_bytes + 16) * 4, r->ids_cap);      // (tokens <= bytes: the kernel writes into it directly)
-    if (!r->off || !r->ids) return fail(SPL_EDEVICE, "pinned result allocation failed");
-    uint32_t* const d_ids = (uint32_t*)dev_ptr_cached(c, r->ids);
-    uint64_t* const d_off = (uint64_t*)dev_ptr_cached(c, r->off);
-    if (!d_ids || !d_off) return fail(SPL_EDEVICE, "hipHostGetDevicePointer failed");
-    c->off_host = d_off; c->off_host_written = false;
-    c->done_seq = c->done_seq + 1u ? c->done_seq + 1u : 1u;                  // (never 0: the word's resting value)
-    c->done_arm = (uint32_t*)(c->dh_small + SMALL_TEXT + SMALL_OFF); c->done_armed = false;
-    rc = launch_all(tk, c, c->dh_small, n_bytes, (const uint64_t*)(c->dh_small + SMALL_TEXT), n_docs, flags, d_ids, n_bytes + 16, c->d_oo, c->s_cmp);
-    const bool armed = c->done_armed, offs = c->off_host_written;
-    c->off_host = nullptr; c->done_arm = nullptr;
-    if (rc) return rc;
-    if (!offs) HIP_TRY(hipMemcpyAsync(r->off, c->d_oo, (n_docs + 1) * 8, hipMemcpyDeviceToHost, c->s_cmp));
-    bool seen = false;
-    if (armed && offs) {
-        // (a call normally completes in 25-40 us; a GPU that is busy with other work may take longer: after ~2 ms the stream is synchronised instead)
-        const uint32_t want = c->done_seq;
-        for (uint32_t spin = 0; spin < 400000u; spin++) {
-            if (*done == want) { seen = true; break; }
-#if defined(__x86_64__) || defined(__i386__)
-            __builtin_ia32_pause();
-#else
-            std::this_thread::yield();
-#endif
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-    }
-    if (!seen || (++c->small_calls & 255u) == 0u) HIP_TRY(hipStreamSynchronize(c->s_cmp));
-    r->n_tokens = r->off[n_docs];
-    return SPL_OK;
-}
-
-int encode_host(spl_tokenizer* tk, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, uint32_t flags, spl_result* r,
-                bool host_split = true) {
-    HT_T(ht0);
-    const uint64_t n_bytes = doc_off[n_docs];
-    const bool src_pinned = is_pinned_host(utf8);
-    HT_T(hta);
-    HT_ACC(3, ht0, hta);
-    // ---- lanes ----------------------------------------------------------------------------------
-    const size_t nl_max = tk->ctx.size();
-    size_t nl = nl_max;
-    if (n_bytes < (1ull << 20) * nl) nl = std::max<size_t>(1, (size_t)(n_bytes >> 20));      // at least 1 MiB per GPU
-    std::vector<Lane> lanes(nl);
-    const bool may_cut = tk->subdoc && !tk->regex && !((flags & SPL_WITH_SPECIAL) && tk->special_newline);   // (a custom pattern's context-free boundaries are unknown)
-    {
-        uint64_t prev = 0;
-        for (size_t l = 0; l < nl; l++) {
-            lanes[l].c = tk->ctx[l].get();
-            lanes[l].host_split = host_split;
-            lanes[l].lo = prev;
-            uint64_t cutp = n_bytes;
-            if (l + 1 < nl) {
-                const uint64_t target = n_bytes / nl * (l + 1), tol = n_bytes / nl / 16;
-                const uint64_t* b = std::lower_bound(doc_off, doc_off + n_docs + 1, target);
-                const uint64_t after = *b, before = b > doc_off ? *(b - 1) : 0;
-                const uint64_t nearest = (target - before <= after - target) ? before : after;
-                cutp = nearest;
-                const uint64_t dist = nearest > target ? nearest - target : target - nearest;
-                if (dist > tol && may_cut && before < target && target < after) {
-                    // inside one large document: the first newline + ASCII letter / digit at or after the target
-                    const uint64_t lim = std::min<uint64_t>(after, target + (1ull << 20));
-                    for (uint64_t i = std::max<uint64_t>(target, before + 1); i < lim; i++)
-                        if (utf8[i - 1] == '\n' && ascii_alnum(utf8[i])) { cutp = i; break; }
-                }
-                if (cutp < prev) cutp = prev;
-            }
-            lanes[l].hi = cutp;
-            prev = cutp;
-        }
-    }
-    const uint64_t lane_max = [&] { uint64_t m = 0; for (auto& ln : lanes) m = std::max(m, ln.hi - ln.lo); return m; }();
-    uint64_t chunk_target = tk->chunk_bytes;
-    if (lane_max <= tk->single_max) chunk_target = std::max<uint64_t>(tk->single_max, 1);
-    else chunk_target = std::min<uint64_t>(tk->chunk_bytes, std::max<uint64_t>(lane_max / 4, 1ull << 20));
-    if (tk->chunk_bytes < tk->single_max) chunk_target = tk->chunk_bytes;                 // (tests: force small chunks)
-    for (size_t l = 0; l < nl; l++) {
-        int rc = lane_prepare(tk, lanes[l], doc_off, n_docs, l + 1 == nl, chunk_target, src_pinned);
-        if (rc) return rc;
-    }
-    size_t n_chunks = 0;
-    for (auto& ln : lanes) n_chunks += ln.chunks.size();
-    HT_T(htb);
-    HT_ACC(4, hta, htb);
-    TRACE("encode_host: %llu bytes %llu docs, %zu lane(s), %zu chunk(s), target %llu, pinned src %d", (unsigned long long)n_bytes,
-          (unsigned long long)n_docs, nl, n_chunks, (unsigned long long)chunk_target, (int)src_pinned);
-
-    // ---- result buffers -------------------------------------------------------------------------------
-    r->pool = tk->pool;
-    r->n_docs = n_docs;
-    r->off = (uint64_t*)tk->pool->get((n_docs + 1) * 8, r->off_cap);
-    uint64_t est = (tk->est_div == 2 ? n_bytes * 3 / 8 : n_bytes / std::max<uint32_t>(tk->est_div, 1)) + 4096;   // default: 0.375 tokens per byte
-    if (est > n_bytes) est = n_bytes;
-    r->ids = (uint32_t*)tk->pool->get((est + 16) * 4, r->ids_cap);
-    if (!r->off || !r->ids) return fail(SPL_EDEVICE, "pinned result allocation failed");
-
-    // ---- one chunk: everything on the compute stream ---------------------------------------------------
-    HT_T(ht1);
-    HT_ACC(0, ht0, ht1);
-    if (n_chunks == 1) {
-        Lane& ln = lanes[0];
-        Ctx* c = ln.c;
-        const Chunk& ch = ln.chunks[0];
-        const uint64_t nd = ch.dhi - ch.dlo;                          // == n_docs
-        if (tk->direct_write && n_bytes) {
-            // the encoder's last kernel writes the ids straight into the pinned result over PCIe (posted,
-            // coalesced writes that overlap the kernel itself): no D2H copy of the ids, ONE synchronisation.
-            // The result must hold the worst case, one token per byte (the pool recycles it).
-            if (r->ids_cap < (n_bytes + 16) * 4) {
-                tk->pool->put(r->ids, r->ids_cap);
-                r->ids = (uint32_t*)tk->pool->get((n_bytes + 16) * 4, r->ids_cap);
-                if (!r->ids) return fail(SPL_EDEVICE, "pinned result allocation failed");
-            }
-            void* dptr = nullptr;
-            HIP_TRY(hipHostGetDevicePointer(&dptr, r->ids, 0));
-            // ... and the offsets into the pinned result as well: no copy back at all
-            void* optr = nullptr;
-            HIP_TRY(hipHostGetDevicePointer(&optr, r->off, 0));
-            c->off_host = (uint64_t*)optr; c->off_host_written = false;
-            // (not with a custom pattern: the device splitter's kernels read the text as well -- in place it would cross PCIe two or three times:
-            //  216 against 182 us per 1 MB call, profiles/r06_surface_bisect.txt; round 5 had it on: the 5.50 -> 4.99 GB/s of VERDICT r05)
-            const bool mapped = tk->direct_read && src_pinned && ((uintptr_t)(utf8 + ch.lo) & 15) == 0 && !tk->regex;
-            // (completion by k_tile_out's word in pinned memory instead of the stream synchronisation -- what the latency path does for a handful of
-            //  tiles -- was measured here too: 150 us against 93 for the 1 MB batch; 1250 workgroups each pay a system-scope fence.  Not adopted.)
-            int rc = lane_submit(tk, ln, utf8, doc_off, flags, src_pinned, true, (uint32_t*)dptr, mapped);
-            c->off_host = nullptr;
-            if (rc) return rc;
-            if (!c->off_host_written) HIP_TRY(hipMemcpyAsync(r->off, c->d_oo + ch.oo_at, (nd + 1) * 8, hipMemcpyDeviceToHost, c->s_cmp));
-            HT_T(ht2);
-            HT_ACC(1, ht1, ht2);
-            HIP_TRY(hipStreamSynchronize(c->s_cmp));
-            if (tk->regex && !ln.host_split && c->h_rx_status[0] == 0 && c->h_rx_bad[0] != 0) {
-                // the device splitter gave up on a few documents (optimistic run: splitter and tile kernel went out together): split those
-                // on the host, patch their bits, and run the tile kernel once more on the patched bitmaps -- its results overwrite the first run's
-                const uint64_t nb = ch.hi - ch.lo, bw = nb / 32 + 4;
-                const uint64_t* const rel = (const uint64_t*)c->h_off[0].p;
-                const uint8_t* const ctext = utf8 + ch.lo;
-                uint64_t n_patched = 0;
-                rc = rx_patch_docs(tk, c, rel, nd, (flags & SPL_WITH_SPECIAL) && !tk->specials.empty(), c->d_ext[0], c->d_ext[0] + bw, c->s_cmp,
-                                   [&](uint64_t d) { return ctext + rel[d]; }, &n_patched);
-                if (rc) return rc;
-                ExtIn ext;
-                ext.d_starts = c->d_ext[0]; ext.d_gaps = c->d_ext[0] + bw;
-                ext.d_status = c->d_rx_status + c->rx_slot; ext.d_status_host = c->dh_rx_status;
-                c->off_host = (uint64_t*)optr; c->off_host_written = false;
-                rc = launch_all(tk, c, c->solo_text, nb, c->solo_off, nd, flags, (uint32_t*)dptr, nb + 16, c->d_oo + ch.oo_at, c->s_cmp, nullptr, &ext, 2);
-                c->off_host = nullptr;
-                if (rc) return rc;
-                HIP_TRY(hipStreamSynchronize(c->s_cmp));
-                ln.patched = n_patched;
-            }
-            if (ln.patched) { tk->rx_fallbacks += ln.patched; ln.patched = 0; }     // (a one-chunk batch WITH special tokens: patched inside lane_submit)
-            HT_T(ht3);
-            HT_ACC(2, ht2, ht3);
-#ifdef SPL_HOST_TIMING
-            if (++g_htn % 256 == 0) {
-                fprintf(stderr, "[spl host timing] setup %.1f us (pinned? %.1f, lanes %.1f), submit %.1f us, sync wait %.1f us (avg of 256 calls)\n", g_ht[0] / 256, g_ht[3] / 256, g_ht[4] / 256, g_ht[1] / 256, g_ht[2] / 256);
-                for (auto& x : g_ht) x = 0;
-            }
-#endif
-            r->n_tokens = r->off[nd];
-            return SPL_OK;
-        }
-        // ids copied back speculatively (a guess of their number), the rest -- if any -- after the count is known
-        int rc = lane_submit(tk, ln, utf8, doc_off, flags, src_pinned, true);
-        if (rc) return rc;
-        const uint64_t spec = std::min<uint64_t>(r->ids_cap / 4, n_bytes);
-        HIP_TRY(hipMemcpyAsync(r->off, c->d_oo + ch.oo_at, (nd + 1) * 8, hipMemcpyDeviceToHost, c->s_cmp));
-        if (spec) HIP_TRY(hipMemcpyAsync(r->ids, c->d_ids, spec * 4, hipMemcpyDeviceToHost, c->s_cmp));
-        HIP_TRY(hipStreamSynchronize(c->s_cmp));
-        // ("direct_write" 0: this path has no second tile pass to give -- documents the device matcher gave up on send the batch through the
-        //  host splitter as a whole, as a status word would)
-        if (tk->regex && !ln.host_split && c->h_rx_bad[0] != 0) c->h_rx_status[0] |= RXS_REACH;
-        const uint64_t T = r->off[nd];
-        if (T > spec) {                                                // the guess was too small: a bigger buffer, the rest
-            size_t ncap = 0;
-            uint32_t* nids = (uint32_t*)tk->pool->get((T + 16) * 4, ncap);
-            if (!nids) return fail(SPL_EDEVICE, "pinned result allocation failed");
-            memcpy(nids, r->ids, spec * 4);
-            tk->pool->put(r->ids, r->ids_cap);
-            r->ids = nids; r->ids_cap = ncap;
-            HIP_TRY(hipMemcpyAsync(r->ids + spec, c->d_ids + spec, (T - spec) * 4, hipMemcpyDeviceToHost, c->s_cmp));
-            HIP_TRY(hipStreamSynchronize(c->s_cmp));
-        }
-        r->n_tokens = T;
-        return SPL_OK;
-    }
-
-    // ---- several chunks: a producer thread per lane, this thread places the results ------------------
-    // (Tried for one GPU and dropped: "streamed" chunks -- the running token count kept on the device, every
-    //  chunk's last kernel writing ids and offsets straight to their place in the pinned result, no per-chunk
-    //  synchronisation, copies or second thread.  Bit-exact, but 12.5 GB/s against 15.8 on C3 (13.1 / 16.6 on C4):
-    //  50 MB of ids stored over PCIe by the kernel serialise with the next chunk's kernels on the one stream,
-    //  where the D2H copy engine overlaps them.  The one-chunk case above keeps the direct write: there is
-    //  nothing to overlap with.)
-    std::vector<std::thread> producers;
-    struct Joiner {                                         // whatever happens below, no producer outlives the lanes
-        std::vector<std::thread>& v;
-        ~Joiner() { for (auto& th : v) if (th.joinable()) th.join(); }
-    } joiner{producers};
-    for (size_t l = 0; l < nl; l++) {
-        Lane* ln = &lanes[l];
-        producers.emplace_back([=] {
-            g_err.clear();
-            int rc = lane_submit(tk, *ln, utf8, doc_off, flags, src_pinned);
-            if (rc) { ln->err = g_err; ln->rc.store(rc, std::memory_order_release); }
-        });
-    }
-    int rc_all = SPL_OK;
-    std::string err_all;
-    uint64_t base = 0;
-    std::vector<hsa_signal_t> dma_sigs;
-    struct SigGuard { std::vector<hsa_signal_t>& v; ~SigGuard() { for (hsa_signal_t sg : v) { hsa_dma().SignalWait(sg, HSA_SIGNAL_CONDITION_LT, 1, UINT64_MAX, HSA_WAIT_STATE_BLOCKED); hsa_dma().SignalDestroy(sg); } } } sig_guard{dma_sigs};
-    auto consume = [&]() -> int {
-        for (size_t l = 0; l < nl; l++) {
-            Lane& ln = lanes[l];
-            Ctx* c = ln.c;
-            HIP_TRY(hipSetDevice(c->device));
-            const uint64_t* const h_oo = (const uint64_t*)c->h_oo.p;
-            for (size_t k = 0; k < ln.chunks.size(); k++) {
-                while (ln.submitted.load(std::memory_order_acquire) <= k) {
-                    if (ln.rc.load(std::memory_order_acquire)) return fail(ln.rc.load(), ln.err);
-                    std::this_thread::yield();
-                }
-                HIP_TRY(hipEventSynchronize(c->ev_chunk[k]));
-                TRACE("chunk %zu event", k);
-                const Chunk& ch = ln.chunks[k];
-                const uint64_t nd = ch.dhi - ch.dlo, T = h_oo[ch.oo_at + nd];
-                TRACE("place lane %zu chunk %zu tokens %llu base %llu", l, k, (unsigned long long)T, (unsigned long long)base);
-                if ((base + T + 16) * 4 > r->ids_cap) {
-                    // the first guess was too small: move to a buffer that holds whatever may still come
-                    for (size_t q = 0; q <= l; q++) { HIP_TRY(hipSetDevice(lanes[q].c->device)); HIP_TRY(hipStreamSynchronize(lanes[q].c->s_d2h)); }
-                    // (sdma_d2h: the copies queued so far write into the OLD buffer -- they must have landed before it is copied and handed back)
-                    for (hsa_signal_t sg : dma_sigs) { hsa_dma().SignalWait(sg, HSA_SIGNAL_CONDITION_LT, 1, UINT64_MAX, HSA_WAIT_STATE_BLOCKED); hsa_dma().SignalDestroy(sg); }
-                    dma_sigs.clear();
-                    HIP_TRY(hipSetDevice(c->device));
-                    const uint64_t rest = n_bytes - ch.lo;              // tokens <= bytes
-                    size_t ncap = 0;
-                    uint32_t* nids = (uint32_t*)tk->pool->get((base + rest + 16) * 4, ncap);
-                    if (!nids) return fail(SPL_EDEVICE, "pinned result allocation failed");
-                    memcpy(nids, r->ids, base * 4);
-                    tk->pool->put(r->ids, r->ids_cap);
-                    r->ids = nids; r->ids_cap = ncap;
-                }
-                if (T && tk->sdma_d2h && c->hsa_state == 0) c->hsa_state = hsa_agent_of(c->device, &c->hsa_agent) ? 1 : 2;
-                if (T && tk->sdma_d2h && c->hsa_state == 1) {
-                    // (the chunk's kernels are through -- the event above --, so the copy has no dependency; its signal is waited for at the end)
-                    HsaDma& H = hsa_dma();
-                    hsa_signal_t sg;
-                    if (H.SignalCreate(1, 0, nullptr, &sg) != HSA_STATUS_SUCCESS) return fail(SPL_EDEVICE, "hsa_signal_create failed");
-                    if (H.AsyncCopy(r->ids + base, H.cpu, c->d_ids + (ch.lo - ln.lo), c->hsa_agent, T * 4, 0, nullptr, sg) != HSA_STATUS_SUCCESS) {
-                        H.SignalDestroy(sg);
-                        return fail(SPL_EDEVICE, "hsa_amd_memory_async_copy failed");
-                    }
-                    dma_sigs.push_back(sg);
-                } else
-                if (T) HIP_TRY(hipMemcpyAsync(r->ids + base, c->d_ids + (ch.lo - ln.lo), T * 4, hipMemcpyDeviceToHost, c->s_d2h));
-                const uint64_t skip = ch.cont ? 1 : 0;
-                {                                                      // the chunk's offsets, rebased: a few thousand additions on this thread
-                    const uint64_t* const oo = h_oo + ch.oo_at;
-                    uint64_t* const dst = r->off + ch.dlo;
-                    for (uint64_t i = skip; i < nd; i++) dst[i] = oo[i] + base;
-                }
-                base += T;
-            }
-        }
-        TRACE("all placed, waiting for the copies");
-        for (auto& ln : lanes) { HIP_TRY(hipSetDevice(ln.c->device)); HIP_TRY(hipStreamSynchronize(ln.c->s_d2h)); }
-        for (hsa_signal_t sg : dma_sigs) hsa_dma().SignalWait(sg, HSA_SIGNAL_CONDITION_LT, 1, UINT64_MAX, HSA_WAIT_STATE_BLOCKED);
-        return SPL_OK;
-    };
-    TRACE("encode_host: producers started");
-    rc_all = consume();
-    TRACE("encode_host: consumed");
-    if (rc_all) err_all = g_err;
-    for (auto& th : producers) th.join();
-    for (auto& ln : lanes)
-        if (!rc_all && ln.rc.load()) { rc_all = ln.rc.load(); err_all = ln.err; }
-    if (rc_all) {
-        for (auto& ln : lanes) { if (hipSetDevice(ln.c->device) == hipSuccess) (void)hipDeviceSynchronize(); }
-        return fail(rc_all, err_all);
-    }
-    for (auto& ln : lanes) tk->rx_fallbacks += ln.patched;
-    r->off[n_docs] = base;
-    r->n_tokens = base;
-    return SPL_OK;
-}
-
-template <class T> int grow(T** p, uint64_t* cap, uint64_t need) {
-    if (need <= *cap && *p) return SPL_OK;
-    HIP_TRY(hipDeviceSynchronize());
-    hipFree(*p); *p = nullptr;
-    const uint64_t c = need + need / 4 + 1024;
-    HIP_TRY(hipMalloc((void**)p, c * sizeof(T)));
-    *cap = c;
-    return SPL_OK;
-}
-
-}  // namespace
-
-namespace {
-#define NCCL_TRY(expr)                                                                             \
-    do {                                                                                           \
-        ncclResult_t r_ = (expr);                                                                  \
-        if (r_ != ncclSuccess)                                                                     \
-            return fail(SPL_EDEVICE, std::string(#expr) + ": " + rccl().GetErrorString(r_));       \
-    } while (0)
-
-int comm_create(const uint8_t* id, int rank, int world, int device, spl_comm** out) {
-    Rccl& R = rccl();
-    if (!R.lib) return fail(SPL_EDEVICE, "spl_comm_create: " + R.err);
-    HIP_TRY(hipSetDevice(device));
-    std::unique_ptr<spl_comm> c(new spl_comm());
-    c->rank = rank; c->world = world; c->device = device;
-    ncclUniqueId uid;
-    static_assert(sizeof uid.internal == SPL_COMM_ID_BYTES, "SPL_COMM_ID_BYTES must be RCCL's NCCL_UNIQUE_ID_BYTES");
-    memcpy(uid.internal, id, SPL_COMM_ID_BYTES);
-    NCCL_TRY(R.CommInitRank(&c->comm, world, uid, rank));
-    HIP_TRY(hipMalloc((void**)&c->d_cnt, 32));
-    HIP_TRY(hipMalloc((void**)&c->d_cnts, 32 * (size_t)world));
-    HIP_TRY(hipHostMalloc((void**)&c->h_cnts, 32 * (size_t)world, hipHostMallocPortable));
-    *out = c.release();
-    return SPL_OK;
-}
-
-int allgatherv_csr(spl_comm* c, const uint32_t* d_ids, const uint64_t* d_out_off, uint64_t n_docs, uint32_t* d_all_ids,
-                   uint64_t all_ids_cap, uint64_t* d_all_off, uint64_t all_off_cap, uint64_t* n_tokens_total, uint64_t* n_docs_total,
-                   hipStream_t s) {
-    Rccl& R = rccl();
-    HIP_TRY(hipSetDevice(c->device));
-    const int W = c->world;
-    // (1) every rank's {T, N} and the capacities of ITS result buffers: 32 bytes per rank, then the one host
-    // synchronisation of the exchange
-    hipLaunchKernelGGL(k_csr_counts, dim3(1), dim3(64), 0, s, d_out_off, n_docs, all_ids_cap, all_off_cap, c->d_cnt);
-    NCCL_TRY(R.AllGather(c->d_cnt, c->d_cnts, 4, ncclUint64, c->comm, s));
-    HIP_TRY(hipMemcpyAsync(c->h_cnts, c->d_cnts, 32 * (size_t)W, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    RankTable tab{};
-    uint64_t min_ids_cap = ~0ull, min_off_cap = ~0ull;
-    for (int p = 0; p < W; p++) {
-        tab.t_pre[p + 1] = tab.t_pre[p] + c->h_cnts[4 * p];
-        tab.n_pre[p + 1] = tab.n_pre[p] + c->h_cnts[4 * p + 1];
-        min_ids_cap = std::min(min_ids_cap, c->h_cnts[4 * p + 2]);
-        min_off_cap = std::min(min_off_cap, c->h_cnts[4 * p + 3]);
-    }
-    if (n_tokens_total) *n_tokens_total = tab.t_pre[W];
-    if (n_docs_total) *n_docs_total = tab.n_pre[W];
-    // Every rank sees the same totals AND the same (smallest) capacities, so every rank takes the same branch even when
-    // the ranks passed buffers of different sizes: nobody is left waiting in a collective its peer never entered.
-    if (tab.t_pre[W] > min_ids_cap || tab.n_pre[W] + 1 > min_off_cap)
-        return fail(SPL_ECAPACITY, "spl_allgatherv_csr: the global CSR does not fit the smallest buffers any rank gave (" +
-                                   std::to_string(tab.t_pre[W]) + " tokens, " + std::to_string(tab.n_pre[W]) + " documents; capacities " +
-                                   std::to_string(min_ids_cap) + " ids, " + std::to_string(min_off_cap) + " offsets)");
-    // (2) exactly T_r ids and N_r offsets from every rank, each straight to its place: one message per peer and
-    // direction, all links busy at once (xGMI is point to point; no ring, no padding)
-    const uint64_t T = c->h_cnts[4 * c->rank], N = c->h_cnts[4 * c->rank + 1];
-    NCCL_TRY(R.GroupStart());
-    for (int p = 0; p < W; p++) {
-        if (T) NCCL_TRY(R.Send(d_ids, T, ncclUint32, p, c->comm, s));
-        if (N) NCCL_TRY(R.Send(d_out_off, N, ncclUint64, p, c->comm, s));
-        const uint64_t Tp = c->h_cnts[4 * p], Np = c->h_cnts[4 * p + 1];
-        if (Tp) NCCL_TRY(R.Recv(d_all_ids + tab.t_pre[p], Tp, ncclUint32, p, c->comm, s));
-        if (Np) NCCL_TRY(R.Recv(d_all_off + tab.n_pre[p], Np, ncclUint64, p, c->comm, s));
-    }
-    NCCL_TRY(R.GroupEnd());
-    // (3) local offsets -> offsets in the global id array, and the closing entry
-    const uint64_t nmax = [&] { uint64_t m = 1; for (int p = 0; p < W; p++) m = std::max<uint64_t>(m, c->h_cnts[4 * p + 1]); return m; }();
-    hipLaunchKernelGGL(k_rebase_offsets, dim3((uint32_t)std::min<uint64_t>((nmax + 255) / 256, 1024), (uint32_t)W), dim3(256), 0, s,
-                       d_all_off, tab, (uint32_t)W);
-    HIP_TRY(hipGetLastError());
-    return SPL_OK;
-}
-}  // namespace
+#include "spl_host_res.h"
+#include "spl_ctx.h"
+#include "spl_streams.h"
+#include "spl_launch.h"
+#include "spl_host_split.h"
+#include "spl_pipeline.h"
+#include "spl_decode_host.h"
+#include "spl_collective.h"
 
 namespace {
 // No exception crosses the C ABI: every entry point that allocates (std::bad_alloc), starts threads or grows
@@ -2227,6 +119,7 @@ uint32_t spl_n_devices(const spl_tokenizer* t) { return t ? (uint32_t)t->ctx.siz
 int spl_set_option(spl_tokenizer* t, const char* name, int64_t value) {
     if (!t || !name) return fail(SPL_EINVAL, "spl_set_option: null argument");
     const std::string k(name);
+    auto memo_drop_all = [&] { for (auto& c : t->ctx) { c->memo_drop(); if (c->twin) c->twin->memo_drop(); } };      // (a new geometry, or Tokenizer::clear_cache)
     if (k == "chunk_bytes" && value >= 1) t->chunk_bytes = (uint64_t)value;
     else if (k == "single_chunk_max_bytes" && value >= 0) t->single_max = (uint64_t)value;
     else if (k == "result_estimate_div" && value >= 1) t->est_div = (uint32_t)value;
@@ -2243,10 +136,10 @@ int spl_set_option(spl_tokenizer* t, const char* name, int64_t value) {
     else if (k == "range_tiles" && value >= 0 && value < (1 << 24)) t->range_tiles = (uint32_t)value;
     else if (k == "range_streams" && (value == 1 || value == 2)) t->range_streams = (int)value;
     else if (k == "memo") t->memo = value != 0;
-    else if (k == "memo_clear") { for (auto& c : t->ctx) { c->memo_drop(); if (c->twin) c->twin->memo_drop(); } }      // Tokenizer::clear_cache (tokenizer.rs:995-1000)
-    else if (k == "memo_bits" && value >= 4 && value <= 22) { t->memo_bits = (uint32_t)value; for (auto& c : t->ctx) { c->memo_drop(); if (c->twin) c->twin->memo_drop(); } }
-    else if (k == "memo_long_bits" && value >= 0 && value <= 20) { t->memo_long_bits = (uint32_t)value; for (auto& c : t->ctx) { c->memo_drop(); if (c->twin) c->twin->memo_drop(); } }
-    else if (k == "memo_log_cap" && value >= 1 && value <= 65536) { t->memo_log_cap = (uint32_t)value; for (auto& c : t->ctx) { c->memo_drop(); if (c->twin) c->twin->memo_drop(); } }
+    else if (k == "memo_clear") memo_drop_all();               // Tokenizer::clear_cache (tokenizer.rs:995-1000)
+    else if (k == "memo_bits" && value >= 4 && value <= 22) { t->memo_bits = (uint32_t)value; memo_drop_all(); }
+    else if (k == "memo_long_bits" && value >= 0 && value <= 20) { t->memo_long_bits = (uint32_t)value; memo_drop_all(); }
+    else if (k == "memo_log_cap" && value >= 1 && value <= 65536) { t->memo_log_cap = (uint32_t)value; memo_drop_all(); }
     else if (k == "fuse_max_tiles" && value >= 0 && value <= (int64_t)FUSE_MAX_TILES) t->fuse_max_tiles = (uint32_t)value;
     else if (k == "copy_threads" && value >= 1 && value <= 64) t->copy_threads = (int)value;
     else if (k == "decode_chunk_ids" && value >= 1024) t->dec_chunk_ids = (uint64_t)value;
@@ -2359,10 +252,10 @@ int spl_encode_batch(spl_tokenizer* t, const uint8_t* utf8, const uint64_t* doc_
                 int rcx = ensure_streams(*c);
                 if (!rcx) rcx = rx_ensure(t, c.get());
                 if (rcx) return rcx;
-                if (!rcx) rcx = rx_next_status(c.get(), c->s_cmp);   // (this batch's status word: cleared by the previous batch's k_rx_mark)
+                if (!rcx) rcx = rx_next_status(c.get(), c->s_cmp.get());   // (this batch's status word: cleared by the previous batch's k_rx_mark)
                 if (rcx) return rcx;
-                c->h_rx_status[0] = 0;
-                c->h_rx_bad[0] = 0;
+                c->h_rx_status.host()[0] = 0;
+                c->h_rx_bad.host()[0] = 0;
             }
         int rc = encode_host(t, utf8, doc_off, n_docs, flags, r.get(), !dev_split);
         TRACE("spl_encode_batch: encode_host returned %d", rc);
@@ -2372,7 +265,7 @@ int spl_encode_batch(spl_tokenizer* t, const uint8_t* utf8, const uint64_t* doc_
             // (every chunk's split left the status word in the context's pinned copy, in front of the kernels whose completion
             //  encode_host has waited for: nothing to copy or wait for here)
             uint32_t gave_up = 0;
-            for (auto& c : t->ctx) gave_up |= c->h_rx_status[0];
+            for (auto& c : t->ctx) gave_up |= c->h_rx_status.host()[0];
             t->rx_fallbacks += gave_up ? n_docs : 0;
             if (gave_up) {
                 r.reset(new spl_result());
@@ -2403,212 +296,6 @@ void* spl_host_alloc(size_t bytes) {
     return p;
 }
 void spl_host_free(void* p) { if (p) (void)hipHostFree(p); }
-
-// ---- decode of a LARGE batch as a pipeline -------------------------------------------------------------------------------------
-// In one piece (below) a 12.5 M-token batch is 0.9 ms of H2D, 0.3 ms of kernels and 0.75 ms of D2H one after the other.  Here the batch goes
-// in chunks of whole documents through two slots of scratch: the ids of chunk k + 1 travel in and are measured (k_decode_len / k_decode_scan on
-// the compute stream) while chunk k's bytes are gathered (k_decode_copy / k_decode_docs on a second compute stream, picked to run beside the
-// first) and travel out.  The host learns a chunk's byte count from pinned memory, knows where its bytes go in the ONE result, and launches
-// its second half; document offsets leave the device already rebased.
-struct DecOut {
-    std::shared_ptr<PinnedPool> pool; uint8_t* b = nullptr; uint64_t* o = nullptr; size_t bcap = 0, ocap = 0;
-    ~DecOut() { if (b) pool->put(b, bcap); if (o) pool->put(o, ocap); }
-};
-static int decode_pipelined(spl_tokenizer* t, Ctx* c, const uint32_t* ids, const uint64_t* ids_off, uint64_t n_docs, DecOut& o) {
-    struct DC { uint64_t d0, d1; };
-    std::vector<DC> ch;
-    uint64_t max_ids = 0, max_docs = 0;
-    for (uint64_t d = 0; d < n_docs;) {
-        uint64_t e = d + 1;
-        while (e < n_docs && ids_off[e + 1] - ids_off[d] <= t->dec_chunk_ids) e++;
-        ch.push_back(DC{d, e});
-        max_ids = std::max(max_ids, ids_off[e] - ids_off[d]);
-        max_docs = std::max(max_docs, e - d);
-        d = e;
-    }
-    const uint64_t n = ids_off[n_docs] - ids_off[0];
-    int rc;
-    if (!c->s_dec2) {
-        HIP_TRY(hipDeviceSynchronize());
-        double cf = 0;
-        if (t->pick_streams) { if ((rc = pick_stream_beside({c->s_cmp, c->s_d2h, c->s_h2d}, &c->s_dec2, &cf))) return rc; }
-        else HIP_TRY(hipStreamCreateWithFlags(&c->s_dec2, hipStreamNonBlocking));
-    }
-    for (auto& ds : c->dslot) {
-        if (!ds.ev_in) for (hipEvent_t* e : {&ds.ev_in, &ds.ev_len, &ds.ev_cp, &ds.ev_out}) HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
-        if (max_ids > ds.cap_ids) {
-            HIP_TRY(hipDeviceSynchronize());
-            hipFree(ds.ids); hipFree(ds.blk); hipFree(ds.idoff);
-            ds.ids = nullptr; ds.blk = nullptr; ds.idoff = nullptr;
-            ds.cap_ids = max_ids + max_ids / 4 + 4096;
-            HIP_TRY(hipMalloc((void**)&ds.ids, ds.cap_ids * 4));
-            HIP_TRY(hipMalloc((void**)&ds.blk, (ds.cap_ids / DEC_BLK + 4) * 8));
-            HIP_TRY(hipMalloc((void**)&ds.idoff, (ds.cap_ids + 1) * 8));
-        }
-        if (max_docs + 1 > ds.cap_docs) {
-            HIP_TRY(hipDeviceSynchronize());
-            hipFree(ds.first); hipFree(ds.docoff);
-            ds.first = nullptr; ds.docoff = nullptr;
-            ds.cap_docs = max_docs + 1 + max_docs / 4 + 1024;
-            HIP_TRY(hipMalloc((void**)&ds.first, ds.cap_docs * 8));
-            HIP_TRY(hipMalloc((void**)&ds.docoff, ds.cap_docs * 8));
-        }
-    }
-    if (!c->h_dtot.ensure(t->pool, ch.size() * 8)) return fail(SPL_EDEVICE, "spl_decode_batch: pinned allocation failed");
-    uint64_t* const h_tot = (uint64_t*)c->h_dtot.p;
-    // the result: a first guess of its size (5 bytes per token), moved to a larger buffer if a chunk does not fit
-    o.b = (uint8_t*)t->pool->get(n * 5 + 4096, o.bcap);
-    if (!o.b) return fail(SPL_EDEVICE, "spl_decode_batch: pinned allocation failed");
-    auto args_of = [&](size_t k) {
-        const DC& q = ch[k];
-        Ctx::DecSlot& ds = c->dslot[k & 1];
-        DecodeArgs a{};
-        a.ids = ds.ids; a.n_ids = ids_off[q.d1] - ids_off[q.d0]; a.tok_off = c->d_tok_off; a.tok_bytes = c->d_tok_bytes; a.max_id = c->dec_max_id;
-        a.sp_ids = c->d_dec_sp_ids; a.sp_off = c->d_dec_sp_off; a.n_sp = c->dec_n_sp;
-        a.blk = ds.blk; a.id_off = ds.idoff; a.doc_first = ds.first; a.n_docs = q.d1 - q.d0; a.doc_off = ds.docoff; a.out = ds.out;
-        return a;
-    };
-    auto submit_len = [&](size_t k) -> int {                  // ids in, lengths, the chunk's byte count to pinned memory
-        const DC& q = ch[k];
-        Ctx::DecSlot& ds = c->dslot[k & 1];
-        if (k >= 2) { HIP_TRY(hipStreamWaitEvent(c->s_h2d, ds.ev_cp, 0)); HIP_TRY(hipStreamWaitEvent(c->s_cmp, ds.ev_cp, 0)); }   // the slot's previous chunk has been gathered
-        const DecodeArgs a = args_of(k);
-        if (a.n_ids) HIP_TRY(hipMemcpyAsync(ds.ids, ids + ids_off[q.d0], a.n_ids * 4, hipMemcpyHostToDevice, c->s_h2d));
-        HIP_TRY(hipMemcpyAsync(ds.first, ids_off + q.d0, (a.n_docs + 1) * 8, hipMemcpyHostToDevice, c->s_h2d));
-        HIP_TRY(hipEventRecord(ds.ev_in, c->s_h2d));
-        HIP_TRY(hipStreamWaitEvent(c->s_cmp, ds.ev_in, 0));
-        const uint64_t n_blk = (a.n_ids + DEC_BLK - 1) / DEC_BLK;
-        if (n_blk) hipLaunchKernelGGL(k_decode_len, dim3((uint32_t)n_blk), dim3(NT), 0, c->s_cmp, a);
-        hipLaunchKernelGGL(k_decode_scan, dim3(1), dim3(1024), 0, c->s_cmp, ds.blk, n_blk);
-        HIP_TRY(hipMemcpyAsync(&h_tot[k], ds.blk + n_blk, 8, hipMemcpyDeviceToHost, c->s_cmp));
-        HIP_TRY(hipEventRecord(ds.ev_len, c->s_cmp));
-        return SPL_OK;
-    };
-    uint64_t base = 0;
-    auto finish = [&](size_t k) -> int {                      // bytes gathered, rebased offsets, both on their way into the result
-        const DC& q = ch[k];
-        Ctx::DecSlot& ds = c->dslot[k & 1];
-        HIP_TRY(hipEventSynchronize(ds.ev_len));
-        const uint64_t total = h_tot[k];
-        if (total + 16 > ds.cap_out) {                        // (grow-only; the slot's previous bytes have left: its event first)
-            if (k >= 2) HIP_TRY(hipEventSynchronize(ds.ev_out));
-            HIP_TRY(hipDeviceSynchronize());
-            hipFree(ds.out); ds.out = nullptr;
-            ds.cap_out = total + total / 4 + 4096;
-            HIP_TRY(hipMalloc((void**)&ds.out, ds.cap_out));
-        }
-        if (base + total > o.bcap) {                          // the guess was too small: what is still to come is at most 128 bytes per token
-            HIP_TRY(hipStreamSynchronize(c->s_d2h));
-            const uint64_t rest_ids = ids_off[n_docs] - ids_off[q.d1];
-            size_t ncap = 0;
-            uint8_t* nb = (uint8_t*)t->pool->get(base + total + rest_ids * 8 + 4096, ncap);
-            if (!nb) return fail(SPL_EDEVICE, "spl_decode_batch: pinned allocation failed");
-            memcpy(nb, o.b, base);
-            t->pool->put(o.b, o.bcap);
-            o.b = nb; o.bcap = ncap;
-        }
-        DecodeArgs a = args_of(k);
-        a.out_base = base;
-        if (k >= 2) HIP_TRY(hipStreamWaitEvent(c->s_dec2, ds.ev_out, 0));     // the slot's previous bytes and offsets have left
-        HIP_TRY(hipStreamWaitEvent(c->s_dec2, ds.ev_len, 0));
-        const uint64_t n_blk = (a.n_ids + DEC_BLK - 1) / DEC_BLK;
-        if (n_blk) hipLaunchKernelGGL(k_decode_copy, dim3((uint32_t)n_blk), dim3(NT), 0, c->s_dec2, a);
-        else HIP_TRY(hipMemsetAsync(ds.idoff, 0, 8, c->s_dec2));              // (a chunk of empty documents: id_off[0] = 0)
-        hipLaunchKernelGGL(k_decode_docs, dim3((uint32_t)((a.n_docs + 1 + 255) / 256)), dim3(256), 0, c->s_dec2, a);
-        HIP_TRY(hipEventRecord(ds.ev_cp, c->s_dec2));
-        HIP_TRY(hipStreamWaitEvent(c->s_d2h, ds.ev_cp, 0));
-        if (total) HIP_TRY(hipMemcpyAsync(o.b + base, ds.out, total, hipMemcpyDeviceToHost, c->s_d2h));
-        const bool last = k + 1 == ch.size();
-        HIP_TRY(hipMemcpyAsync(o.o + q.d0, ds.docoff, (a.n_docs + (last ? 1 : 0)) * 8, hipMemcpyDeviceToHost, c->s_d2h));
-        HIP_TRY(hipEventRecord(ds.ev_out, c->s_d2h));
-        base += total;
-        return SPL_OK;
-    };
-    if ((rc = submit_len(0))) return rc;
-    for (size_t k = 1; k < ch.size(); k++) {
-        if ((rc = submit_len(k))) return rc;
-        if ((rc = finish(k - 1))) return rc;
-    }
-    if ((rc = finish(ch.size() - 1))) return rc;
-    HIP_TRY(hipStreamSynchronize(c->s_d2h));
-    HIP_TRY(hipGetLastError());
-    return SPL_OK;
-}
-
-static int spl_decode_batch_impl(spl_tokenizer* t, const uint32_t* ids, const uint64_t* ids_off, uint64_t n_docs, uint8_t** out_bytes,
-                     uint64_t** out_off) {
-    if (!t || !ids_off || !out_bytes || !out_off) return fail(SPL_EINVAL, "spl_decode_batch: null argument");
-    for (uint64_t d = 0; d < n_docs; d++)
-        if (ids_off[d + 1] < ids_off[d]) return fail(SPL_EINVAL, "spl_decode_batch: ids_off must be non-decreasing");
-    Ctx* c = t->ctx[0].get();
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = ensure_streams(*c);
-    if (rc) return rc;
-    if ((rc = upload_decode(t, c))) return rc;
-    const uint64_t n = ids_off[n_docs] - ids_off[0];
-    if (n && !ids) return fail(SPL_EINVAL, "spl_decode_batch: null ids");
-    const uint64_t n_blk = (n + DEC_BLK - 1) / DEC_BLK;
-    // outputs in pinned memory from the handle's pool (the D2H copies run at PCIe speed into it; pageable
-    // memory would be staged by the runtime page by page); returned to the pool on every error path
-    DecOut o;
-    o.pool = t->pool;
-    o.o = (uint64_t*)t->pool->get((n_docs + 1) * 8, o.ocap);
-    if (!o.o) return fail(SPL_EDEVICE, "spl_decode_batch: pinned allocation failed");
-    uint64_t total = 0;
-    if (n >= 3 * t->dec_chunk_ids && n_docs >= 3) {
-        if ((rc = decode_pipelined(t, c, ids, ids_off, n_docs, o))) return rc;
-    } else if (n) {
-        // scratch grows, never shrinks: a steady stream of calls allocates nothing
-        if (n > c->dec_cap_ids || !c->d_dec_ids) {
-            HIP_TRY(hipDeviceSynchronize());
-            hipFree(c->d_dec_ids); hipFree(c->d_dec_blk); hipFree(c->d_dec_idoff);
-            c->d_dec_ids = nullptr; c->d_dec_blk = nullptr; c->d_dec_idoff = nullptr;
-            c->dec_cap_ids = n + n / 4 + 4096;
-            HIP_TRY(hipMalloc((void**)&c->d_dec_ids, c->dec_cap_ids * 4));
-            HIP_TRY(hipMalloc((void**)&c->d_dec_blk, (c->dec_cap_ids / DEC_BLK + 4) * 8));
-            HIP_TRY(hipMalloc((void**)&c->d_dec_idoff, (c->dec_cap_ids + 1) * 8));
-        }
-        if (n_docs + 1 > c->dec_cap_docs || !c->d_dec_first) {
-            HIP_TRY(hipDeviceSynchronize());
-            hipFree(c->d_dec_first); hipFree(c->d_dec_docoff);
-            c->d_dec_first = nullptr; c->d_dec_docoff = nullptr;
-            c->dec_cap_docs = n_docs + 1 + n_docs / 4 + 1024;
-            HIP_TRY(hipMalloc((void**)&c->d_dec_first, c->dec_cap_docs * 8));
-            HIP_TRY(hipMalloc((void**)&c->d_dec_docoff, c->dec_cap_docs * 8));
-        }
-        HIP_TRY(hipMemcpyAsync(c->d_dec_ids, ids + ids_off[0], n * 4, hipMemcpyHostToDevice, c->s_cmp));
-        HIP_TRY(hipMemcpyAsync(c->d_dec_first, ids_off, (n_docs + 1) * 8, hipMemcpyHostToDevice, c->s_cmp));
-        DecodeArgs a{};
-        a.ids = c->d_dec_ids; a.n_ids = n; a.tok_off = c->d_tok_off; a.tok_bytes = c->d_tok_bytes; a.max_id = c->dec_max_id;
-        a.sp_ids = c->d_dec_sp_ids; a.sp_off = c->d_dec_sp_off; a.n_sp = c->dec_n_sp;
-        a.blk = c->d_dec_blk; a.id_off = c->d_dec_idoff; a.doc_first = c->d_dec_first; a.n_docs = n_docs; a.doc_off = c->d_dec_docoff;
-        hipLaunchKernelGGL(k_decode_len, dim3((uint32_t)n_blk), dim3(NT), 0, c->s_cmp, a);
-        hipLaunchKernelGGL(k_decode_scan, dim3(1), dim3(1024), 0, c->s_cmp, c->d_dec_blk, n_blk);
-        uint64_t* h_total = (uint64_t*)o.o;                       // (pinned: the count lands without a staging copy)
-        HIP_TRY(hipMemcpyAsync(h_total, c->d_dec_blk + n_blk, 8, hipMemcpyDeviceToHost, c->s_cmp));
-        HIP_TRY(hipStreamSynchronize(c->s_cmp));                  // the output size: the one host round trip
-        total = *h_total;
-        if ((rc = grow(&c->d_dec_out, &c->dec_cap_out, total + 16))) return rc;
-        a.out = c->d_dec_out;
-        hipLaunchKernelGGL(k_decode_copy, dim3((uint32_t)n_blk), dim3(NT), 0, c->s_cmp, a);
-        hipLaunchKernelGGL(k_decode_docs, dim3((uint32_t)((n_docs + 1 + 255) / 256)), dim3(256), 0, c->s_cmp, a);
-        HIP_TRY(hipGetLastError());
-        o.b = (uint8_t*)t->pool->get(total ? total : 1, o.bcap);
-        if (!o.b) return fail(SPL_EDEVICE, "spl_decode_batch: pinned allocation failed");
-        if (total) HIP_TRY(hipMemcpyAsync(o.b, c->d_dec_out, total, hipMemcpyDeviceToHost, c->s_cmp));
-        HIP_TRY(hipMemcpyAsync(o.o, c->d_dec_docoff, (n_docs + 1) * 8, hipMemcpyDeviceToHost, c->s_cmp));
-        HIP_TRY(hipStreamSynchronize(c->s_cmp));
-    } else {
-        o.b = (uint8_t*)t->pool->get(1, o.bcap);
-        if (!o.b) return fail(SPL_EDEVICE, "spl_decode_batch: pinned allocation failed");
-        for (uint64_t d = 0; d <= n_docs; d++) o.o[d] = 0;
-    }
-    loose().add(o.b, t->pool, o.bcap);
-    loose().add(o.o, t->pool, o.ocap);
-    *out_bytes = o.b; *out_off = o.o;
-    o.b = nullptr; o.o = nullptr;
-    return SPL_OK;
-}
 
 void spl_free(void* p) { if (p && !loose().release(p)) free(p); }
 
@@ -2704,9 +391,9 @@ int spl_debug_blocks(spl_tokenizer* t, unsigned long long* out, int max_blocks) 
     Ctx* c = t->ctx[0].get();
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());
-    if (!c->d_dbg) return 0;
+    if (!c->d_dbg.get()) return 0;
     const int n = max_blocks < SPL_DEBUG_BLOCKS ? max_blocks : SPL_DEBUG_BLOCKS;
-    HIP_TRY(hipMemcpy(out, c->d_dbg + 16, (size_t)n * 32, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, c->d_dbg.get() + 16, (size_t)n * 32, hipMemcpyDeviceToHost));
     return n;
 }
 
@@ -2718,7 +405,7 @@ int spl_debug_phases(spl_tokenizer* t, int enable, unsigned long long stamps_out
         Ctx* c = cp.get();
         HIP_TRY(hipSetDevice(c->device));
         HIP_TRY(hipDeviceSynchronize());
-        if (c == t->ctx[0].get() && stamps_out && c->d_dbg) HIP_TRY(hipMemcpy(stamps_out, c->d_dbg, 16 * 8, hipMemcpyDeviceToHost));
+        if (c == t->ctx[0].get() && stamps_out && c->d_dbg.get()) HIP_TRY(hipMemcpy(stamps_out, c->d_dbg.get(), 16 * 8, hipMemcpyDeviceToHost));
         c->dbg_on = (enable & 1) != 0;
         c->stop_phase = (enable >> 4) & 7;
         c->force_tile = (enable >> 1) & 7;      // development: 1 = small tiles, 2 = large tiles, 3 = small tiles + multi-pass, 4 = queue mode, 5 = tile-owned with geometry B
@@ -2738,19 +425,19 @@ int spl_debug_merge_timing(unsigned long long out[8], int reset) {
 int spl_memo_stats(spl_tokenizer* t, uint64_t out[4]) {
     if (!t || !out) return fail(SPL_EINVAL, "null argument");
     Ctx* c = t->ctx[0].get();
-    out[0] = c->memo_fills; out[1] = out[2] = 0; out[3] = c->d_memo ? (uint64_t)c->memo_mask + 1 + (c->d_memo2 ? (uint64_t)c->memo2_mask + 1 : 0) : 0;
-    if (c->d_mstats) {
+    out[0] = c->memo_fills; out[1] = out[2] = 0; out[3] = c->d_memo.get() ? (uint64_t)c->memo_mask + 1 + (c->d_memo2.get() ? (uint64_t)c->memo2_mask + 1 : 0) : 0;
+    if (c->d_mstats.get()) {
         HIP_TRY(hipSetDevice(c->device));
         HIP_TRY(hipDeviceSynchronize());
         unsigned long long st[2] = {0, 0};
-        HIP_TRY(hipMemcpy(st, c->d_mstats, 16, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(st, c->d_mstats.get(), 16, hipMemcpyDeviceToHost));
         out[1] = st[0]; out[2] = st[1];
     }
     return SPL_OK;
 }
 
 int spl_last_queue_counts(spl_tokenizer* t, uint32_t counts_out[4]) {
-    if (!t || !t->ctx[0]->d_zero) return fail(SPL_EINVAL, "no batch has run");
+    if (!t || !t->ctx[0]->d_zero.get()) return fail(SPL_EINVAL, "no batch has run");
     Ctx* c = t->ctx[0].get();
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());
@@ -2815,9 +502,8 @@ void spl_comm_destroy(spl_comm* c) {
     if (hipSetDevice(c->device) == hipSuccess) {
         (void)hipDeviceSynchronize();
         if (c->comm) (void)rccl().CommDestroy(c->comm);
-        (void)hipFree(c->d_cnt); (void)hipFree(c->d_cnts); (void)hipHostFree(c->h_cnts);
     }
-    delete c;
+    delete c;                                 // (its buffers free themselves)
 }
 int spl_comm_rank(const spl_comm* c) { return c ? c->rank : -1; }
 int spl_comm_world(const spl_comm* c) { return c ? c->world : 0; }
@@ -2912,6 +598,3 @@ int spl_encode_chunks_device(spl_tokenizer* t, const uint8_t* d_utf8, uint64_t n
 }
 
 }  // extern "C"
-
-
-

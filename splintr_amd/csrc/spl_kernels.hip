@@ -1,5 +1,5 @@
 // spl_kernels.hip -- gfx950 kernels of the batch encode path (DESIGN.md 4 has the full table).  ONE translation unit (spl_api.hip
-// includes this file), in parts since round 4:
+// includes this file and then the host side, spl_host_res.h .. spl_collective.h), in parts since round 4:
 //
 //   this file          constants, TileDesc, Batch (the per-call argument struct), small wave helpers
 //   spl_k_special.h    k_mark_docs / k_special_scan / _ends / _select: text-start bitmap from the document offsets,
@@ -17,7 +17,7 @@
 //   spl_k_output.h     k_tile_out: tile records -> dense ids[] and per-document offsets (CSR); queue mode's
 //                      k_range_count / k_range_out, k_bpe_segments, k_bpe_long
 //   spl_k_decode.h     id -> bytes gather (k_decode_*), k_ext_specials, slabs around the RCCL all-gather, CSR rebase
-//   (spl_rx_split.h, included by spl_api.hip: the device splitter for custom split patterns)
+//   (spl_rx_split.h, included by spl_api.hip: the device splitter for custom split patterns; its host half is in spl_launch.h)
 // (The multi-pass pipeline of rounds 1-3 -- k_bpe_lanes64, k_count, k_scan, k_compact_docs and the k_pretok
 //  instantiations without tile records -- was removed in round 4: no BASELINE configuration reached it.)
 //

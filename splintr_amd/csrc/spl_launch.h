@@ -1,0 +1,433 @@
+// spl_launch.h -- one device call: the chunk memo's life cycle (memo_ensure / memo_before_launch), the choice of mode and the launch order
+// (launch_all), and the device splitter's host half (rx_ensure / rx_next_status / rx_launch).  Needs Ctx and spl_tokenizer (spl_ctx.h) and
+// pick_stream_beside (spl_streams.h).
+#pragma once
+namespace {
+
+struct SlabOut { uint32_t* d_slab = nullptr; uint64_t cap_words = 0, max_docs = 0; };
+// chunk boundaries given from outside (host splitter): device bitmaps, and the special tokens found on the host
+constexpr uint32_t RX_STATUS_SLOTS = 8;
+struct ExtIn {
+    const uint32_t* d_starts = nullptr; const uint32_t* d_gaps = nullptr; const uint32_t* d_sp_pos = nullptr; const uint32_t* d_sp_id = nullptr; uint32_t n_sp = 0;
+    // the two bitmaps are still to be made, by the device splitter, inside launch_all (behind the special-token kernels, whose bitmaps it reads):
+    uint32_t* d_status = nullptr;          // non-null: yes; the status word it reports to
+    uint32_t* d_status_host = nullptr;     // ... and (device pointer of) its pinned host copy, written by k_rx_mark itself
+};
+int rx_launch(spl_tokenizer* tk, Ctx* c, const uint8_t* d_text, uint64_t n_bytes, const uint64_t* d_doc_off, uint64_t n_docs,
+              uint32_t* d_starts, uint32_t* d_gaps, uint32_t* d_status, hipStream_t s, const Batch* sp = nullptr, uint32_t sp_words = 0,
+              uint32_t* d_status_host = nullptr, bool bad_sets_status = false);
+
+// The chunk memo of a context (spl_k_memo.h): built empty at the first launch; the tiles log what it did not hold and raise the pinned
+// flag; a launch that finds the flag raised first runs k_memo_fill on its stream -- encode the logged chunks, put them in -- and then
+// its own kernels: the memo is only ever written between two launches of the stream that reads it.
+// (the parts of the second table's one allocation)
+struct Memo2Parts { MemoEnt* ent; MemoExt* ext; MemoHi* hi; uint32_t* claim; uint32_t* log; };
+Memo2Parts memo2_parts(Ctx* t) {
+    const size_t s2 = (size_t)t->memo2_mask + 1;
+    Memo2Parts m;
+    m.ent = (MemoEnt*)t->d_memo2.get(); m.ext = (MemoExt*)(m.ent + s2); m.hi = (MemoHi*)(m.ext + s2); m.claim = (uint32_t*)(m.hi + s2); m.log = m.claim + s2;
+    return m;
+}
+void memo_tables(Ctx* t) {
+    t->dt.memo = t->d_memo.get(); t->dt.memo_mask = t->memo_mask; t->dt.memo_ext = t->d_memo_ext.get();
+    t->dt.memo2 = nullptr; t->dt.memo2_mask = 0; t->dt.memo2_ext = nullptr; t->dt.memo2_hi = nullptr;
+    if (t->d_memo2.get()) { const Memo2Parts m = memo2_parts(t); t->dt.memo2 = m.ent; t->dt.memo2_mask = t->memo2_mask; t->dt.memo2_ext = m.ext; t->dt.memo2_hi = m.hi; }
+}
+int memo_ensure(spl_tokenizer* tk, Ctx* t) {
+    if (t->d_memo.get()) return SPL_OK;
+    const size_t slots = (size_t)1 << tk->memo_bits;
+    SPL_TRY(t->d_memo.alloc_zeroed(slots));
+    SPL_TRY(t->d_memo_ext.alloc(slots));      // (only hits of seven to fourteen tokens ever touch it)
+    SPL_TRY(t->d_mclaim.alloc_zeroed(slots));
+    // (the log of a context that takes LARGE batches is larger: a cold pass over 200 MB misses the vocabulary three million times, and at 65 536
+    //  logged chunks a fill -- duplicates among them -- the memo needed a dozen passes to hold them all; one entry per 192 bytes of capacity, 16 384 a region at most)
+    t->memo_cap = (uint32_t)std::min<uint64_t>(16384, std::max<uint64_t>(tk->memo_log_cap, t->cap_bytes / ((uint64_t)SPL_MEMO_LOG_REGIONS * 192)));
+    SPL_TRY(t->d_mlog.alloc((size_t)SPL_MEMO_LOG_REGIONS * t->memo_cap * SPL_MEMO_LOG_WORDS));
+    SPL_TRY(t->d_mlog_cnt.alloc_zeroed(2 * SPL_MEMO_LOG_REGIONS));              // (the second half: the log of chunks of 33..64 bytes)
+    t->memo2_mask = 0; t->memo2_cap = 0;
+    if (tk->memo_long_bits) {
+        const size_t s2 = (size_t)1 << tk->memo_long_bits;
+        t->memo2_cap = std::max<uint32_t>(t->memo_cap / 8, 16);
+        const size_t bytes = s2 * (sizeof(MemoEnt) + sizeof(MemoExt) + sizeof(MemoHi) + 4) + (size_t)SPL_MEMO_LOG_REGIONS * t->memo2_cap * SPL_MEMO_LOG_WORDS2 * 4;
+        SPL_TRY(t->d_memo2.alloc(bytes));
+        HIP_TRY(hipMemset(t->d_memo2.get(), 0, s2 * (sizeof(MemoEnt) + sizeof(MemoExt) + sizeof(MemoHi) + 4)));
+        t->memo2_mask = (uint32_t)(s2 - 1);
+    }
+    SPL_TRY(t->d_mstats.alloc_zeroed(2));
+    if (!t->h_mflag) SPL_TRY(t->h_mflag.alloc(16));
+    t->h_mflag.host()[0] = 0;
+    t->memo_mask = (uint32_t)(slots - 1);
+    memo_tables(t);
+    t->memo_round = 0; t->memo_fills = 0; t->memo_since = 0;
+    return SPL_OK;
+}
+int memo_before_launch(spl_tokenizer* tk, Ctx* t, hipStream_t s) {
+    if (!tk->memo) { t->dt.memo = nullptr; t->dt.memo2 = nullptr; return SPL_OK; }
+    int rc = memo_ensure(tk, t);
+    if (rc) return rc;
+    memo_tables(t);
+    t->memo_since++;
+    // (the flag was raised by an EARLIER launch's tiles, when one of the log's regions became half full)
+    if (*(volatile uint32_t*)t->h_mflag.host()) {
+        *(volatile uint32_t*)t->h_mflag.host() = 0;
+        t->memo_round++;
+        hipLaunchKernelGGL(k_memo_fill<false>, dim3((t->memo_cap + MEMO_FILL_NT - 1) / MEMO_FILL_NT, SPL_MEMO_LOG_REGIONS), dim3(MEMO_FILL_NT), 0, s, t->dt, t->d_memo.get(), t->d_memo_ext.get(),
+                           (MemoHi*)nullptr, (const uint32_t*)t->d_mlog.get(), (const uint32_t*)t->d_mlog_cnt.get(), t->memo_cap, t->d_mclaim.get(), t->memo_round, t->d_mstats.get());
+        if (t->d_memo2.get()) {
+            const Memo2Parts m = memo2_parts(t);
+            hipLaunchKernelGGL(k_memo_fill<true>, dim3((t->memo2_cap + MEMO_FILL_NT2 - 1) / MEMO_FILL_NT2, SPL_MEMO_LOG_REGIONS), dim3(MEMO_FILL_NT2), 0, s, t->dt, m.ent, m.ext, m.hi,
+                               (const uint32_t*)m.log, (const uint32_t*)(t->d_mlog_cnt.get() + SPL_MEMO_LOG_REGIONS), t->memo2_cap, m.claim, t->memo_round, t->d_mstats.get());
+        }
+        HIP_TRY(hipMemsetAsync(t->d_mlog_cnt.get(), 0, 2 * SPL_MEMO_LOG_REGIONS * 4, s));
+        t->memo_fills++;
+        t->memo_since = 0;
+    }
+    return SPL_OK;
+}
+
+// How one device call runs.  Tile-owned: every tile finishes its own tokens (k_pretok + k_tile_out, or the one fused launch), in one of two
+// geometries of the same window (spl_kernels.hip SPL_TILE_DIRECT_A / _B).  Queue: tile-owned tiles plus global queues for what is long, for
+// batches beyond the tile-owned limit; it has no form with special tokens or external boundaries.  force_tile (spl_debug_phases): 0 by
+// size, 1 tile-owned, 4 queue mode where it has a form, 5 geometry B at any size; anything else only runs with external boundaries.
+enum class TileMode { OwnedA, OwnedB, Queue, Refuse };
+TileMode pick_mode(int force_tile, bool ext, bool special, uint64_t n_bytes) {
+    static_assert(SPL_DIRECT_MAX_BYTES <= SPL_QUEUE_MAX_BYTES, "queue mode takes over where the tile-owned mode ends");
+    static_assert(TileGeom<SPL_TILE_DIRECT_A>::Wv == TileGeom<SPL_TILE_SMALL>::Wv && TileGeom<SPL_TILE_DIRECT_B>::Wv == TileGeom<SPL_TILE_SMALL>::Wv &&
+                  TileGeom<SPL_TILE_DIRECT_A>::TBv >= TileGeom<SPL_TILE_SMALL>::TBv && TileGeom<SPL_TILE_DIRECT_B>::TBv >= TileGeom<SPL_TILE_SMALL>::TBv,
+                  "the workspace is sized for SPL_TILE_SMALL's window and tile count");
+    if (!ext && !special && (force_tile == 4 || (force_tile == 0 && n_bytes > SPL_DIRECT_MAX_BYTES)) && n_bytes <= SPL_QUEUE_MAX_BYTES) return TileMode::Queue;
+    const bool known = force_tile == 0 || force_tile == 1 || force_tile == 4 || force_tile == 5;
+    if (n_bytes > SPL_DIRECT_MAX_BYTES || !(ext || known)) return TileMode::Refuse;
+    return (force_tile == 5 || n_bytes > SPL_DIRECT_A_MAX_BYTES) ? TileMode::OwnedB : TileMode::OwnedA;
+}
+
+int launch_all(spl_tokenizer* tk, Ctx* t, const uint8_t* d_utf8, uint64_t n_bytes, const uint64_t* d_doc_off, uint64_t n_docs,
+               uint32_t flags, uint32_t* d_ids, uint64_t ids_cap, uint64_t* d_out_off, hipStream_t s,
+               const SlabOut* so = nullptr, const ExtIn* ext = nullptr, int phase = 0) {
+    // phase (tile-owned mode with the device splitter, per-document fallback): 0 = everything; 1 = only what comes in FRONT of the tile kernel
+    // (bitmap fills, special-token scan, the device splitter); 2 = only the tile kernel and k_tile_out, on bitmaps the caller may have patched
+    if (((uintptr_t)d_utf8 & 15) != 0) return fail(SPL_EINVAL, "text buffer must be 16-byte aligned");
+    if (ext && n_bytes > SPL_DIRECT_MAX_BYTES) return fail(SPL_EINVAL, "external chunk boundaries: at most 256 MB per device call");
+    // (external boundaries from the HOST splitter: the special tokens -- if any -- were found there; the GPU's literal scan stays off)
+    const bool special = (!ext || ext->d_status) && (flags & SPL_WITH_SPECIAL) && !tk->specials.empty();
+    if (special) { int rc0 = upload_specials(tk, t); if (rc0) return rc0; }
+    if (n_bytes > 0x7FFF0000ull) return fail(SPL_EINVAL, "n_bytes per device call must be < 2^31 - 65536 (split the corpus at document boundaries; spl_encode_batch does that by itself)");
+    if (n_docs > 0xFFFFFFF0ull) return fail(SPL_EINVAL, "n_docs per device call must be < 2^32 - 16");
+    int rc = reserve(t, n_bytes, n_docs);
+    if (rc) return rc;
+    if (t->prof && !t->ev_ready) {
+        for (auto& e : t->ev) SPL_TRY(e.create(hipEventDefault));
+        t->ev_ready = true;
+    }
+    Batch b{};
+    b.text = d_utf8; b.n_bytes = (uint32_t)n_bytes; b.doc_off = d_doc_off; b.n_docs = (uint32_t)n_docs;
+    b.n_blk = (uint32_t)(n_bytes / RANK_BLK + 1);
+    const size_t uw = (size_t)b.n_blk * 32 + 32;
+    // bitmaps and queue counters packed back to back for THIS batch size: one memset clears them
+    b.tbits = t->d_zero.get(); b.tstart = t->d_zero.get() + uw;
+    const bool general = special && tk->special_general;
+    const size_t nbm = special ? (general ? 4 : 3) : 2;             // bitmaps in use for THIS call
+    b.skip = special ? t->d_zero.get() + 2 * uw : nullptr;
+    b.spcand = general ? t->d_zero.get() + 3 * uw : nullptr;
+    b.qcount = t->d_zero.get() + nbm * uw;
+    t->last_qcount = b.qcount;
+    b.sp_lits = t->d_sp_lits.get(); b.n_special = special ? (uint32_t)tk->specials.size() : 0u;
+    b.stage = t->d_stage.get(); b.rank_scr = t->d_rank.get(); b.aux = t->d_aux;
+    b.q64 = t->d_q64.get(); b.qlong = t->d_qlong.get(); b.qdefer = t->d_qdefer.get();
+    b.qcap64 = t->qcap64; b.qcaplong = t->qcaplong; b.qcapdefer = t->qcapdefer;
+    b.dbg = (t->dbg_on || t->prof) ? t->d_dbg.get() : nullptr;
+    b.stop_phase = (uint32_t)t->stop_phase;
+    { static const uint32_t dbg_wg = [] { const char* e = getenv("SPL_DEBUG_WG"); return e ? (uint32_t)strtoul(e, nullptr, 10) : 0xFFFFFFFFu; }(); b.dbg_wg = dbg_wg; }
+    if (t->prof) {
+        const unsigned long long init[2] = {~0ull, 0ull};
+        HIP_TRY(hipMemcpyAsync(t->d_dbg.get() + 14, init, 16, hipMemcpyHostToDevice, s));
+    }
+    b.blk_base = t->d_blk.get();
+    b.id_limit = t->dt.id_limit;
+    b.ids_out = d_ids; b.ids_cap = ids_cap; b.off_out = d_out_off;
+    if (phase != 1) {                                        // (the chunk memo: a fill, if the earlier launches left something to put in)
+        int rcm = memo_before_launch(tk, t, s);
+        if (rcm) return rcm;
+        if (t->dt.memo) { b.mlog = t->d_mlog.get(); b.mlog_cnt = t->d_mlog_cnt.get(); b.mlog_cap = t->memo_cap; b.mflag = t->h_mflag.dev(); }
+        if (t->dt.memo && t->d_memo2.get()) { b.mlog2 = memo2_parts(t).log; b.mlog2_cap = t->memo2_cap; }
+    }
+
+    const bool pf = t->prof;
+#define MARK(i) do { if (pf) HIP_TRY(hipEventRecord(t->ev[i].get(), s)); } while (0)
+    const TileMode mode = pick_mode(t->force_tile, ext != nullptr, special, n_bytes);
+    if (mode == TileMode::Refuse)
+        return fail(SPL_EINVAL, (flags & SPL_WITH_SPECIAL) && !tk->specials.empty()
+                                    ? "a device call with SPL_WITH_SPECIAL takes at most 256 MB: split the call at document boundaries -- spl_encode_batch does that by itself"
+                                    : "this device call fits neither the tile-owned mode (256 MB) nor queue mode (2047 MiB, no forced geometry): split it at document boundaries");
+    const bool queue_mode = mode == TileMode::Queue, direct_b = mode == TileMode::OwnedB;
+    const uint32_t tile_bytes = queue_mode ? TileGeom<SPL_TILE_SMALL>::TBv : direct_b ? TileGeom<SPL_TILE_DIRECT_B>::TBv : TileGeom<SPL_TILE_DIRECT_A>::TBv;
+    const uint32_t ntiles = (uint32_t)((n_bytes + tile_bytes - 1) / tile_bytes);
+    // (A/B on the 1 MB bench batch: folding these launches together -- clean-after-use bitmaps, one
+    //  tail kernel with a grid barrier and a last-workgroup scan -- was SLOWER than this plain
+    //  sequence: back-to-back launches overlap their dispatch with the previous kernel, while
+    //  single-workgroup tails and agent-scope fences sit on the critical path.)
+    // Single pass: small batches without special tokens are finished by ONE kernel.
+    bool fused_launch = false;               // tile-owned mode as ONE launch: no k_tile_out
+    if (queue_mode) {
+        t->bitmap_dirty = true;
+        HIP_TRY(hipMemsetAsync(t->d_zero.get(), 0, (2 * uw + QCOUNT_WORDS) * 4, s));
+        b.tdesc = t->d_tdesc.get(); b.tile_ids = t->d_tile_ids.get(); b.tctl = t->d_tctl.get(); b.tile_bits = t->d_tile_bits.get(); b.tcnt = t->d_tcnt.get();
+        b.tgroups = t->tgroups; b.tpar = t->tpar; b.tslot = (uint32_t)TileGeom<SPL_TILE_SMALL>::Wv + 1u;
+        t->tpar ^= 1u;
+        MARK(KI_MARK);
+        if (n_docs) hipLaunchKernelGGL(k_mark_docs, dim3((uint32_t)((n_docs + 255) / 256)), dim3(256), 0, s, b);
+        MARK(KI_SPECIAL); MARK(KI_PRETOK);
+        hipLaunchKernelGGL((k_pretok<SPL_TILE_SMALL>), dim3(ntiles), dim3(NT), 0, s, PRETOK_EARLY(t->dt, b), t->dt, b);
+        MARK(KI_DEFER);
+        hipLaunchKernelGGL(k_deferred_wave, dim3(256), dim3(64), 0, s, t->dt, b);
+        MARK(KI_BPELANES);
+        hipLaunchKernelGGL(k_bpe_segments, dim3(std::min<uint32_t>(2048, ntiles / 4 + 8)), dim3(NT), 0, s, t->dt, b);
+        MARK(KI_BPELONG);
+        hipLaunchKernelGGL(k_bpe_long, dim3(std::min<uint32_t>(2048, ntiles / 4 + 8)), dim3(NT), 0, s, t->dt, b, 1);
+        MARK(KI_COUNT);
+        hipLaunchKernelGGL((k_range_count<SPL_TILE_SMALL>), dim3(ntiles), dim3(64), 0, s, b);
+        MARK(KI_SCAN); MARK(KI_COMPACT);
+        hipLaunchKernelGGL((k_range_out<SPL_TILE_SMALL>), dim3(ntiles), dim3(64), 0, s, b);
+        MARK(KI_N);
+    } else {
+        const bool ext_sp = ext && ext->n_sp > 0;
+        if (phase == 2) {
+        } else if (special) {
+            // the three bitmaps are cleared per call; documents and literals are marked by the
+            // multi-pass kernels, the tile kernel reads the bitmaps on top of its document search
+            HIP_TRY(hipMemsetAsync(t->d_zero.get(), 0, (nbm * uw + QCOUNT_WORDS) * 4, s));
+            t->bitmap_dirty = true;
+        } else if (ext_sp) {                   // the token bitmap takes the host-found literals: cleared per call
+            HIP_TRY(hipMemsetAsync(t->d_zero.get(), 0, uw * 4, s));
+            t->bitmap_dirty = true;
+        } else if (t->bitmap_dirty) {
+            HIP_TRY(hipMemsetAsync(t->d_zero.get(), 0, t->zero_words * 4, s));
+            t->bitmap_dirty = false;
+        }
+        b.tdesc = t->d_tdesc.get(); b.tile_ids = t->d_tile_ids.get(); b.tctl = t->d_tctl.get();
+        b.tgroups = t->tgroups; b.tpar = t->tpar; b.tslot = (uint32_t)TileGeom<SPL_TILE_SMALL>::Wv + 1u;
+        if (so && ntiles) { b.slab = so->d_slab; b.slab_cap = (uint32_t)so->cap_words; b.slab_max_docs = (uint32_t)so->max_docs; b.slab_p24 = tk->slab_pack24 ? 1u : 0u; }
+        // (The latency path as ONE launch -- the last workgroup of the tile kernel turning every tile's record into the CSR by itself, no
+        //  k_tile_out -- was built and measured in round 5: 33.6 us per 1 KB call against 31.2 with the two launches, 23.9 against 22.8 for 13
+        //  bytes.  Two back-to-back launches overlap the second one's dispatch with the first kernel; the fused epilogue's device-scope fences,
+        //  L1-bypassing loads and serial walk over the tiles cost more than that launch.  Dropped.)
+        // ONE launch (spl_k_fuse.h): every tile resident at once, each learns its base from the others' published counts and writes its
+        // part of the CSR itself
+        const bool fuse = tk->fuse && !t->fuse_off && ntiles && ntiles <= tk->fuse_max_tiles && phase != 1;
+        if (fuse) {
+            uint8_t* const mine = t->d_fctl.get() + (size_t)t->fpar * FUSE_PARITY_BYTES, * const other = t->d_fctl.get() + (size_t)(t->fpar ^ 1u) * FUSE_PARITY_BYTES;
+            b.ftc = (uint16_t*)mine; b.ftb = (uint32_t*)(mine + (size_t)FUSE_REPL * FUSE_STRIDE * 2);
+            b.fzc = (uint16_t*)other; b.fzb = (uint32_t*)(other + (size_t)FUSE_REPL * FUSE_STRIDE * 2); b.fz_n = t->fprev;
+            t->fpar ^= 1u;
+            t->fprev = ntiles;
+            fused_launch = true;
+        }
+        if (ntiles && phase != 1 && !fuse) t->tpar ^= 1u;     // k_tile_out zeroes the other parity's sums for the next call
+        if (ntiles && t->off_host && phase != 1) { b.off_out2 = t->off_host; t->off_host_written = true; }
+        if (ntiles && t->done_arm && phase != 1) { b.done = t->done_arm; b.done_seq = t->done_seq; t->done_armed = true; }
+        if (!special) b.tstart = nullptr;
+        b.qcount = nullptr;
+        t->last_qcount = nullptr;
+        if (ext) {
+            b.ext_starts = ext->d_starts; b.ext_gaps = ext->d_gaps;
+            if (ext_sp) {
+                b.skip = const_cast<uint32_t*>(ext->d_gaps);     // (read-only here: the spans the literals' tokens lie in)
+                if (phase != 2) hipLaunchKernelGGL(k_ext_specials, dim3((ext->n_sp + 255) / 256), dim3(256), 0, s, b, ext->d_sp_pos, ext->d_sp_id, ext->n_sp);
+            }
+        }
+        MARK(KI_MARK);
+        if (special && n_docs && phase != 2) hipLaunchKernelGGL(k_mark_docs, dim3((uint32_t)((n_docs + 255) / 256)), dim3(256), 0, s, b);
+        MARK(KI_SPECIAL);
+        if (special && n_bytes && phase != 2) {
+            if (!general) hipLaunchKernelGGL(k_special_scan, dim3((uint32_t)((n_bytes + 255) / 256)), dim3(256), 0, s, b);
+            else {
+                hipLaunchKernelGGL(k_special_ends, dim3((uint32_t)((n_bytes + 255) / 256)), dim3(256), 0, s, b);
+                hipLaunchKernelGGL(k_special_select, dim3((uint32_t)((n_docs + 255) / 256)), dim3(256), 0, s, b);
+            }
+        }
+        if (ext && ext->d_status && phase != 2) {            // the device splitter, behind the literal scan whose bitmaps it reads
+            int rcx = rx_launch(tk, t, d_utf8, n_bytes, d_doc_off, n_docs, const_cast<uint32_t*>(ext->d_starts), const_cast<uint32_t*>(ext->d_gaps),
+                                ext->d_status, s, special ? &b : nullptr, (uint32_t)uw, ext->d_status_host);
+            if (rcx) return rcx;
+        }
+        if (phase == 1) {
+            const hipError_t le1 = hipGetLastError();
+            if (le1 != hipSuccess) return fail(SPL_EDEVICE, std::string("kernel launch: ") + hipGetErrorString(le1));
+            return SPL_OK;
+        }
+        MARK(KI_PRETOK);
+        // A LARGE batch goes out as ranges of its tiles -- k_pretok and k_tile_out of range k, then of range k + 1, ...: what k_pretok leaves for
+        // k_tile_out (the tiles' ids and records) is still in the caches when k_tile_out reads it (one launch pair over 215 MB: 42 GB/s; its
+        // 27 MB ranges: 50), and on two streams the slow last tiles of one range run beside the next range's first.  A tile's base is the sum
+        // of the counts of the tiles in front of it: k_tile_out of range k needs k_pretok of the ranges 0 .. k, nothing else.
+        const bool ranged = ntiles && !fuse && tk->range_tiles && ntiles > tk->range_tiles + tk->range_tiles / 4 && !so && !pf && !b.done && !b.off_out2 &&
+                            phase == 0 && direct_b;
+        if (ranged) {
+            // (ranges of equal size, a multiple of 64 tiles: the tiles' counts are summed per group of 64)
+            const uint32_t nr = (ntiles + tk->range_tiles - 1) / tk->range_tiles, R = (((ntiles + nr - 1) / nr) + 63u) & ~63u;
+            const bool two = tk->range_streams == 2;
+            if (two && t->s_rng.get() && t->s_rng_for != s && tk->pick_streams) { (void)hipStreamSynchronize(t->s_rng.get()); t->s_rng.reset(); }
+            if (two && !t->s_rng) {
+                // (a stream MEASURED to run beside the caller's: which hardware queue a stream gets is the runtime's choice -- pick_stream_beside)
+                if (tk->pick_streams) { double cf = 0; hipStream_t picked = nullptr; SPL_TRY(pick_stream_beside({s}, &picked, &cf)); t->s_rng.reset(picked); }
+                else SPL_TRY(t->s_rng.create());
+                t->s_rng_for = s;
+                if (!t->ev_rng_in) { SPL_TRY(t->ev_rng_in.create()); SPL_TRY(t->ev_rng_out.create()); }
+            }
+            while (two && t->ev_rng.size() < nr) { Event e; SPL_TRY(e.create()); t->ev_rng.push_back(std::move(e)); }
+            if (two) { HIP_TRY(hipEventRecord(t->ev_rng_in.get(), s)); HIP_TRY(hipStreamWaitEvent(t->s_rng.get(), t->ev_rng_in.get(), 0)); }     // (what the caller's stream holds comes first)
+            for (uint32_t k = 0; k < nr; k++) {
+                hipStream_t st = (two && (k & 1u)) ? t->s_rng.get() : s;
+                if (k * R >= ntiles) break;
+                const uint32_t n = std::min(R, ntiles - k * R);
+                b.tile0 = k * R;
+                hipLaunchKernelGGL((k_pretok<SPL_TILE_DIRECT_B>), dim3(n), dim3(NT), 0, st, PRETOK_EARLY(t->dt, b), t->dt, b);
+                if (two) {
+                    HIP_TRY(hipEventRecord(t->ev_rng[k].get(), st));
+                    if (k) HIP_TRY(hipStreamWaitEvent(st, t->ev_rng[k - 1].get(), 0));        // (k_pretok of range k - 1, on the other stream; the ranges before it: in order)
+                }
+                hipLaunchKernelGGL(k_tile_out, dim3(n), dim3(TOUT_NT), 0, st, tile_out_args(b));
+            }
+            b.tile0 = 0;
+            if (two) { HIP_TRY(hipEventRecord(t->ev_rng_out.get(), t->s_rng.get())); HIP_TRY(hipStreamWaitEvent(s, t->ev_rng_out.get(), 0)); }
+        }
+        else if (ntiles && direct_b) hipLaunchKernelGGL((k_pretok<SPL_TILE_DIRECT_B>), dim3(ntiles), dim3(NT), 0, s, PRETOK_EARLY(t->dt, b), t->dt, b);
+        else if (ntiles) hipLaunchKernelGGL((k_pretok<SPL_TILE_DIRECT_A>), dim3(ntiles), dim3(NT), 0, s, PRETOK_EARLY(t->dt, b), t->dt, b);
+        else HIP_TRY(hipMemsetAsync(d_out_off, 0, (n_docs + 1) * 8, s));
+        MARK(KI_DEFER); MARK(KI_BPELANES); MARK(KI_BPELONG); MARK(KI_COUNT); MARK(KI_SCAN); MARK(KI_COMPACT);
+        if (ntiles && !fuse && !ranged) {
+            const uint32_t ng = (ntiles + 63u) / 64u;
+            if (ng > tk->group_scan_min && tk->group_scan_min) {
+                unsigned long long* const gpre = reinterpret_cast<unsigned long long*>(t->d_tctl.get() + ((16 + 2 * (size_t)t->tgroups + 1) & ~(size_t)1));
+                hipLaunchKernelGGL(k_group_scan, dim3(1), dim3(256), 0, s, (const uint32_t*)(t->d_tctl.get() + 16 + b.tpar * t->tgroups), ng, gpre);
+                b.gpre = gpre;
+            }
+            hipLaunchKernelGGL(k_tile_out, dim3(ntiles), dim3(TOUT_NT), 0, s, tile_out_args(b));
+        }
+        MARK(KI_N);
+    }
+#undef MARK
+    {
+        const hipError_t le = hipGetLastError();
+        if (le != hipSuccess) {
+            return fail(SPL_EDEVICE, std::string("kernel launch: ") + hipGetErrorString(le));
+        }
+    }
+    if (so && (queue_mode || !ntiles))          // the slab copy of the result, where k_tile_out did not write it
+        hipLaunchKernelGGL(k_gatherv_pack, dim3(256), dim3(256), 0, s, d_ids, d_out_off, (uint32_t)n_docs, so->d_slab,
+                           (uint32_t)so->cap_words, (uint32_t)so->max_docs, tk->slab_pack24 ? 1u : 0u);
+    if (pf) {
+        HIP_TRY(hipEventSynchronize(t->ev[KI_N].get()));
+        for (int i = 0; i < KI_N; i++) {
+            // slots whose kernels were not launched in this mode would only show the event overhead
+            const bool launched = queue_mode ? (i != KI_SPECIAL && i != KI_SCAN)
+                                             : (i == KI_PRETOK || (i == KI_COMPACT && !fused_launch) || (special && (i == KI_MARK || i == KI_SPECIAL)));
+            if (!launched) continue;
+            float ms = 0;
+            HIP_TRY(hipEventElapsedTime(&ms, t->ev[i].get(), t->ev[i + 1].get()));
+            if (i == KI_PRETOK && ntiles) {
+                // the dominant kernel is timed on the device's wall clock instead (see k_pretok)
+                unsigned long long span[2];
+                HIP_TRY(hipMemcpy(span, t->d_dbg.get() + 14, 16, hipMemcpyDeviceToHost));
+#ifndef SPL_DEBUG_STAMPS
+                {   // the end: the latest of the workgroups' own words (spl_k_pretok.h)
+                    static thread_local std::vector<unsigned long long> ends;
+                    ends.resize(std::min<size_t>(ntiles, 4 * (size_t)SPL_DEBUG_BLOCKS));
+                    HIP_TRY(hipMemcpy(ends.data(), t->d_dbg.get() + 16, ends.size() * 8, hipMemcpyDeviceToHost));
+                    span[1] = 0;
+                    for (unsigned long long e : ends) span[1] = std::max(span[1], e);
+                }
+#endif
+                int khz = 0;
+                HIP_TRY(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, t->device));
+                if (khz > 0 && span[1] > span[0]) ms = (float)((double)(span[1] - span[0]) / (double)khz);
+            }
+            t->prof_ms[i] += ms;
+            t->prof_n[i] += 1;
+        }
+    }
+    return SPL_OK;
+}
+
+// ---- custom split patterns on the device (spl_rx_split.h) ---------------------------------------------------------
+// Uploads the program image (and the general-category table if a class set tests one) to this context once, grows the
+// workspace, and launches the two kernels on `s`: d_starts / d_gaps (n_bytes / 32 + 2 words each, at least) are zeroed here;
+// *d_status collects RXS_* bits (not cleared here: a batch of several chunks shares one word).
+bool rx_applies(const spl_tokenizer* tk, uint32_t flags) {
+    (void)flags;                           // (SPL_WITH_SPECIAL too: the literals are found by the GPU's own scan, as for the built-in patterns)
+    return tk->regex && tk->rx_device && !tk->rx_image.empty();
+}
+int rx_ensure(spl_tokenizer* tk, Ctx* c) {
+    if (c->d_rx_image) return SPL_OK;
+    // (every piece only if it is not there yet: a call that failed half-way is repeated without leaking what it had allocated)
+    if (tk->rx_image[7] && !tk->ht.gc_stage1.empty()) {
+        if (!c->d_gc1) SPL_TRY(c->d_gc1.upload(tk->ht.gc_stage1));
+        if (!c->d_gc2) SPL_TRY(c->d_gc2.upload(tk->ht.gc_stage2));
+    }
+    if (!c->d_rx_status) SPL_TRY(c->d_rx_status.alloc_zeroed(16));
+    if (!c->h_rx_status) SPL_TRY(c->h_rx_status.alloc(16));
+    if (!c->d_rx_bad) SPL_TRY(c->d_rx_bad.alloc_zeroed(1 + RX_BAD_CAP));
+    if (!c->h_rx_bad) SPL_TRY(c->h_rx_bad.alloc(1 + 2 * RX_BAD_CAP));
+    if (!c->ev_split) SPL_TRY(c->ev_split.create());
+    return c->d_rx_image.upload(tk->rx_image);
+}
+// This batch's status word: the next one of the context's rotation -- cleared by the previous batch's k_rx_mark, or here if that batch launched none
+int rx_next_status(Ctx* c, hipStream_t s) {
+    c->rx_slot = (c->rx_slot + 1) % RX_STATUS_SLOTS;
+    if (!c->rx_next_clean) HIP_TRY(hipMemsetAsync(c->d_rx_status.get() + c->rx_slot, 0, 4, s));
+    c->rx_next_clean = false;
+    return SPL_OK;
+}
+int rx_launch(spl_tokenizer* tk, Ctx* c, const uint8_t* d_text, uint64_t n_bytes, const uint64_t* d_doc_off, uint64_t n_docs,
+              uint32_t* d_starts, uint32_t* d_gaps, uint32_t* d_status, hipStream_t s, const Batch* sp, uint32_t sp_words, uint32_t* d_status_host,
+              bool bad_sets_status) {
+    if (n_bytes > SPL_DIRECT_MAX_BYTES) return fail(SPL_EINVAL, "device split: at most 256 MB per call");
+    if (((uintptr_t)d_text & 15) != 0) return fail(SPL_EINVAL, "text buffer must be 16-byte aligned");
+    int rc = rx_ensure(tk, c);
+    if (rc) return rc;
+    const uint64_t words = n_bytes / 32 + 2;
+    if (!n_bytes) {                                    // (no block, no kernel: the two closing words by a fill)
+        HIP_TRY(hipMemsetAsync(d_starts, 0, words * 4, s));
+        HIP_TRY(hipMemsetAsync(d_gaps, 0, words * 4, s));
+        return SPL_OK;
+    }
+    const uint64_t nblk = (n_bytes + RXB - 1) / RXB;
+    // workspace, laid out by its CAPACITY in blocks (the per-block entries must stay where they are from call to call -- they are
+    // told apart by generation, not cleared): blk | bskip | bad_hi | bad_lo | dstart | nx | gx
+    if (nblk > c->rx_cap_blk) {
+        const uint64_t cb = nblk + nblk / 4 + 16;
+        const uint64_t cap = 16 * cb + 4 * (8 * cb + 2) + 4 * cb * RXB + 256;
+        c->rx_cap_blk = 0;
+        SPL_TRY(c->d_rx_ws.grow(&c->rx_ws_cap, cap, cap));
+        c->rx_cap_blk = cb;
+        c->rx_gen = 0xFFFFu;                           // (fresh memory: cleared below)
+    }
+    // the per-block entries carry the call's generation instead of being cleared per call (two fills of ~5 us each in front of the
+    // kernels of a 1 MB batch); every 65 535 calls -- and on fresh memory -- the workspace is cleared once
+    if (++c->rx_gen > 0xFFFFu) {
+        HIP_TRY(hipMemsetAsync(c->d_rx_ws.get(), 0, c->rx_ws_cap, s));
+        c->rx_gen = 1;
+    }
+    RxArgs a{};
+    a.image = c->d_rx_image.get(); a.image_words = (uint32_t)tk->rx_image.size();
+    a.text = d_text; a.doc_off = d_doc_off; a.n_bytes = (uint32_t)n_bytes; a.n_docs = (uint32_t)n_docs;
+    a.ucls1 = c->dt.ucls_stage1; a.ucls2 = c->dt.ucls_stage2; a.shift = c->dt.ucls_shift;
+    a.gc1 = c->d_gc1.get(); a.gc2 = c->d_gc2.get();
+    a.blk = (uint32_t*)c->d_rx_ws.get(); a.bskip = a.blk + c->rx_cap_blk; a.bad_hi = a.bskip + c->rx_cap_blk; a.bad_lo = a.bad_hi + c->rx_cap_blk;
+    a.dstart = a.bad_lo + c->rx_cap_blk;
+    a.bad_list = c->d_rx_bad.get(); a.bad_host = c->h_rx_bad.dev(); a.bad_sets_status = bad_sets_status ? 1u : 0u;
+    a.nx = (uint16_t*)(a.dstart + 8 * c->rx_cap_blk + 2); a.gx = a.nx + c->rx_cap_blk * RXB;
+    a.gen = c->rx_gen; a.bm_words = (uint32_t)words;
+    a.starts = d_starts; a.gaps = d_gaps; a.status = d_status; a.status_host = d_status_host;
+    if (d_status >= c->d_rx_status.get() && d_status < c->d_rx_status.get() + RX_STATUS_SLOTS)          // (one of the context's own words: the next one in the rotation)
+    {
+        a.status_next = c->d_rx_status.get() + ((uint32_t)(d_status - c->d_rx_status.get()) + 1) % RX_STATUS_SLOTS;
+        c->rx_next_clean = true;
+    }
+    if (sp) { a.sp_tstart = sp->tstart; a.sp_tbits = sp->tbits; a.sp_words = sp_words; }
+    hipLaunchKernelGGL(k_rx_match, dim3((uint32_t)nblk), dim3(RXT), (a.image_words * 4 + 15) & ~15u, s, a);
+    hipLaunchKernelGGL(k_rx_mark, dim3((uint32_t)nblk), dim3(RXB), 0, s, a);
+    HIP_TRY(hipGetLastError());
+    return SPL_OK;
+}
+}  // namespace

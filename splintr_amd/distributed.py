@@ -154,7 +154,7 @@ def plan_shards(docs: Sequence[bytes], world: int, split_docs: bool = True,
     mistral_v3: SURVEY 8e; spl_scan.h is_sync rule (d)), so the ids of the two pieces concatenate to the ids of
     the document.  It is NOT one for an arbitrary pattern (`[^\n]+\n*\p{L}+` matches across it): callers whose
     tokenizer has a custom pattern pass split_docs=False (encode_batch_sharded does so by itself; the C host
-    path likewise, `may_cut`, spl_api.hip).  This is what lets
+    path likewise, `may_cut`, csrc/spl_pipeline.h).  This is what lets
     100 equal 2 MiB documents (BASELINE config 5), or ONE huge document (the reference's
     encode_rayon case, src/core/tokenizer.rs:815-837), spread evenly over 8 GPUs."""
     n = len(docs)
@@ -210,7 +210,7 @@ def encode_batch_sharded(encode_csr, texts: Sequence[str], device: torch.device,
 
     `special_literals`: when `encode_csr` encodes WITH special tokens, pass the literals of its map.  A cut
     sits directly behind a newline, so it can only fall inside a literal that contains one; if any does,
-    documents are not cut at all (what spl_encode_batch's host path does: `special_newline`, spl_api.hip).
+    documents are not cut at all (what spl_encode_batch's host path does: `special_newline`, csrc/spl_pipeline.h).
 
     `context_free_cuts`: whether "behind a newline, in front of an ASCII letter or digit" is a match boundary of the
     encoder's split pattern whatever surrounds it.  True for the three built-in patterns, unknown for a custom one

@@ -1,6 +1,6 @@
 // host_san.cpp -- TEST TOOL: the product's host-only code under sanitizers (no GPU): the table builder
 // (spl_tables.cpp: tiktoken / SPLV parser, salted placement, pair table) and the host splitter (spl_regex.cpp)
-// splitting many documents from several threads into SHARED bitmaps, as spl_api.hip's host_split_docs does.
+// splitting many documents from several threads into SHARED bitmaps, as spl_host_split.h's host_split_docs does.
 //   host_san <vocab.splv> <unicode_classes.bin> <corpus.bin>      corpus.bin = u64 n_docs | u64 off[n + 1] | bytes
 // Built by tests/test_sanitizers.py with -fsanitize=address,undefined and with -fsanitize=thread.
 #include <atomic>

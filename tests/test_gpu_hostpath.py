@@ -209,7 +209,7 @@ def test_round_trip_property_on_arbitrary_unicode():
 
 
 def test_latency_path_equals_the_pipeline_and_the_oracle(coracle):
-    """Batches of at most 4 KB / 256 documents take encode_small (csrc/spl_api.hip: text read from pinned host memory, completion by a
+    """Batches of at most 4 KB / 256 documents take encode_small (csrc/spl_pipeline.h: text read from pinned host memory, completion by a
     word the host spins on): the same ids as the chunk pipeline and as the oracle, at every size up to and across the limit, for
     several documents, empty ones, special tokens, multi-byte text cut by the limit; and the counter says which calls took it.
     Reference: Tokenizer::encode, src/core/tokenizer.rs:729-808."""
