@@ -275,6 +275,52 @@ int spl_gatherv_unpack_group(spl_tokenizer* t, const uint32_t* d_slabs, uint32_t
                              uint64_t cap_words, uint64_t max_docs, uint32_t* d_all_ids, uint64_t all_ids_cap,
                              uint64_t* d_all_off, uint64_t off_stride, uint32_t* d_status, void* hip_stream);
 
+/* From the CSR to what a model on the same GPU reads: padding and sequence packing ON THE DEVICE, one launch each behind the encode on
+ * the same stream.  The reference has no counterpart: it returns Vec<Vec<u32>> (src/core/tokenizer.rs:932-942) and leaves both to the caller.
+ * Both calls are fully asynchronous on `hip_stream`, neither allocate nor synchronise, use the handle only for its device (as
+ * spl_gatherv_pack does) and take ANY CSR with d_out_off[0] == 0 in device memory, not only one the handle produced.  The ids must
+ * actually be there: after an encode whose d_out_off[n_docs] exceeded its ids_capacity the values of the dropped range are unspecified.
+ * Ids are bit patterns (a special token's id may be any u32): int32 rows store the 32 bits, int64 rows (SPL_COLLATE_I64) ZERO-extend,
+ * never sign-extend.  k = (BOS ? 1 : 0) + (EOS ? 1 : 0) below.
+ *
+ *   spl_pad_device   d_rows[n_docs, row_len]: row d = [bos_id] + tokens_d' + [eos_id], where tokens_d' is document d's ids cut to the
+ *                    budget row_len - k -- the head is kept; with SPL_COLLATE_KEEP_TAIL the tail -- and BOS / EOS are never cut away.
+ *                    The rest of the row is pad_id, on the right (SPL_COLLATE_PAD_LEFT: on the left).  d_mask[d, c] (bytes, NULL:
+ *                    not wanted) = 1 where the entry is not padding, d_len[d] (NULL: not wanted) = the number of such entries
+ *                    (k for an empty document).  n_docs == 0: nothing to do.
+ *   spl_pack_device  the stream = the concatenation over d of [bos_id] tokens_d [eos_id], S = d_out_off[n_docs] + n_docs * k entries,
+ *                    cut into n_rows = ceil(S / row_len) rows; nothing is truncated.  Element (r, c) is stream position
+ *                    p = r * row_len + c.  For p < S its document is the LARGEST d with d_out_off[d] + d * k <= p (empty documents add
+ *                    nothing when k == 0 and are skipped), j = p minus that start; the value is bos_id if BOS is on and j == 0,
+ *                    eos_id if EOS is on and j == len_d + BOS, ids[d_out_off[d] + j - BOS] otherwise; d_doc[p] = d (the index
+ *                    within the batch) and d_pos[p] = p - max(start_d, r * row_len): positions restart at a document's start and at a
+ *                    row's start, a row being the attention context.  For p >= S, up to the end of the buffer: pad_id, d_doc = -1,
+ *                    d_pos = 0.  Every element of the rows_cap rows is written, nothing at or beyond them; d_n[0] always receives
+ *                    n_rows -- the need: compare it with rows_cap, as d_out_off[n_docs] with ids_capacity -- and d_n[1] receives S.
+ *                    n_docs == 0 or S == 0: d_n = {0, 0}.  d_doc / d_pos [rows_cap * row_len] may be NULL.
+ *
+ * SPL_EINVAL, with the cause in spl_last_error() and before anything touches the device: a null required pointer (d_rows is required
+ * where there is a row to write); a struct_size of 0, shorter than the fields below or above 4096 (a longer struct up to that is accepted, its
+ * tail ignored, as for spl_opts); row_len == 0; pad mode with row_len < k; SPL_COLLATE_PAD_LEFT or _KEEP_TAIL in pack mode; an unknown flag bit; d_rows,
+ * d_doc, d_pos or d_len not 16-byte aligned, d_mask not 4-byte aligned; n_docs >= 2^31; rows_cap * row_len beyond 2^63. */
+#define SPL_COLLATE_I64       1u   /* rows are int64 (torch.long); default int32 */
+#define SPL_COLLATE_PAD_LEFT  2u   /* pad mode only */
+#define SPL_COLLATE_KEEP_TAIL 4u   /* pad mode only: truncation drops the FRONT of a document */
+#define SPL_COLLATE_BOS       8u
+#define SPL_COLLATE_EOS       16u
+
+typedef struct spl_collate_opts {
+    uint32_t struct_size;   /* sizeof the struct as the CALLER was compiled: versioned exactly like spl_opts */
+    uint32_t flags, row_len, pad_id, bos_id, eos_id;
+} spl_collate_opts;
+
+int spl_pad_device(spl_tokenizer* t, const uint32_t* d_ids, const uint64_t* d_out_off, uint64_t n_docs,
+                   const spl_collate_opts* o, void* d_rows /* [n_docs*row_len] */, uint8_t* d_mask /* NULL ok */,
+                   int32_t* d_len /* NULL ok */, void* hip_stream);
+int spl_pack_device(spl_tokenizer* t, const uint32_t* d_ids, const uint64_t* d_out_off, uint64_t n_docs,
+                    const spl_collate_opts* o, void* d_rows /* [rows_cap*row_len] */, uint64_t rows_cap,
+                    int32_t* d_doc /* NULL ok */, int32_t* d_pos /* NULL ok */, uint64_t* d_n /* [2] */, void* hip_stream);
+
 /* ONE batch exchanged in WAVES (strong scaling, pipelined: the ids of wave k travel while wave k + 1 encodes).  The batch's documents, in
  * their order, are cut into waves and every wave into one contiguous slice per rank; rank r encodes its slice of wave k into a slab
  * (spl_encode_batch_device_packed), one all-gather of equal slabs moves the wave (spl_allgather_slabs / _p2p), and this call unpacks the

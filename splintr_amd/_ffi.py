@@ -29,9 +29,11 @@ SYMBOLS = [
     "spl_comm_unique_id", "spl_comm_create", "spl_comm_destroy", "spl_comm_rank", "spl_comm_world",
     "spl_allgather_slabs", "spl_allgather_slabs_p2p", "spl_gatherv_unpack_at", "spl_allgatherv_csr", "spl_split_host", "spl_encode_chunks_device",
     "spl_split_device", "spl_device_split_fallbacks", "spl_small_path_calls", "spl_pick_stream", "spl_memo_stats",
+    "spl_pad_device", "spl_pack_device",
 ]
 SPL_PATTERN_CUSTOM = 3
 SPL_OPT_BYTE_LEVEL = 1
+SPL_COLLATE_I64, SPL_COLLATE_PAD_LEFT, SPL_COLLATE_KEEP_TAIL, SPL_COLLATE_BOS, SPL_COLLATE_EOS = 1, 2, 4, 8, 16
 
 
 class SplOpts(ctypes.Structure):
@@ -40,6 +42,15 @@ class SplOpts(ctypes.Structure):
 
     def __init__(self, pattern=0, device=0, flags=0, pattern_text=None):
         super().__init__(ctypes.sizeof(SplOpts), pattern, device, flags, pattern_text, len(pattern_text) if pattern_text else 0)
+
+
+class SplCollateOpts(ctypes.Structure):
+    """spl_collate_opts (include/splintr_hip.h): what spl_pad_device / spl_pack_device are told about a row."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("row_len", ctypes.c_uint32),
+                ("pad_id", ctypes.c_uint32), ("bos_id", ctypes.c_uint32), ("eos_id", ctypes.c_uint32)]
+
+    def __init__(self, flags=0, row_len=0, pad_id=0, bos_id=0, eos_id=0):
+        super().__init__(ctypes.sizeof(SplCollateOpts), flags, row_len, pad_id, bos_id, eos_id)
 
 
 _lib = None
@@ -137,6 +148,8 @@ def lib() -> ctypes.CDLL:
                                         vp, vp, vp]
     L.spl_allgatherv_csr.argtypes = [vp, vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, ctypes.c_uint64,
                                      u64p, u64p, vp]
+    L.spl_pad_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.POINTER(SplCollateOpts), vp, vp, vp, vp]
+    L.spl_pack_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.POINTER(SplCollateOpts), vp, ctypes.c_uint64, vp, vp, vp, vp]
     _lib = L
     return L
 

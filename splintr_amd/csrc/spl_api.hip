@@ -1,7 +1,7 @@
 // spl_api.hip -- the C ABI (include/splintr_hip.h): the root of the library's one HIP translation unit.  It includes the kernels
 // (spl_kernels.hip) and the host side, one file per concern and each building on the ones before it -- spl_host_res.h (resource owners,
 // pinned pool), spl_ctx.h (per-GPU context, handle, uploads), spl_streams.h (stream probe), spl_launch.h (memo, launch order, device
-// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h -- and holds the entry points.
+// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h -- and holds the entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -39,6 +39,7 @@ using namespace spl;
 #include "spl_pipeline.h"
 #include "spl_decode_host.h"
 #include "spl_collective.h"
+#include "spl_collate_host.h"
 
 namespace {
 // No exception crosses the C ABI: every entry point that allocates (std::bad_alloc), starts threads or grows
@@ -384,6 +385,17 @@ int spl_gatherv_unpack_at(spl_tokenizer* t, const uint32_t* d_slabs, uint32_t wo
     hipLaunchKernelGGL(k_gatherv_advance, dim3(1), dim3(64), 0, (hipStream_t)hip_stream, d_slabs, world, (uint32_t)cap_words, d_run);
     HIP_TRY(hipGetLastError());
     return SPL_OK;
+}
+
+int spl_pad_device(spl_tokenizer* t, const uint32_t* d_ids, const uint64_t* d_out_off, uint64_t n_docs, const spl_collate_opts* o,
+                   void* d_rows, uint8_t* d_mask, int32_t* d_len, void* hip_stream) {
+    return guarded("spl_pad_device", [&] { return pad_device(t, d_ids, d_out_off, n_docs, o, d_rows, d_mask, d_len, (hipStream_t)hip_stream); });
+}
+
+int spl_pack_device(spl_tokenizer* t, const uint32_t* d_ids, const uint64_t* d_out_off, uint64_t n_docs, const spl_collate_opts* o,
+                    void* d_rows, uint64_t rows_cap, int32_t* d_doc, int32_t* d_pos, uint64_t* d_n, void* hip_stream) {
+    return guarded("spl_pack_device", [&] {
+        return pack_device(t, d_ids, d_out_off, n_docs, o, d_rows, rows_cap, d_doc, d_pos, d_n, (hipStream_t)hip_stream); });
 }
 
 int spl_debug_blocks(spl_tokenizer* t, unsigned long long* out, int max_blocks) {

@@ -1,7 +1,8 @@
 """Device-resident batch encode: torch tensors in HBM in, CSR tensors in HBM out.
 
 PyTorch is plumbing here (device memory, streams, torch.distributed); the work is done by
-`spl_encode_batch_device` (include/splintr_hip.h) on torch's current HIP stream.
+`spl_encode_batch_device` (include/splintr_hip.h) on torch's current HIP stream -- and, for a model on the same GPU, by
+`spl_pad_device` / `spl_pack_device` behind it: the CSR as a padded batch or as packed sequences, one launch each.
 """
 from __future__ import annotations
 
@@ -52,6 +53,82 @@ def result_csr(batch: DeviceBatch) -> Tuple[np.ndarray, np.ndarray]:
     off = batch.out_off.cpu().numpy().astype(np.uint64)
     ids = batch.ids[: int(off[-1])].cpu().numpy().view(np.uint32)
     return ids, off
+
+
+def _collate_opts(row_len: int, pad_id: int, bos_id: Optional[int], eos_id: Optional[int], dtype, flags: int = 0):
+    """spl_collate_opts for one call; ValueError for what the Python surface can refuse by itself."""
+    if dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"dtype must be torch.int32 or torch.int64, not {dtype}")
+    for name, v in (("pad_id", pad_id), ("bos_id", bos_id), ("eos_id", eos_id)):
+        if v is not None and not 0 <= int(v) < (1 << 32):
+            raise ValueError(f"{name} must fit 32 bits")
+    if int(row_len) <= 0 or int(row_len) >= (1 << 32):
+        raise ValueError("the row length must be in 1 .. 2**32 - 1")
+    flags |= _ffi.SPL_COLLATE_I64 if dtype == torch.int64 else 0
+    flags |= _ffi.SPL_COLLATE_BOS if bos_id is not None else 0
+    flags |= _ffi.SPL_COLLATE_EOS if eos_id is not None else 0
+    return _ffi.SplCollateOpts(flags, int(row_len), int(pad_id), int(bos_id or 0), int(eos_id or 0))
+
+
+def _side(name: str, value: str) -> bool:
+    if value not in ("right", "left"):
+        raise ValueError(f"{name} must be 'right' or 'left', not {value!r}")
+    return value == "left"
+
+
+def check_collate_args(row_len: int, pad_id: int, bos_id: Optional[int], eos_id: Optional[int], dtype, padding_side: str = "right",
+                       truncation_side: str = "right") -> None:
+    """ValueError for a dtype, side string, id or row length that pad_device / pack_device would refuse -- for callers that want to
+    know before they put a batch on the device."""
+    _side("padding_side", padding_side)
+    _side("truncation_side", truncation_side)
+    _collate_opts(row_len, pad_id, bos_id, eos_id, dtype)
+
+
+def pad_device(tok: Tokenizer, batch: DeviceBatch, max_length: int, *, pad_id: int, bos_id: Optional[int] = None,
+               eos_id: Optional[int] = None, padding_side: str = "right", truncation_side: str = "right",
+               dtype: torch.dtype = torch.int32) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """batch's CSR (encode_device) as a dense batch, ONE launch on torch's current stream (spl_pad_device): row d = [bos_id] + the ids
+    of document d cut to max_length - (BOS + EOS) + [eos_id], padded with pad_id.  truncation_side "right" keeps a document's head,
+    "left" its tail; BOS and EOS are never cut away.  Returns (input_ids [n_docs, L], attention_mask uint8 [n_docs, L], lengths int32
+    [n_docs]); nothing synchronises."""
+    flags = (_ffi.SPL_COLLATE_PAD_LEFT if _side("padding_side", padding_side) else 0) | \
+        (_ffi.SPL_COLLATE_KEEP_TAIL if _side("truncation_side", truncation_side) else 0)
+    o = _collate_opts(max_length, pad_id, bos_id, eos_id, dtype, flags)
+    dev = batch.ids.device
+    rows = torch.empty((batch.n_docs, o.row_len), dtype=dtype, device=dev)       # (every element is written by the kernel)
+    mask = torch.empty((batch.n_docs, o.row_len), dtype=torch.uint8, device=dev)
+    lens = torch.empty(batch.n_docs, dtype=torch.int32, device=dev)
+    rc = _ffi.lib().spl_pad_device(tok.handle, batch.ids.data_ptr(), batch.out_off.data_ptr(), batch.n_docs, ctypes.byref(o),
+                                   rows.data_ptr(), mask.data_ptr(), lens.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise (ValueError if rc == -1 else RuntimeError)(f"spl_pad_device failed ({rc}): {_ffi.last_error()}")
+    return rows, mask, lens
+
+
+def pack_device(tok: Tokenizer, batch: DeviceBatch, seq_len: int, *, pad_id: int, bos_id: Optional[int] = None,
+                eos_id: Optional[int] = None, dtype: torch.dtype = torch.int32,
+                max_rows: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """batch's CSR as ONE stream -- [bos_id] ids_0 [eos_id] [bos_id] ids_1 [eos_id] ... -- cut into rows of seq_len, ONE launch on torch's
+    current stream (spl_pack_device); nothing is truncated.  Returns (rows [max_rows, L], doc_ids int32 [max_rows, L], positions int32
+    [max_rows, L], n): n is a DEVICE tensor (int64[2]: the rows the stream needs, its length), so nothing synchronises here; rows from
+    n[0] on hold pad_id, doc_ids -1 there.  The default max_rows, ceil((batch.n_bytes + n_docs * (BOS + EOS)) / L), always suffices (a
+    token has at least one byte); with a smaller one compare n[0] with it."""
+    o = _collate_opts(seq_len, pad_id, bos_id, eos_id, dtype)
+    k = (bos_id is not None) + (eos_id is not None)
+    if max_rows is None:
+        max_rows = (batch.n_bytes + batch.n_docs * k + o.row_len - 1) // o.row_len
+    dev = batch.ids.device
+    rows = torch.empty((int(max_rows), o.row_len), dtype=dtype, device=dev)      # (every element is written by the kernel)
+    doc = torch.empty((int(max_rows), o.row_len), dtype=torch.int32, device=dev)
+    pos = torch.empty((int(max_rows), o.row_len), dtype=torch.int32, device=dev)
+    n = torch.empty(2, dtype=torch.int64, device=dev)
+    rc = _ffi.lib().spl_pack_device(tok.handle, batch.ids.data_ptr(), batch.out_off.data_ptr(), batch.n_docs, ctypes.byref(o),
+                                    rows.data_ptr(), int(max_rows), doc.data_ptr(), pos.data_ptr(), n.data_ptr(),
+                                    torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise (ValueError if rc == -1 else RuntimeError)(f"spl_pack_device failed ({rc}): {_ffi.last_error()}")
+    return rows, doc, pos, n
 
 
 class Comm:

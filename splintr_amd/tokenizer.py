@@ -277,6 +277,43 @@ class Tokenizer:
         """src/python/bindings.rs:348-350."""
         return self._batch(texts, _ffi.SPL_WITH_SPECIAL)
 
+    # ------------------------------------------------------------------ tokens a model on the same GPU reads (device tensors)
+    def _encode_on_device(self, texts: Sequence[str], with_special: bool):
+        import torch                                 # (lazily: this module imports without torch)
+        from . import device as dv
+        batch = dv.DeviceBatch(texts, torch.device("cuda", self._device))
+        dv.encode_device(self, batch, with_special)
+        return dv, batch
+
+    def encode_batch_padded(self, texts: Sequence[str], max_length: int, *, pad_id: int, with_special: bool = False,
+                            bos_id: Optional[int] = None, eos_id: Optional[int] = None, padding_side: str = "right",
+                            truncation_side: str = "right", dtype=None):
+        """Extension: encode_batch as a dense batch ON THE GPU -- (input_ids [n_docs, max_length], attention_mask uint8, lengths int32),
+        torch tensors on this tokenizer's device; dtype torch.int32 (default) or torch.int64.  The texts go to the device, the encode
+        and ONE more launch (splintr_amd.device.pad_device) run on torch's current stream, nothing synchronises in between."""
+        import torch
+        from . import device as dv
+        dtype = torch.int32 if dtype is None else dtype
+        dv.check_collate_args(max_length, pad_id, bos_id, eos_id, dtype, padding_side, truncation_side)   # (before anything goes to the device)
+        dv, batch = self._encode_on_device(texts, with_special)
+        return dv.pad_device(self, batch, max_length, pad_id=pad_id, bos_id=bos_id, eos_id=eos_id, padding_side=padding_side,
+                             truncation_side=truncation_side, dtype=dtype)
+
+    def encode_batch_packed(self, texts: Sequence[str], seq_len: int, *, pad_id: int, with_special: bool = False,
+                            bos_id: Optional[int] = None, eos_id: Optional[int] = None, dtype=None):
+        """Extension: encode_batch as packed sequences ON THE GPU -- the documents, each as [bos_id] ids [eos_id], joined into one
+        stream and cut into rows of seq_len: (rows [n_rows, seq_len], doc_ids int32, positions int32); the tail of the last row holds
+        pad_id (doc_ids -1).  Positions restart at every document and every row.  ONE synchronisation, to learn n_rows."""
+        import torch
+        from . import device as dv
+        dtype = torch.int32 if dtype is None else dtype
+        dv.check_collate_args(seq_len, pad_id, bos_id, eos_id, dtype)        # (before anything goes to the device)
+        dv, batch = self._encode_on_device(texts, with_special)
+        rows, doc, pos, n = dv.pack_device(self, batch, seq_len, pad_id=pad_id, bos_id=bos_id, eos_id=eos_id,
+                                           dtype=dtype)
+        n_rows = int(n[0].item())
+        return rows[:n_rows], doc[:n_rows], pos[:n_rows]
+
     # ------------------------------------------------------------------ decode (test helper / "next" row)
     def decode_bytes(self, tokens: Sequence[int]) -> bytes:
         """src/python/bindings.rs:313-315."""
