@@ -385,6 +385,60 @@ int spl_decode_batch(spl_tokenizer* t, const uint32_t* ids, const uint64_t* ids_
                      uint8_t** out_bytes, uint64_t** out_off);
 void spl_free(void* p);
 
+/* The same decode with everything in DEVICE memory: ids in HBM to a bytes CSR in HBM, three launches on `hip_stream`.
+ * Per document the semantics are spl_decode_batch's (Tokenizer::decode_bytes): a vocabulary id gives its bytes (ByteLevel: the raw bytes;
+ * a key that is not ByteLevel text gives the key itself), otherwise an id of the special map gives its literal, any other id gives
+ * nothing; nothing is validated as UTF-8.  The output is d_bytes plus d_out_off[n_docs + 1]: d_out_off[0] = 0, d_out_off[n_docs] = the
+ * byte count NEEDED.  Bytes at or beyond bytes_capacity are dropped (the ids_capacity convention of spl_encode_batch_device: compare the
+ * need with the capacity); nothing at or beyond d_bytes + min(need, bytes_capacity) is written; every one of the n_docs + 1 offsets is
+ * written exactly once, whatever the capacity; n_docs == 0 writes d_out_off[0] = 0.  d_bytes (16-byte aligned) and the u64 offsets are
+ * exactly what spl_encode_batch_device takes as its input: decode with one handle, encode with another, two calls on one stream.
+ * (That call wants its text readable up to the next multiple of 16, not zeroed: a d_bytes whose capacity is a multiple of 16 is enough; the
+ * decode leaves the bytes between the need and that multiple unwritten.)
+ *
+ *   CSR mode (row_len == 0)   document d is ids[d_ids_off[d] .. d_ids_off[d + 1]), d_ids_off[0] == 0, d_len NULL.  The host does not know
+ *                    d_ids_off[n_docs] without synchronising: the grid covers n_ids_cap, ANY upper bound (the ids_capacity of the encode
+ *                    in front is one).  Ids at or beyond d_ids_off[n_docs] are not read.  If the CSR claims more than n_ids_cap every
+ *                    offset is clamped to it: the dropped ids of an overflowed encode decode to nothing and are not read.
+ *   rows mode (row_len > 0)   document r is row r of ids[n_docs, row_len] (what a sampler leaves, the inverse of spl_pad_device), d_ids_off
+ *                    NULL, n_ids_cap ignored.  With d_len [n_docs] the valid entries of row r are its first d_len[r] -- with
+ *                    SPL_DECODE_PAD_LEFT its last -- d_len[r] clamped to 0 .. row_len; with d_len NULL every entry is valid.  An entry
+ *                    that is not valid contributes nothing.
+ *   SPL_DECODE_I64   ids are 64-bit (torch.long); a value outside 0 .. 2^32 - 1 (-1, -100, anything sign-extended, 2^32 + 17) is an id of
+ *                    neither map and gives nothing.  Without the flag ids are 32-bit patterns (int32 input is read as uint32).
+ *   SPL_DECODE_SKIP_SPECIAL   an id the vocabulary lacks and the special map holds gives nothing; an id both maps hold is a vocabulary id
+ *                    and is emitted (the reference looks in `decoder` first).
+ *
+ * spl_decode_reserve_device uploads the decode tables (synchronises once) and sizes the scratch -- 8 bytes per 1 024 ids, grow-only, shared
+ * with neither spl_decode_batch nor the encode workspace -- for max_ids ids (rows mode: n_docs * row_len).  After it, calls within that
+ * size neither allocate nor synchronise and are fully asynchronous on hip_stream; a call that was not reserved for does both once and is
+ * then asynchronous.  Device decodes of ONE handle share that scratch: they need stream order among themselves; encode and decode calls
+ * on one handle need only stream order between producer and consumer.
+ *
+ * SPL_EINVAL, with the cause in spl_last_error() and before anything touches the device: a null t, o or d_out_off; a null d_ids where
+ * there is an id to read; a null d_bytes with bytes_capacity > 0; a struct_size of 0, shorter than the fields below or above 4096 (a
+ * longer struct up to that is accepted, its tail ignored); an unknown flag bit; SPL_DECODE_PAD_LEFT or d_len in CSR mode; a missing
+ * d_ids_off in CSR mode, a d_ids_off in rows mode; d_bytes not 16-byte aligned; d_ids not aligned to four ids (16 bytes, 32 with
+ * SPL_DECODE_I64); n_docs >= 2^31; an id count (n_ids_cap, or n_docs * row_len) of 2^41 or more (one workgroup per 1 024 ids). */
+#define SPL_DECODE_I64          1u  /* ids are int64 (torch.long); default uint32/int32 bit patterns */
+#define SPL_DECODE_PAD_LEFT     2u  /* rows mode only: a row's valid entries are its LAST d_len[r] */
+#define SPL_DECODE_SKIP_SPECIAL 4u  /* ids that only the special-token map knows contribute nothing */
+
+typedef struct spl_decode_opts {
+    uint32_t struct_size;           /* sizeof the struct as the CALLER was compiled: versioned exactly like spl_opts / spl_collate_opts */
+    uint32_t flags;
+    uint32_t row_len;               /* 0: CSR mode; > 0: rows mode, ids are [n_docs, row_len] */
+} spl_decode_opts;
+
+int spl_decode_reserve_device(spl_tokenizer* t, uint64_t max_ids);
+int spl_decode_batch_device(spl_tokenizer* t, const void* d_ids, uint64_t n_ids_cap,
+                            const uint64_t* d_ids_off /* CSR mode: [n_docs+1] */,
+                            const int32_t* d_len      /* rows mode: [n_docs], NULL = every entry valid */,
+                            uint64_t n_docs, const spl_decode_opts* o,
+                            uint8_t* d_bytes, uint64_t bytes_capacity,
+                            uint64_t* d_out_off /* [n_docs+1] */, void* hip_stream);
+uint32_t spl_max_token_bytes(const spl_tokenizer* t);   /* longest byte string any id decodes to (computed once, again after spl_add_special) */
+
 /* Host-side lookup of ONE id, for consumers that decode token by token on the CPU -- the streaming
  * decoders (src/core/streaming.rs, src/python/bindings.rs:465-834 take clones of Tokenizer::decoder
  * and special_tokens_decoder).  *bytes / *len = what decode_bytes emits for the id; the pointer

@@ -30,10 +30,12 @@ SYMBOLS = [
     "spl_allgather_slabs", "spl_allgather_slabs_p2p", "spl_gatherv_unpack_at", "spl_allgatherv_csr", "spl_split_host", "spl_encode_chunks_device",
     "spl_split_device", "spl_device_split_fallbacks", "spl_small_path_calls", "spl_pick_stream", "spl_memo_stats",
     "spl_pad_device", "spl_pack_device",
+    "spl_decode_reserve_device", "spl_decode_batch_device", "spl_max_token_bytes",
 ]
 SPL_PATTERN_CUSTOM = 3
 SPL_OPT_BYTE_LEVEL = 1
 SPL_COLLATE_I64, SPL_COLLATE_PAD_LEFT, SPL_COLLATE_KEEP_TAIL, SPL_COLLATE_BOS, SPL_COLLATE_EOS = 1, 2, 4, 8, 16
+SPL_DECODE_I64, SPL_DECODE_PAD_LEFT, SPL_DECODE_SKIP_SPECIAL = 1, 2, 4
 
 
 class SplOpts(ctypes.Structure):
@@ -51,6 +53,14 @@ class SplCollateOpts(ctypes.Structure):
 
     def __init__(self, flags=0, row_len=0, pad_id=0, bos_id=0, eos_id=0):
         super().__init__(ctypes.sizeof(SplCollateOpts), flags, row_len, pad_id, bos_id, eos_id)
+
+
+class SplDecodeOpts(ctypes.Structure):
+    """spl_decode_opts (include/splintr_hip.h): flags and the mode of spl_decode_batch_device (row_len 0: CSR, > 0: rows)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("row_len", ctypes.c_uint32)]
+
+    def __init__(self, flags=0, row_len=0):
+        super().__init__(ctypes.sizeof(SplDecodeOpts), flags, row_len)
 
 
 _lib = None
@@ -150,6 +160,11 @@ def lib() -> ctypes.CDLL:
                                      u64p, u64p, vp]
     L.spl_pad_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.POINTER(SplCollateOpts), vp, vp, vp, vp]
     L.spl_pack_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.POINTER(SplCollateOpts), vp, ctypes.c_uint64, vp, vp, vp, vp]
+    L.spl_decode_reserve_device.argtypes = [vp, ctypes.c_uint64]
+    L.spl_decode_batch_device.argtypes = [vp, vp, ctypes.c_uint64, vp, vp, ctypes.c_uint64, ctypes.POINTER(SplDecodeOpts), vp,
+                                          ctypes.c_uint64, vp, vp]
+    L.spl_max_token_bytes.restype = ctypes.c_uint32
+    L.spl_max_token_bytes.argtypes = [vp]
     _lib = L
     return L
 

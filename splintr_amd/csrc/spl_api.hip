@@ -1,7 +1,7 @@
 // spl_api.hip -- the C ABI (include/splintr_hip.h): the root of the library's one HIP translation unit.  It includes the kernels
 // (spl_kernels.hip) and the host side, one file per concern and each building on the ones before it -- spl_host_res.h (resource owners,
 // pinned pool), spl_ctx.h (per-GPU context, handle, uploads), spl_streams.h (stream probe), spl_launch.h (memo, launch order, device
-// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h -- and holds the entry points.
+// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_decode_dev_host.h -- and holds the entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -40,6 +40,7 @@ using namespace spl;
 #include "spl_decode_host.h"
 #include "spl_collective.h"
 #include "spl_collate_host.h"
+#include "spl_decode_dev_host.h"
 
 namespace {
 // No exception crosses the C ABI: every entry point that allocates (std::bad_alloc), starts threads or grows
@@ -187,6 +188,7 @@ static int spl_add_special_impl(spl_tokenizer* t, const uint8_t* literal, size_t
     }
     for (auto& c : t->ctx) { c->sp_uploaded = false; c->dec_uploaded = false; if (c->twin) c->twin->sp_uploaded = false; }
     t->max_special_id = 0;
+    t->max_tok_bytes = 0;
     for (const auto& sp : t->specials) t->max_special_id = std::max(t->max_special_id, sp.id);
     if (lit.find('\n') != std::string::npos) t->special_newline = true;
     return SPL_OK;
@@ -391,6 +393,19 @@ int spl_pad_device(spl_tokenizer* t, const uint32_t* d_ids, const uint64_t* d_ou
                    void* d_rows, uint8_t* d_mask, int32_t* d_len, void* hip_stream) {
     return guarded("spl_pad_device", [&] { return pad_device(t, d_ids, d_out_off, n_docs, o, d_rows, d_mask, d_len, (hipStream_t)hip_stream); });
 }
+
+int spl_decode_reserve_device(spl_tokenizer* t, uint64_t max_ids) {
+    return guarded("spl_decode_reserve_device", [&] { return decode_reserve_device(t, max_ids); });
+}
+
+int spl_decode_batch_device(spl_tokenizer* t, const void* d_ids, uint64_t n_ids_cap, const uint64_t* d_ids_off, const int32_t* d_len,
+                            uint64_t n_docs, const spl_decode_opts* o, uint8_t* d_bytes, uint64_t bytes_capacity, uint64_t* d_out_off,
+                            void* hip_stream) {
+    return guarded("spl_decode_batch_device", [&] {
+        return decode_batch_device(t, d_ids, n_ids_cap, d_ids_off, d_len, n_docs, o, d_bytes, bytes_capacity, d_out_off, (hipStream_t)hip_stream); });
+}
+
+uint32_t spl_max_token_bytes(const spl_tokenizer* t) { return t ? max_token_bytes(t) : 0u; }
 
 int spl_pack_device(spl_tokenizer* t, const uint32_t* d_ids, const uint64_t* d_out_off, uint64_t n_docs, const spl_collate_opts* o,
                     void* d_rows, uint64_t rows_cap, int32_t* d_doc, int32_t* d_pos, uint64_t* d_n, void* hip_stream) {

@@ -32,7 +32,9 @@ struct Ctx {
     DevBuf<uint8_t> d_tok_bytes;
     uint32_t dec_max_id = 0;
     DevBuf<uint32_t> d_dec_sp_ids, d_dec_sp_off; uint32_t dec_n_sp = 0;   // specials beyond the vocabulary's ids
+    DevBuf<uint32_t> d_dec_spbits;             // one bit per id of the dense table: only the special map holds it (SPL_DECODE_SKIP_SPECIAL)
     bool dec_uploaded = false;
+    DevBuf<uint64_t> d_ddblk; uint64_t ddblk_cap = 0;   // spl_decode_batch_device: block sums, 8 bytes per 1 024 ids (grow-only; shared with nothing)
     DevBuf<uint8_t> d_sp_lits;                 // uploaded lazily; invalidated by spl_add_special
     bool sp_uploaded = false;
     // workspace
@@ -164,6 +166,7 @@ struct spl_tokenizer {
     HostTables ht;
     std::vector<Special> specials;
     uint32_t max_special_id = 0;
+    mutable uint32_t max_tok_bytes = 0;       // spl_max_token_bytes, computed at its first call (0: not yet; spl_add_special resets it)
     bool special_newline = false;             // a literal contains '\n': no sub-document cuts with SPL_WITH_SPECIAL
     bool special_general = false;             // occurrences can overlap, or a literal exceeds SP_MAXLEN: the two-launch general matcher
     RegexPtr regex;                           // SPL_PATTERN_CUSTOM: the host splitter's program (null: one of the GPU scanner's patterns)
@@ -362,14 +365,14 @@ int upload_decode(spl_tokenizer* tk, Ctx* t) {
         }
     }
     std::sort(far.begin(), far.end(), [](const Special* a, const Special* b) { return a->id < b->id; });
-    std::vector<uint32_t> off(max_id + 2, 0);
+    std::vector<uint32_t> off(max_id + 2, 0), sp_bits(max_id / 32 + 1, 0);
     std::vector<uint8_t> bytes;
     bytes.reserve(tk->ht.tok_bytes.size() + 4096);
     for (uint32_t id = 0; id <= max_id; id++) {
         off[id] = (uint32_t)bytes.size();
         const bool in_vocab = tk->ht.tok_present[id];
         if (in_vocab) bytes.insert(bytes.end(), tk->ht.tok_bytes.begin() + tk->ht.tok_off[id], tk->ht.tok_bytes.begin() + tk->ht.tok_off[id + 1]);
-        else if (sp[id]) bytes.insert(bytes.end(), sp[id]->lit.begin(), sp[id]->lit.end());
+        else if (sp[id]) { bytes.insert(bytes.end(), sp[id]->lit.begin(), sp[id]->lit.end()); sp_bits[id >> 5] |= 1u << (id & 31); }
     }
     off[max_id + 1] = (uint32_t)bytes.size();
     std::vector<uint32_t> sp_ids, sp_off;
@@ -384,6 +387,7 @@ int upload_decode(spl_tokenizer* tk, Ctx* t) {
     SPL_TRY(t->d_tok_bytes.upload(bytes));
     SPL_TRY(t->d_dec_sp_ids.upload(sp_ids));
     SPL_TRY(t->d_dec_sp_off.upload(sp_off));
+    SPL_TRY(t->d_dec_spbits.upload(sp_bits));
     t->dec_n_sp = (uint32_t)sp_ids.size();
     t->dec_max_id = max_id;
     t->dec_uploaded = true;

@@ -2,7 +2,8 @@
 
 PyTorch is plumbing here (device memory, streams, torch.distributed); the work is done by
 `spl_encode_batch_device` (include/splintr_hip.h) on torch's current HIP stream -- and, for a model on the same GPU, by
-`spl_pad_device` / `spl_pack_device` behind it: the CSR as a padded batch or as packed sequences, one launch each.
+`spl_pad_device` / `spl_pack_device` behind it: the CSR as a padded batch or as packed sequences, one launch each.  The way back is
+`spl_decode_batch_device`: ids in HBM (a CSR, or the rows a sampler leaves) to a bytes CSR in HBM.
 """
 from __future__ import annotations
 
@@ -129,6 +130,101 @@ def pack_device(tok: Tokenizer, batch: DeviceBatch, seq_len: int, *, pad_id: int
     if rc != 0:
         raise (ValueError if rc == -1 else RuntimeError)(f"spl_pack_device failed ({rc}): {_ffi.last_error()}")
     return rows, doc, pos, n
+
+
+# ---------------------------------------------------------------------------------------------- device-resident decode
+def _decode_error(rc: int) -> Exception:
+    return (ValueError if rc == -1 else RuntimeError)(f"spl_decode_batch_device failed ({rc}): {_ffi.last_error()}")
+
+
+def _max_bytes(max_bytes) -> int:
+    if isinstance(max_bytes, bool) or not isinstance(max_bytes, (int, np.integer)) or not 0 <= int(max_bytes) < (1 << 62):
+        raise ValueError(f"max_bytes must be an integer in 0 .. 2**62 - 1, not {max_bytes!r}")
+    return (int(max_bytes) + 15) // 16 * 16
+
+
+def check_decode_args(ids, offsets=None, lengths=None, *, rows: bool, max_bytes=0, padding_side: str = "right") -> None:
+    """ValueError for a dtype, rank, device, layout, side string or size that decode_device / decode_rows_device would refuse -- before
+    anything goes to the device."""
+    _side("padding_side", padding_side)
+    _max_bytes(max_bytes)
+    if not isinstance(ids, torch.Tensor) or ids.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"the ids must be a torch tensor of dtype int32 or int64, not {getattr(ids, 'dtype', type(ids))}")
+    if not ids.is_contiguous():
+        raise ValueError("the ids must be contiguous")
+    other = None
+    if rows:
+        if ids.dim() != 2:
+            raise ValueError(f"the rows must have rank 2 ([batch, steps]), not {ids.dim()}")
+        if ids.shape[1] >= (1 << 32) or ids.shape[0] >= (1 << 31):
+            raise ValueError("the rows must be fewer than 2**31 and shorter than 2**32")
+        if lengths is not None:
+            if not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.int32 or lengths.dim() != 1 or \
+                    lengths.shape[0] != ids.shape[0] or not lengths.is_contiguous():
+                raise ValueError("lengths must be a contiguous int32 tensor of shape [batch]")
+            other = ("lengths", lengths)
+    else:
+        if ids.dim() != 1:
+            raise ValueError(f"the ids of a CSR must have rank 1, not {ids.dim()}")
+        if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.shape[0] < 1 or \
+                not offsets.is_contiguous():
+            raise ValueError("offsets must be a contiguous int64 tensor of shape [n_docs + 1]")
+        if offsets.shape[0] - 1 >= (1 << 31):
+            raise ValueError("the documents must be fewer than 2**31")
+        other = ("offsets", offsets)
+    if not ids.is_cuda:
+        raise ValueError("the ids must be on a GPU (device-resident decode takes no host tensor)")
+    if other is not None and other[1].device != ids.device:
+        raise ValueError(f"{other[0]} must be on the device of the ids")
+
+
+def decode_reserve(tok: Tokenizer, max_ids: int) -> None:
+    """spl_decode_reserve_device: the decode tables on the device and scratch for max_ids ids (rows: batch * steps); decode_device /
+    decode_rows_device calls within that size then neither allocate nor synchronise."""
+    rc = _ffi.lib().spl_decode_reserve_device(tok.handle, int(max_ids))
+    if rc != 0:
+        raise (ValueError if rc == -1 else RuntimeError)(f"spl_decode_reserve_device failed ({rc}): {_ffi.last_error()}")
+
+
+def _decode_call(tok: Tokenizer, ids: torch.Tensor, n_ids_cap: int, offsets, lengths, n_docs: int, o, max_bytes: int):
+    dev = ids.device
+    out = torch.empty(_max_bytes(max_bytes), dtype=torch.uint8, device=dev)
+    out_off = torch.empty(n_docs + 1, dtype=torch.int64, device=dev)           # (every offset is written by the kernel)
+    rc = _ffi.lib().spl_decode_batch_device(tok.handle, ids.data_ptr() if ids.numel() else None, n_ids_cap,
+                                            offsets.data_ptr() if offsets is not None else None,
+                                            lengths.data_ptr() if lengths is not None else None, n_docs, ctypes.byref(o),
+                                            out.data_ptr() if out.numel() else None, out.numel(), out_off.data_ptr(),
+                                            torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise _decode_error(rc)
+    return out, out_off
+
+
+def decode_device(tok: Tokenizer, ids: torch.Tensor, offsets: torch.Tensor, *, max_bytes: int,
+                  skip_special_tokens: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A CSR of ids in HBM (ids int32 / int64 [capacity], offsets int64 [n_docs + 1], offsets[0] == 0 -- what encode_device leaves) to a
+    bytes CSR in HBM, on torch's current stream (spl_decode_batch_device); nothing synchronises.  ids.numel() is only an upper bound of
+    the id count.  Returns (bytes uint8 [max_bytes rounded up to 16], out_off int64 [n_docs + 1]); out_off[-1] is the byte count NEEDED:
+    bytes beyond the buffer are dropped, compare the two."""
+    check_decode_args(ids, offsets, rows=False, max_bytes=max_bytes)
+    flags = (_ffi.SPL_DECODE_I64 if ids.dtype == torch.int64 else 0) | (_ffi.SPL_DECODE_SKIP_SPECIAL if skip_special_tokens else 0)
+    return _decode_call(tok, ids, ids.numel(), offsets, None, offsets.shape[0] - 1, _ffi.SplDecodeOpts(flags, 0), max_bytes)
+
+
+def decode_rows_device(tok: Tokenizer, rows: torch.Tensor, lengths: Optional[torch.Tensor] = None, *, max_bytes: int,
+                       padding_side: str = "right", skip_special_tokens: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Rows [batch, steps] int32 / int64 in HBM (what a sampler leaves, or pad_device) to a bytes CSR in HBM, one document per row.  With
+    lengths (int32 [batch], as pad_device returns them) a row's valid entries are its first lengths[r] -- padding_side "left": its last --
+    and the others contribute nothing; an int64 value outside 0 .. 2**32 - 1 (-1, -100) is no id and contributes nothing.  Same return
+    as decode_device; nothing synchronises."""
+    check_decode_args(rows, None, lengths, rows=True, max_bytes=max_bytes, padding_side=padding_side)
+    flags = (_ffi.SPL_DECODE_I64 if rows.dtype == torch.int64 else 0) | (_ffi.SPL_DECODE_SKIP_SPECIAL if skip_special_tokens else 0) | \
+        (_ffi.SPL_DECODE_PAD_LEFT if padding_side == "left" else 0)
+    n_docs, row_len = int(rows.shape[0]), int(rows.shape[1])
+    if row_len == 0:                                  # (no entry anywhere: every document is empty; row_len 0 would mean CSR mode)
+        out = torch.empty(_max_bytes(max_bytes), dtype=torch.uint8, device=rows.device)
+        return out, torch.zeros(n_docs + 1, dtype=torch.int64, device=rows.device)
+    return _decode_call(tok, rows, 0, None, lengths, n_docs, _ffi.SplDecodeOpts(flags, row_len), max_bytes)
 
 
 class Comm:

@@ -358,6 +358,29 @@ class Tokenizer:
     def decode_batch_lossy(self, token_lists: Sequence[Sequence[int]]) -> List[str]:
         return [b.decode("utf-8", "replace") for b in self._decode_batch_bytes(token_lists)]
 
+    def decode_tensor(self, input_ids, lengths=None, *, padding_side: str = "right", skip_special_tokens: bool = False,
+                      errors: str = "strict") -> List[str]:
+        """Extension: rows [batch, steps] of ids ON THE GPU (int32 / int64; lengths int32 [batch] or None, as encode_batch_padded
+        returns them) to one str per row.  The decode runs on the device (splintr_amd.device.decode_rows_device) into a buffer of 6
+        bytes per id; the byte count it needed is read back, and only if the guess was short the decode runs once more with the exact
+        size; then ONE copy of the bytes and one of the offsets to the host.  errors: "strict" (ValueError on invalid UTF-8, as decode)
+        or "replace"."""
+        from . import device as dv
+        if errors not in ("strict", "replace"):
+            raise ValueError(f"errors must be 'strict' or 'replace', not {errors!r}")
+        dv.check_decode_args(input_ids, None, lengths, rows=True, padding_side=padding_side)      # (before anything goes to the device)
+        kw = dict(padding_side=padding_side, skip_special_tokens=skip_special_tokens)
+        out, off = dv.decode_rows_device(self, input_ids, lengths, max_bytes=6 * input_ids.numel(), **kw)
+        need = int(off[-1].item())
+        if need > out.numel():
+            out, off = dv.decode_rows_device(self, input_ids, lengths, max_bytes=need, **kw)
+        raw = out[:need].cpu().numpy().tobytes()
+        o = off.cpu().tolist()
+        try:
+            return [raw[o[i]:o[i + 1]].decode("utf-8", errors) for i in range(len(o) - 1)]
+        except UnicodeDecodeError:
+            raise ValueError("Decoding error: invalid UTF-8") from None
+
     # ------------------------------------------------------------------ streaming decoders (host side)
     def _token_bytes(self, token_id: int, byte_level_decoded: bool) -> Optional[bytes]:
         """What the reference's decoder / special_tokens_decoder maps give for one id.
