@@ -488,6 +488,15 @@ int spl_debug_phases(spl_tokenizer* t, int enable, unsigned long long stamps_out
 #define SPL_DEBUG_BLOCKS 4096
 int spl_debug_blocks(spl_tokenizer* t, unsigned long long* out, int max_blocks);
 
+/* Development aid: the device side of spl_allgatherv_csr's last step WITHOUT a communicator (RCCL does not put two ranks on one GPU, so
+ * the tests could not reach it at world > 1).  d_all_off (device memory) holds every rank's LOCAL offsets side by side, rank r's N_r of
+ * them from index N_0 + .. + N_{r-1}; counts (HOST memory) is [world][2] = {T_r, N_r}.  Afterwards d_all_off[0 .. N_total] are the
+ * offsets into the global id array, the closing entry T_total included; nothing else is written.  Runs the same code as
+ * spl_allgatherv_csr, asynchronously on `hip_stream`; the handle only names the device.  SPL_EINVAL for world == 0 or world > 64 (the
+ * largest communicator spl_comm_create accepts) -- checked first, before anything touches a device -- and for a null argument. */
+int spl_debug_rebase_offsets(spl_tokenizer* t, uint64_t* d_all_off, const uint64_t* counts /* [world][2]: T, N */,
+                             uint32_t world, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

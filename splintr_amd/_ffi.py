@@ -23,7 +23,7 @@ SYMBOLS = [
     "spl_reserve", "spl_encode_batch", "spl_result_tokens", "spl_result_offsets", "spl_result_n_tokens",
     "spl_result_n_docs", "spl_result_free", "spl_encode_batch_device", "spl_decode_batch", "spl_free",
     "spl_profile_enable", "spl_profile_reset", "spl_profile_read", "spl_kernel_name", "spl_last_queue_counts",
-    "spl_debug_phases", "spl_debug_blocks", "spl_gatherv_pack", "spl_gatherv_unpack", "spl_gatherv_unpack_group", "spl_encode_batch_device_packed",
+    "spl_debug_phases", "spl_debug_blocks", "spl_debug_rebase_offsets", "spl_gatherv_pack", "spl_gatherv_unpack", "spl_gatherv_unpack_group", "spl_encode_batch_device_packed",
     "spl_set_devices", "spl_n_devices", "spl_set_option", "spl_host_alloc", "spl_host_free",
     "spl_token_bytes", "spl_is_byte_level",
     "spl_comm_unique_id", "spl_comm_create", "spl_comm_destroy", "spl_comm_rank", "spl_comm_world",
@@ -129,6 +129,7 @@ def lib() -> ctypes.CDLL:
     L.spl_last_queue_counts.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32)]
     L.spl_debug_phases.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
     L.spl_debug_blocks.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
+    L.spl_debug_rebase_offsets.argtypes = [vp, vp, u64p, ctypes.c_uint32, vp]
     L.spl_gatherv_pack.argtypes = [vp, vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_uint64, vp]
     L.spl_gatherv_unpack.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, vp, ctypes.c_uint64, vp,
                                      vp, vp]

@@ -440,6 +440,15 @@ int spl_debug_phases(spl_tokenizer* t, int enable, unsigned long long stamps_out
     return SPL_OK;
 }
 
+int spl_debug_rebase_offsets(spl_tokenizer* t, uint64_t* d_all_off, const uint64_t* counts, uint32_t world, void* hip_stream) {
+    if (world == 0 || world > (uint32_t)COMM_MAX_WORLD) return fail(SPL_EINVAL, "spl_debug_rebase_offsets: world must be 1 .. 64");
+    if (!t || !d_all_off || !counts) return fail(SPL_EINVAL, "spl_debug_rebase_offsets: null argument");
+    return guarded("spl_debug_rebase_offsets", [&] {
+        HIP_TRY(hipSetDevice(t->ctx[0]->device));
+        return rebase_offsets(d_all_off, counts, 2, world, (hipStream_t)hip_stream);
+    });
+}
+
 #ifdef SPL_MERGE_TIMING
 int spl_debug_merge_timing(unsigned long long out[8], int reset) {
     if (reset) { unsigned long long z[8] = {0}; hipMemcpyToSymbol(HIP_SYMBOL(spl::g_mt), z, sizeof z); return 0; }

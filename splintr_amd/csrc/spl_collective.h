@@ -27,6 +27,26 @@ int comm_create(const uint8_t* id, int rank, int world, int device, spl_comm** o
     return SPL_OK;
 }
 
+// The device side of the exact form: every rank's {T, N} (host memory, `stride` u64 words per rank, T and N first) -> the prefix table, and
+// the launch that turns the received LOCAL offsets into offsets of the global id array (+ the closing entry).  allgatherv_csr and the test
+// seam spl_debug_rebase_offsets both come through here, each with 1 <= W <= COMM_MAX_WORLD (spl_comm_create / the seam refuse anything else).
+RankTable rank_table(const uint64_t* counts, size_t stride, uint32_t W) {
+    RankTable tab{};
+    for (uint32_t p = 0; p < W; p++) {
+        tab.t_pre[p + 1] = tab.t_pre[p] + counts[stride * p];
+        tab.n_pre[p + 1] = tab.n_pre[p] + counts[stride * p + 1];
+    }
+    return tab;
+}
+int rebase_offsets(uint64_t* d_all_off, const uint64_t* counts, size_t stride, uint32_t W, hipStream_t s) {
+    const RankTable tab = rank_table(counts, stride, W);
+    uint64_t nmax = 1;
+    for (uint32_t p = 0; p < W; p++) nmax = std::max<uint64_t>(nmax, counts[stride * p + 1]);
+    hipLaunchKernelGGL(k_rebase_offsets, dim3((uint32_t)std::min<uint64_t>((nmax + 255) / 256, 1024), W), dim3(256), 0, s, d_all_off, tab, W);
+    HIP_TRY(hipGetLastError());
+    return SPL_OK;
+}
+
 int allgatherv_csr(spl_comm* c, const uint32_t* d_ids, const uint64_t* d_out_off, uint64_t n_docs, uint32_t* d_all_ids,
                    uint64_t all_ids_cap, uint64_t* d_all_off, uint64_t all_off_cap, uint64_t* n_tokens_total, uint64_t* n_docs_total,
                    hipStream_t s) {
@@ -39,11 +59,9 @@ int allgatherv_csr(spl_comm* c, const uint32_t* d_ids, const uint64_t* d_out_off
     NCCL_TRY(R.AllGather(c->d_cnt.get(), c->d_cnts.get(), 4, ncclUint64, c->comm, s));
     HIP_TRY(hipMemcpyAsync(c->h_cnts.host(), c->d_cnts.get(), 32 * (size_t)W, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    RankTable tab{};
+    const RankTable tab = rank_table(c->h_cnts.host(), 4, (uint32_t)W);
     uint64_t min_ids_cap = ~0ull, min_off_cap = ~0ull;
     for (int p = 0; p < W; p++) {
-        tab.t_pre[p + 1] = tab.t_pre[p] + c->h_cnts.host()[4 * p];
-        tab.n_pre[p + 1] = tab.n_pre[p] + c->h_cnts.host()[4 * p + 1];
         min_ids_cap = std::min(min_ids_cap, c->h_cnts.host()[4 * p + 2]);
         min_off_cap = std::min(min_off_cap, c->h_cnts.host()[4 * p + 3]);
     }
@@ -68,10 +86,6 @@ int allgatherv_csr(spl_comm* c, const uint32_t* d_ids, const uint64_t* d_out_off
     }
     NCCL_TRY(R.GroupEnd());
     // (3) local offsets -> offsets in the global id array, and the closing entry
-    const uint64_t nmax = [&] { uint64_t m = 1; for (int p = 0; p < W; p++) m = std::max<uint64_t>(m, c->h_cnts.host()[4 * p + 1]); return m; }();
-    hipLaunchKernelGGL(k_rebase_offsets, dim3((uint32_t)std::min<uint64_t>((nmax + 255) / 256, 1024), (uint32_t)W), dim3(256), 0, s,
-                       d_all_off, tab, (uint32_t)W);
-    HIP_TRY(hipGetLastError());
-    return SPL_OK;
+    return rebase_offsets(d_all_off, c->h_cnts.host(), 4, (uint32_t)W, s);
 }
 }  // namespace

@@ -95,7 +95,9 @@ TileMode pick_mode(int force_tile, bool ext, bool special, uint64_t n_bytes) {
     static_assert(TileGeom<SPL_TILE_DIRECT_A>::Wv == TileGeom<SPL_TILE_SMALL>::Wv && TileGeom<SPL_TILE_DIRECT_B>::Wv == TileGeom<SPL_TILE_SMALL>::Wv &&
                   TileGeom<SPL_TILE_DIRECT_A>::TBv >= TileGeom<SPL_TILE_SMALL>::TBv && TileGeom<SPL_TILE_DIRECT_B>::TBv >= TileGeom<SPL_TILE_SMALL>::TBv,
                   "the workspace is sized for SPL_TILE_SMALL's window and tile count");
-    if (!ext && !special && (force_tile == 4 || (force_tile == 0 && n_bytes > SPL_DIRECT_MAX_BYTES)) && n_bytes <= SPL_QUEUE_MAX_BYTES) return TileMode::Queue;
+    // (a call without a byte launches no tile at all: forced queue mode would ask for grids of ZERO workgroups -- an invalid launch -- so
+    //  it takes the tile-owned branch, which only zeroes the offsets and, for a packed call, queues the pack kernel)
+    if (!ext && !special && n_bytes && (force_tile == 4 || (force_tile == 0 && n_bytes > SPL_DIRECT_MAX_BYTES)) && n_bytes <= SPL_QUEUE_MAX_BYTES) return TileMode::Queue;
     const bool known = force_tile == 0 || force_tile == 1 || force_tile == 4 || force_tile == 5;
     if (n_bytes > SPL_DIRECT_MAX_BYTES || !(ext || known)) return TileMode::Refuse;
     return (force_tile == 5 || n_bytes > SPL_DIRECT_A_MAX_BYTES) ? TileMode::OwnedB : TileMode::OwnedA;

@@ -614,6 +614,15 @@ class WaveGather:
         self._timing = []
         return float(total), n
 
+    def _allgather(self, k) -> None:
+        """wave k's `world` slabs, send[k] -> recv[k], on the exchange stream (current here).  (overridable: the GPU tests stand in for
+        the other ranks of a world > 1 on one GPU)"""
+        L = _ffi.lib()
+        fn = L.spl_allgather_slabs_p2p if self.collective == "p2p" else L.spl_allgather_slabs
+        rc = fn(self.comm.handle, self.send[k].data_ptr(), self.recv[k].data_ptr(), self.cap_words, self.exch.cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f"spl_allgather_slabs failed ({rc}): {_ffi.last_error()}")
+
     def begin(self) -> None:
         """Start a new batch: the running totals back to zero (on the exchange stream, behind the previous batch's last unpack;
         the main stream waits for it only through finish())."""
@@ -643,10 +652,7 @@ class WaveGather:
             if self._timing is not None:
                 ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
                 ev[0].record(self.exch)
-            fn = L.spl_allgather_slabs_p2p if self.collective == "p2p" else L.spl_allgather_slabs
-            rc = fn(self.comm.handle, self.send[k].data_ptr(), self.recv[k].data_ptr(), self.cap_words, self.exch.cuda_stream)
-            if rc != 0:
-                raise RuntimeError(f"spl_allgather_slabs failed ({rc}): {_ffi.last_error()}")
+            self._allgather(k)
             rc = L.spl_gatherv_unpack_at(self.tok.handle, self.recv[k].data_ptr(), self.world, self.cap_words, self.max_docs,
                                          self.all_ids.data_ptr(), self.all_ids.numel(), self.all_off.data_ptr(), self.all_off.numel(),
                                          self.run.data_ptr(), self.status.data_ptr(), self.exch.cuda_stream)

@@ -49,6 +49,12 @@ def test_errors_without_gpu_or_bad_input(built):
     assert b"struct_size" not in L.spl_last_error()
     assert L.spl_kernel_name(0) and L.spl_kernel_name(99) is None
     assert L.spl_vocab_size(None) == 0
+    # spl_debug_rebase_offsets refuses a world the RankTable cannot hold before it looks at anything else (no device here)
+    counts = (ctypes.c_uint64 * 2)(0, 0)
+    for world in (0, 65, 1 << 31):
+        assert L.spl_debug_rebase_offsets(None, None, counts, world, None) == -1
+        assert b"spl_debug_rebase_offsets: world" in L.spl_last_error()
+    assert L.spl_debug_rebase_offsets(None, None, counts, 64, None) == -1 and b"null argument" in L.spl_last_error()
 
 
 def test_product_has_no_cpu_fallback_and_never_touches_the_oracle():
