@@ -138,6 +138,8 @@ uint32_t spl_n_devices(const spl_tokenizer* t);
  *   "sdma_d2h"               0/1 (0): the ids of a pipeline chunk leave through hsa_amd_memory_async_copy (an SDMA engine) instead of
  *                            hipMemcpyAsync; hipMemcpyAsync where the HSA runtime cannot be bound
  *   "decode_chunk_ids"       >= 1024 (2^21): spl_decode_batch pipelines batches of at least three such chunks through two slots
+ *   "window_totals_chunk"    1..256 (256; for tests): the span totals spl_window_device's second scan launch takes per round, so that a batch
+ *                            of a few thousand documents reaches its second round
  *   "slab_pack24"            0/1 (0): the ids of the all-gather slabs travel three bytes each; every rank alike; refused (SPL_EINVAL) when an
  *                            id of the tokenizer -- vocabulary or special token -- does not fit 24 bits
  * Unknown names and values out of range: SPL_EINVAL. */
@@ -320,6 +322,43 @@ int spl_pad_device(spl_tokenizer* t, const uint32_t* d_ids, const uint64_t* d_ou
 int spl_pack_device(spl_tokenizer* t, const uint32_t* d_ids, const uint64_t* d_out_off, uint64_t n_docs,
                     const spl_collate_opts* o, void* d_rows /* [rows_cap*row_len] */, uint64_t rows_cap,
                     int32_t* d_doc /* NULL ok */, int32_t* d_pos /* NULL ok */, uint64_t* d_n /* [2] */, void* hip_stream);
+
+/* SLIDING WINDOWS over the CSR: every document alone and complete, as rows of row_len that overlap by `overlap` ids -- the one
+ * per-document layout that loses nothing (pad mode truncates, pack mode joins documents), and what Hugging Face tokenizers call
+ * return_overflowing_tokens with stride = overlap.  The reference has no counterpart, as for pad and pack; the same conventions hold:
+ * fully asynchronous on `hip_stream`, nothing allocated, nothing synchronised, the handle used only for its device, ANY CSR with
+ * d_out_off[0] == 0, ids as bit patterns (SPL_COLLATE_I64 zero-extends).  spl_collate_opts is the struct of pad and pack, unchanged;
+ * accepted flags: SPL_COLLATE_I64, _PAD_LEFT, _BOS, _EOS.
+ *
+ * k = BOS + EOS, B = row_len - k (the body budget, at least 1), overlap in 0 .. B - 1, step = B - overlap.  For document d of len_d ids:
+ *   rows       n_w(d) = 1 if len_d <= B, else 1 + ceil((len_d - B) / step).  Every document has at least one row: an empty one's
+ *              holds its k specials and padding, as in pad mode.
+ *   window w   holds ids [w * step, min(w * step + B, len_d)) of the document, as [bos_id] + body + [eos_id], the rest pad_id -- on the
+ *              right, or on the left with SPL_COLLATE_PAD_LEFT.  BOS and EOS are on every row; only a document's last window can be short.
+ *   row index  d_row_off[d] = the sum of n_w(i) over i < d (exclusive; strictly increasing), d_row_off[n_docs] = the number of rows.
+ *              Row r belongs to the largest d with d_row_off[d] <= r, and is its window w = r - d_row_off[d].
+ * Outputs: d_rows[r, c] and d_mask[r, c] (1 where the entry is not padding) as in pad mode; d_len[r] = the entries of row r that are not
+ * padding; d_row_doc[r] = d; d_row_start[r] = w * step, the body's first id within its document; d_row_off[n_docs + 1], the CSR of rows
+ * per document (what a caller reduces over, to mean-pool a document's windows for example); d_n[0] = d_row_off[n_docs], the NEED --
+ * compare it with rows_cap, as d_out_off[n_docs] with ids_capacity -- and d_n[1] = min(d_n[0], rows_cap), the rows that hold documents.
+ * d_row_off and d_n are always written in full, also when rows_cap is too small or 0.  Every element of every per-row and per-element
+ * array below rows_cap is written -- rows from d_n[0] on: pad_id, mask 0, len 0, doc -1, start 0 -- and nothing at or beyond rows_cap.
+ * n_docs == 0: d_row_off[0] = 0, d_n = {0, 0}, every row padding.
+ * d_work: spl_window_work_bytes(n_docs) bytes of device memory, a pure function of n_docs (0 for up to 4096 documents, where one launch
+ * computes d_row_off; beyond that three launches do, through the workspace, and no workgroup of them ever waits for another one).
+ *
+ * SPL_EINVAL, with the cause in spl_last_error() and before anything touches the handle or the device: everything spl_pad_device
+ * refuses; row_len <= k; overlap >= row_len - k; SPL_COLLATE_KEEP_TAIL (nothing is truncated); a null d_row_off or d_n; a null d_work
+ * when spl_window_work_bytes(n_docs) > 0; d_rows, d_len, d_row_doc, d_row_start or d_row_off not 16-byte aligned, d_mask not 4-byte
+ * aligned, d_work not 8-byte aligned; rows_cap * row_len beyond 2^63. */
+uint64_t spl_window_work_bytes(uint64_t n_docs);
+int spl_window_device(spl_tokenizer* t, const uint32_t* d_ids, const uint64_t* d_out_off, uint64_t n_docs,
+                      const spl_collate_opts* o, uint32_t overlap,
+                      void* d_rows /* [rows_cap*row_len] */, uint64_t rows_cap,
+                      uint8_t* d_mask /* [rows_cap*row_len], NULL ok */, int32_t* d_len /* [rows_cap], NULL ok */,
+                      int32_t* d_row_doc /* [rows_cap], NULL ok */, int64_t* d_row_start /* [rows_cap], NULL ok */,
+                      uint64_t* d_row_off /* [n_docs+1], required */, uint64_t* d_n /* [2], required */,
+                      void* d_work /* spl_window_work_bytes(n_docs) bytes; NULL ok when that is 0 */, void* hip_stream);
 
 /* ONE batch exchanged in WAVES (strong scaling, pipelined: the ids of wave k travel while wave k + 1 encodes).  The batch's documents, in
  * their order, are cut into waves and every wave into one contiguous slice per rank; rank r encodes its slice of wave k into a slab

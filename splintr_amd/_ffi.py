@@ -29,7 +29,7 @@ SYMBOLS = [
     "spl_comm_unique_id", "spl_comm_create", "spl_comm_destroy", "spl_comm_rank", "spl_comm_world",
     "spl_allgather_slabs", "spl_allgather_slabs_p2p", "spl_gatherv_unpack_at", "spl_allgatherv_csr", "spl_split_host", "spl_encode_chunks_device",
     "spl_split_device", "spl_device_split_fallbacks", "spl_small_path_calls", "spl_pick_stream", "spl_memo_stats",
-    "spl_pad_device", "spl_pack_device",
+    "spl_pad_device", "spl_pack_device", "spl_window_work_bytes", "spl_window_device",
     "spl_decode_reserve_device", "spl_decode_batch_device", "spl_max_token_bytes",
 ]
 SPL_PATTERN_CUSTOM = 3
@@ -161,6 +161,10 @@ def lib() -> ctypes.CDLL:
                                      u64p, u64p, vp]
     L.spl_pad_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.POINTER(SplCollateOpts), vp, vp, vp, vp]
     L.spl_pack_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.POINTER(SplCollateOpts), vp, ctypes.c_uint64, vp, vp, vp, vp]
+    L.spl_window_work_bytes.restype = ctypes.c_uint64
+    L.spl_window_work_bytes.argtypes = [ctypes.c_uint64]
+    L.spl_window_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.POINTER(SplCollateOpts), ctypes.c_uint32, vp, ctypes.c_uint64,
+                                    vp, vp, vp, vp, vp, vp, vp, vp]
     L.spl_decode_reserve_device.argtypes = [vp, ctypes.c_uint64]
     L.spl_decode_batch_device.argtypes = [vp, vp, ctypes.c_uint64, vp, vp, ctypes.c_uint64, ctypes.POINTER(SplDecodeOpts), vp,
                                           ctypes.c_uint64, vp, vp]

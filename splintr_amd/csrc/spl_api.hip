@@ -1,7 +1,7 @@
 // spl_api.hip -- the C ABI (include/splintr_hip.h): the root of the library's one HIP translation unit.  It includes the kernels
 // (spl_kernels.hip) and the host side, one file per concern and each building on the ones before it -- spl_host_res.h (resource owners,
 // pinned pool), spl_ctx.h (per-GPU context, handle, uploads), spl_streams.h (stream probe), spl_launch.h (memo, launch order, device
-// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_decode_dev_host.h -- and holds the entry points.
+// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_window_host.h, spl_decode_dev_host.h -- and holds the entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -40,6 +40,7 @@ using namespace spl;
 #include "spl_decode_host.h"
 #include "spl_collective.h"
 #include "spl_collate_host.h"
+#include "spl_window_host.h"
 #include "spl_decode_dev_host.h"
 
 namespace {
@@ -146,6 +147,7 @@ int spl_set_option(spl_tokenizer* t, const char* name, int64_t value) {
     else if (k == "copy_threads" && value >= 1 && value <= 64) t->copy_threads = (int)value;
     else if (k == "decode_chunk_ids" && value >= 1024) t->dec_chunk_ids = (uint64_t)value;
     else if (k == "sdma_d2h") t->sdma_d2h = value != 0;        // (where the HSA runtime or the device's agent cannot be found: hipMemcpyAsync, silently)
+    else if (k == "window_totals_chunk" && value >= 1 && value <= (int64_t)WIN_CHUNK) t->win_chunk = (uint32_t)value;
     else if (k == "slab_pack24") {
         if (value && std::max(t->ht.max_id, t->max_special_id) >= (1u << 24))
             return fail(SPL_EINVAL, "slab_pack24: an id of this tokenizer does not fit three bytes (vocabulary or special-token ids >= 2^24)");
@@ -411,6 +413,16 @@ int spl_pack_device(spl_tokenizer* t, const uint32_t* d_ids, const uint64_t* d_o
                     void* d_rows, uint64_t rows_cap, int32_t* d_doc, int32_t* d_pos, uint64_t* d_n, void* hip_stream) {
     return guarded("spl_pack_device", [&] {
         return pack_device(t, d_ids, d_out_off, n_docs, o, d_rows, rows_cap, d_doc, d_pos, d_n, (hipStream_t)hip_stream); });
+}
+
+uint64_t spl_window_work_bytes(uint64_t n_docs) { return window_work_bytes(n_docs); }
+
+int spl_window_device(spl_tokenizer* t, const uint32_t* d_ids, const uint64_t* d_out_off, uint64_t n_docs, const spl_collate_opts* o,
+                      uint32_t overlap, void* d_rows, uint64_t rows_cap, uint8_t* d_mask, int32_t* d_len, int32_t* d_row_doc,
+                      int64_t* d_row_start, uint64_t* d_row_off, uint64_t* d_n, void* d_work, void* hip_stream) {
+    return guarded("spl_window_device", [&] {
+        return window_device(t, d_ids, d_out_off, n_docs, o, overlap, d_rows, rows_cap, d_mask, d_len, d_row_doc, d_row_start, d_row_off, d_n,
+                             d_work, (hipStream_t)hip_stream); });
 }
 
 int spl_debug_blocks(spl_tokenizer* t, unsigned long long* out, int max_blocks) {

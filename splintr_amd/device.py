@@ -132,6 +132,57 @@ def pack_device(tok: Tokenizer, batch: DeviceBatch, seq_len: int, *, pad_id: int
     return rows, doc, pos, n
 
 
+def check_window_args(row_len: int, overlap: int, pad_id: int, bos_id: Optional[int], eos_id: Optional[int], dtype,
+                      padding_side: str = "right") -> None:
+    """check_collate_args for window_device: also ValueError for a row without room for a token beside BOS and EOS, and for an overlap
+    outside 0 .. row_len - (BOS + EOS) - 1."""
+    check_collate_args(row_len, pad_id, bos_id, eos_id, dtype, padding_side)
+    budget = int(row_len) - (bos_id is not None) - (eos_id is not None)
+    if budget < 1:
+        raise ValueError("the row length must leave room for at least one token beside BOS and EOS")
+    if isinstance(overlap, bool) or not isinstance(overlap, (int, np.integer)) or not 0 <= int(overlap) < budget:
+        raise ValueError(f"overlap must be an integer in 0 .. {budget - 1} (the row length minus BOS, EOS and one), not {overlap!r}")
+
+
+def window_device(tok: Tokenizer, batch: DeviceBatch, max_length: int, *, overlap: int = 0, pad_id: int, bos_id: Optional[int] = None,
+                  eos_id: Optional[int] = None, padding_side: str = "right", dtype: torch.dtype = torch.int32,
+                  max_rows: Optional[int] = None):
+    """batch's CSR as SLIDING WINDOWS on torch's current stream (spl_window_device): every document alone and complete, as rows of
+    max_length whose bodies (max_length - (BOS + EOS) ids) overlap by `overlap` ids -- Hugging Face's return_overflowing_tokens with
+    stride = overlap.  Nothing is truncated and no row holds two documents; only a document's last window can be short.  Returns (rows
+    [max_rows, L], mask uint8 [max_rows, L], lengths int32 [max_rows], row_doc int32 [max_rows], row_start int64 [max_rows], row_off int64
+    [n_docs + 1], n): row r is window r - row_off[row_doc[r]] of document row_doc[r] and starts at id row_start[r] of it; n is a DEVICE
+    tensor (int64[2]: the rows needed, the rows of these that fit max_rows), so nothing synchronises here; rows from n[0] on hold pad_id,
+    row_doc -1.  The default max_rows, n_docs + batch.n_bytes // step with step = max_length - (BOS + EOS) - overlap, always suffices: a
+    document of len ids needs one row, or beyond the body budget B 1 + ceil((len - B) / step) <= 1 + (len - 1) // step of them (because
+    B >= step), so all documents together at most n_docs + (all ids) // step, and a token has at least one byte; with a smaller one
+    compare n[0] with it."""
+    check_window_args(max_length, overlap, pad_id, bos_id, eos_id, dtype, padding_side)
+    o = _collate_opts(max_length, pad_id, bos_id, eos_id, dtype, _ffi.SPL_COLLATE_PAD_LEFT if _side("padding_side", padding_side) else 0)
+    step = o.row_len - (bos_id is not None) - (eos_id is not None) - int(overlap)
+    if max_rows is None:
+        max_rows = batch.n_docs + batch.n_bytes // step
+    max_rows = int(max_rows)
+    dev = batch.ids.device
+    L = _ffi.lib()
+    rows = torch.empty((max_rows, o.row_len), dtype=dtype, device=dev)           # (every element is written by the kernel)
+    mask = torch.empty((max_rows, o.row_len), dtype=torch.uint8, device=dev)
+    lens = torch.empty(max_rows, dtype=torch.int32, device=dev)
+    row_doc = torch.empty(max_rows, dtype=torch.int32, device=dev)
+    row_start = torch.empty(max_rows, dtype=torch.int64, device=dev)
+    row_off = torch.empty(batch.n_docs + 1, dtype=torch.int64, device=dev)
+    n = torch.empty(2, dtype=torch.int64, device=dev)
+    work = torch.empty(int(L.spl_window_work_bytes(batch.n_docs)), dtype=torch.uint8, device=dev)
+    rc = L.spl_window_device(tok.handle, batch.ids.data_ptr(), batch.out_off.data_ptr(), batch.n_docs, ctypes.byref(o), int(overlap),
+                             rows.data_ptr() if max_rows else None, max_rows, mask.data_ptr() if max_rows else None,
+                             lens.data_ptr() if max_rows else None, row_doc.data_ptr() if max_rows else None,
+                             row_start.data_ptr() if max_rows else None, row_off.data_ptr(), n.data_ptr(),
+                             work.data_ptr() if work.numel() else None, torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise (ValueError if rc == -1 else RuntimeError)(f"spl_window_device failed ({rc}): {_ffi.last_error()}")
+    return rows, mask, lens, row_doc, row_start, row_off, n
+
+
 # ---------------------------------------------------------------------------------------------- device-resident decode
 def _decode_error(rc: int) -> Exception:
     return (ValueError if rc == -1 else RuntimeError)(f"spl_decode_batch_device failed ({rc}): {_ffi.last_error()}")

@@ -314,6 +314,23 @@ class Tokenizer:
         n_rows = int(n[0].item())
         return rows[:n_rows], doc[:n_rows], pos[:n_rows]
 
+    def encode_batch_windows(self, texts: Sequence[str], max_length: int, *, overlap: int = 0, pad_id: int, with_special: bool = False,
+                             bos_id: Optional[int] = None, eos_id: Optional[int] = None, padding_side: str = "right", dtype=None):
+        """Extension: encode_batch as SLIDING WINDOWS ON THE GPU -- every document alone and complete, as rows of max_length whose
+        bodies overlap by `overlap` ids (Hugging Face's name for `overlap` is `stride`, with return_overflowing_tokens): (input_ids
+        [n_rows, max_length], attention_mask uint8, lengths int32 [n_rows], doc_ids int32 [n_rows], starts int64 [n_rows], row_offsets
+        int64 [n_docs + 1]).  Row r is a window of document doc_ids[r] that begins at id starts[r] of it; the rows of document d are
+        row_offsets[d] .. row_offsets[d + 1] - 1.  BOS and EOS are on every row.  ONE synchronisation, to learn n_rows."""
+        import torch
+        from . import device as dv
+        dtype = torch.int32 if dtype is None else dtype
+        dv.check_window_args(max_length, overlap, pad_id, bos_id, eos_id, dtype, padding_side)   # (before anything goes to the device)
+        dv, batch = self._encode_on_device(texts, with_special)
+        rows, mask, lens, doc, start, row_off, n = dv.window_device(self, batch, max_length, overlap=overlap, pad_id=pad_id, bos_id=bos_id,
+                                                                    eos_id=eos_id, padding_side=padding_side, dtype=dtype)
+        n_rows = int(n[0].item())
+        return rows[:n_rows], mask[:n_rows], lens[:n_rows], doc[:n_rows], start[:n_rows], row_off
+
     # ------------------------------------------------------------------ decode (test helper / "next" row)
     def decode_bytes(self, tokens: Sequence[int]) -> bytes:
         """src/python/bindings.rs:313-315."""
