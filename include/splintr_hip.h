@@ -122,6 +122,9 @@ uint32_t spl_n_devices(const spl_tokenizer* t);
  *   "memo"                   0/1 (1): the chunk memo (spl_memo_stats); "memo_bits" 4..22 (20): log2 of its entries for chunks of up to 32 bytes
  *                            (128 bytes each); "memo_long_bits" 0..20 (16; 0: none): ... for chunks of 33..64 bytes (164 bytes each);
  *                            "memo_log_cap" 1..65536 (1024): missed chunks the tiles log per region (of 64) between two fills
+ *   "memo_first"             0/1 (1): a new memo is SEEDED with the vocabulary's keys of 2..64 bytes (spl_memo_seed_stats) and the tile kernel asks
+ *                            it before the vocabulary's tables -- one memory trip for a vocabulary token and a learned chunk alike; 0: the memo
+ *                            holds learned chunks only and is asked behind the tables.  Same results.  Changing it empties the memo ("memo_clear").
  *   "memo_clear"             (any value) empties the memo of every context: Tokenizer::clear_cache (src/core/tokenizer.rs:995-1000)
  *   "group_scan_min"         0..2^24 (256; 0: never): a batch of more than this many groups of 64 tiles gets the groups' prefix sums from one small launch
  *                            (k_group_scan) between k_pretok and k_tile_out instead of every tile adding up the sums of the groups in front of it
@@ -508,6 +511,14 @@ const char* spl_kernel_name(int index);   /* NULL past the last kernel */
  * launches), out[1] chunks put in, out[2] chunks found to be beyond an entry (more than fourteen tokens: remembered as such), out[3] entries of
  * the table (0: off).  spl_set_option("memo", 0) turns it off; "memo_bits" (4..22, default 16) sizes it.  Synchronises the device. */
 int spl_memo_stats(spl_tokenizer* t, uint64_t out[4]);
+/* The memo's seed (option "memo_first"), first device: out[0] = vocabulary keys of 2..64 bytes put into the memo when it was created, out[1] = keys
+ * that found neither of their two slots free (the vocabulary's own tables answer those).  Both 0 with "memo_first" or "memo" off.  Seeds are no
+ * learned chunks: spl_memo_stats does not count them.  Where the memo does not exist yet (a fresh handle, behind "memo_clear") the figures are
+ * those of the host's plan for the next launch's memo: a query, no device state is made. */
+int spl_memo_seed_stats(spl_tokenizer* t, uint64_t out[2]);
+/* Debug / tests: slot `slot` of the first device's memo as it lies in HBM: the entry's sixteen words (key[8], meta0, meta1, ids[6]), then
+ * bytes 32..63 of the key for the table of 33..64-byte chunks (long_table != 0; zeros otherwise).  Synchronises the device. */
+int spl_debug_memo_entry(spl_tokenizer* t, int long_table, uint32_t slot, uint32_t out[24]);
 
 /* Counters of the last encode call on this handle (device -> host copy, synchronises):
  * [2] items of the global long-chunk queue (> 64 B, plus every miss of a deferred segment),

@@ -28,7 +28,7 @@ SYMBOLS = [
     "spl_token_bytes", "spl_is_byte_level",
     "spl_comm_unique_id", "spl_comm_create", "spl_comm_destroy", "spl_comm_rank", "spl_comm_world",
     "spl_allgather_slabs", "spl_allgather_slabs_p2p", "spl_gatherv_unpack_at", "spl_allgatherv_csr", "spl_split_host", "spl_encode_chunks_device",
-    "spl_split_device", "spl_device_split_fallbacks", "spl_small_path_calls", "spl_pick_stream", "spl_memo_stats",
+    "spl_split_device", "spl_device_split_fallbacks", "spl_small_path_calls", "spl_pick_stream", "spl_memo_stats", "spl_memo_seed_stats", "spl_debug_memo_entry",
     "spl_pad_device", "spl_pack_device", "spl_window_work_bytes", "spl_window_device",
     "spl_decode_reserve_device", "spl_decode_batch_device", "spl_max_token_bytes",
 ]

@@ -139,6 +139,7 @@ int spl_set_option(spl_tokenizer* t, const char* name, int64_t value) {
     else if (k == "range_tiles" && value >= 0 && value < (1 << 24)) t->range_tiles = (uint32_t)value;
     else if (k == "range_streams" && (value == 1 || value == 2)) t->range_streams = (int)value;
     else if (k == "memo") t->memo = value != 0;
+    else if (k == "memo_first") { if ((value != 0) != (t->memo_first != 0)) memo_drop_all(); t->memo_first = value != 0; }     // (the seed is part of the form: the next launch builds the memo anew)
     else if (k == "memo_clear") memo_drop_all();               // Tokenizer::clear_cache (tokenizer.rs:995-1000)
     else if (k == "memo_bits" && value >= 4 && value <= 22) { t->memo_bits = (uint32_t)value; memo_drop_all(); }
     else if (k == "memo_long_bits" && value >= 0 && value <= 20) { t->memo_long_bits = (uint32_t)value; memo_drop_all(); }
@@ -480,6 +481,38 @@ int spl_memo_stats(spl_tokenizer* t, uint64_t out[4]) {
         unsigned long long st[2] = {0, 0};
         HIP_TRY(hipMemcpy(st, c->d_mstats.get(), 16, hipMemcpyDeviceToHost));
         out[1] = st[0]; out[2] = st[1];
+    }
+    return SPL_OK;
+}
+
+int spl_memo_seed_stats(spl_tokenizer* t, uint64_t out[2]) {
+    if (!t || !out) return fail(SPL_EINVAL, "null argument");
+    Ctx* c = t->ctx[0].get();
+    out[0] = out[1] = 0;
+    if (c->d_memo.get()) { out[0] = c->memo_seed_placed; out[1] = c->memo_seed_left; }
+    else if (t->memo && t->memo_first) {                        // (no memo yet: what the next launch will seed -- the host's plan, no device state)
+        std::lock_guard<std::mutex> lock(t->seed_mu);
+        const spl::MemoSeedPlan& plan = memo_seed_planned(t, t->memo_bits, t->memo_long_bits);
+        out[0] = plan.placed; out[1] = plan.left_out;
+    }
+    return SPL_OK;
+}
+
+// Debug / tests: one slot of the first device's memo as it lies in HBM -- the entry's sixteen words (MemoEnt), then bytes 32..63 of the key for the
+// table of 33..64-byte chunks (zeros for the other).  SPL_EINVAL where there is no such table or slot.  Synchronises the device.
+int spl_debug_memo_entry(spl_tokenizer* t, int long_table, uint32_t slot, uint32_t out[24]) {
+    if (!t || !out) return fail(SPL_EINVAL, "null argument");
+    Ctx* c = t->ctx[0].get();
+    const bool lng = long_table != 0;
+    if (!c->d_memo.get() || (lng && !c->d_memo2.get()) || slot > (lng ? c->memo2_mask : c->memo_mask)) return fail(SPL_EINVAL, "spl_debug_memo_entry: no such table or slot");
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipDeviceSynchronize());
+    memset(out, 0, 24 * sizeof(uint32_t));
+    if (!lng) HIP_TRY(hipMemcpy(out, c->d_memo.get() + slot, sizeof(MemoEnt), hipMemcpyDeviceToHost));
+    else {
+        const Memo2Parts m = memo2_parts(c);
+        HIP_TRY(hipMemcpy(out, m.ent + slot, sizeof(MemoEnt), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out + 16, m.hi + slot, sizeof(MemoHi), hipMemcpyDeviceToHost));
     }
     return SPL_OK;
 }

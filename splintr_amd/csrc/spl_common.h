@@ -118,7 +118,7 @@ struct alignas(8) PfxEnt { uint32_t lm, id2; };
 // boundaries on one stream give the coherence an in-kernel insert lacked (round 3).  Keys are compared in full: result-transparent.
 struct alignas(64) MemoEnt {
     uint32_t key[8];     // the chunk's bytes, little endian, zero padded
-    uint32_t meta0;      // bits 0-5 length in bytes (2..32), bits 8-11 tokens (0: known, but not memoizable -- more than fourteen), bit 31 valid
+    uint32_t meta0;      // bits 0-5 length in bytes (2..32), bits 8-11 tokens (0: known, but not memoizable -- more than fourteen), bit 30 a vocabulary key of the seed, bit 31 valid
     uint32_t meta1;      // token t (t = 0..4) ends at byte (meta1 >> 6 t) & 63 of the chunk; the last token ends with the chunk
     uint32_t ids[6];
 };

@@ -2,6 +2,7 @@
 // spl_host_res.h), the handle, result and communicator structs of the C ABI, and what fills a context: upload_tables, upload_specials,
 // upload_decode, reserve, ensure_streams.  Needs spl_host_res.h and the kernels' types (spl_kernels.hip, spl_tables.h, spl_regex.h, spl_comm.h).
 #pragma once
+#include <mutex>
 namespace {
 
 constexpr size_t QCOUNT_WORDS = 16;      // Batch::qcount
@@ -67,6 +68,7 @@ struct Ctx {
     HostMapped<uint32_t> h_mflag;
     uint32_t memo_round = 0, memo_cap = 0, memo_mask = 0;
     uint64_t memo_fills = 0, memo_since = 0;
+    uint64_t memo_seed_placed = 0, memo_seed_left = 0;     // the vocabulary keys this memo was seeded with / that found neither slot free (memo_seed)
     bool fuse_off = false;                    // set by the caller of launch_all for this call: the two-launch form (text read in place over PCIe, below)
     uint64_t* off_host = nullptr;             // set by the caller of launch_all: where k_tile_out also stores the offsets (one-chunk host batches)
     bool off_host_written = false;            // launch_all: the tile-owned mode did so
@@ -164,6 +166,12 @@ struct Ctx {
 
 struct spl_tokenizer {
     HostTables ht;
+    // the memo's seed as last planned (memo_seed_plan, spl_tables.cpp), for the table sizes it was planned for: every context, every twin and every
+    // memo built again behind clear_cache uploads this one
+    std::mutex seed_mu;
+    spl::MemoSeedPlan seed_plan;
+    uint32_t seed_plan_bits = 0, seed_plan_long_bits = 0;
+    bool seed_plan_valid = false;
     std::vector<Special> specials;
     uint32_t max_special_id = 0;
     mutable uint32_t max_tok_bytes = 0;       // spl_max_token_bytes, computed at its first call (0: not yet; spl_add_special resets it)
@@ -188,6 +196,7 @@ struct spl_tokenizer {
     uint64_t dec_chunk_ids = 2ull << 20;      // decode pipeline: ids per chunk (batches of fewer than three such chunks are decoded in one piece; C3: 28.3 GB/s at 1 M, 30.5 at 2 M, 29.6 at 3 M)
     int copy_threads = 4;                     // pipeline, pageable input: threads that copy a chunk into pinned staging
     int memo = 1;                             // the chunk memo (spl_k_memo.h); "memo_bits": log2 of its entries (64 bytes each), "memo_log_cap": logged misses per region and fill
+    int memo_first = 1;                       // the memo is seeded with the vocabulary's keys and the tile kernel asks it BEFORE the vocabulary's tables (spl_k_pretok.h); 0: behind them, an unseeded memo
     uint32_t memo_bits = 20, memo_log_cap = 1024, memo_long_bits = 16;          // "memo_long_bits": log2 of the entries for chunks of 33..64 bytes (160 bytes each; 0: none)
     uint32_t range_tiles = 0;                 // "range_tiles" (measured, +2 % on the 215 MB configurations, -2 % on C3 in the bench line: not the default): batches of more than 1.25 x this many tiles go out as ranges of this many (k_pretok + k_tile_out per range; 0: one launch pair)
     uint32_t group_scan_min = 256;            // "group_scan_min": batches of more than this many groups of 64 tiles get the groups' prefix sums from k_group_scan (0: never)

@@ -12,9 +12,15 @@ namespace spl {
 // per chunk, byte_pair_encode by the pair table (bpe_serial, spl_lookup.h) -- and
 // writes their entries between two launches on the handle's stream: kernel boundaries give the coherence that an insert from inside the
 // tile kernel lacked (round 3: eight L2s, plain stores, torn lines).  Result-transparent: a hit returns exactly what the merge returns.
+// With "memo_first" a new memo also holds the vocabulary's own keys -- the seed, k_memo_seed below -- and the tile kernel asks it BEFORE the
+// vocabulary's tables: one trip for a vocabulary token and a learned chunk alike (spl_k_pretok.h, the probe phase).
 
 // meta0 of a valid entry for a chunk of n bytes with t tokens
 __device__ __forceinline__ uint32_t memo_meta0(uint32_t n, uint32_t t) { return 0x80000000u | (t << 8) | n; }
+// bit 30 of meta0: the entry is a vocabulary key put in when the memo was created (k_memo_seed), not a learned chunk.  The probe's compare
+// mask (0x8000003F) ignores it; k_memo_fill reads it where it has to evict.
+constexpr uint32_t MEMO_SEEDED = 0x40000000u;
+constexpr uint32_t MEMO_SEED_KEEP_IDS = 32768u;       // k_memo_fill never lets a seed of a lower id give way to a learned chunk while a learned chunk could
 
 // A miss-list item (window position | length << 16) of a chunk the memo KNOWS and cannot hold: merged as ever, not logged again
 constexpr uint32_t MISS_KNOWN = 0x80000000u;
@@ -22,6 +28,9 @@ constexpr uint32_t MISS_KNOWN = 0x80000000u;
 
 // The probe: text[p, p + n) lies inside the window; LONG: 33 <= n <= 64 (the second table), else 2 <= n <= 32.  emit(position, id) for every
 // token of a hit.  0: not held; 1: held, its tokens are emitted; 2: held as "more than fourteen tokens" -- the chunk goes the usual way, and is not logged.
+#ifndef SPL_MEMO_SKIP_C
+#define SPL_MEMO_SKIP_C 1        /* the second quad of an entry is not loaded for a chunk of up to 16 bytes (0: always, A/B; profiles/memo_first.txt) */
+#endif
 template <bool LONG, class TX, class Emit>
 __device__ __forceinline__ int memo_probe(const DeviceTables& T, const TX& tx, int p, int n, Emit emit) {
     constexpr int KW = LONG ? 16 : 8;
@@ -39,7 +48,9 @@ __device__ __forceinline__ int memo_probe(const DeviceTables& T, const TX& tx, i
 #pragma nounroll
     for (int way = 0; way < 2; way++) {
         const Quad* q = reinterpret_cast<const Quad*>(tab + slot);
-        const Quad a = q[0], c = q[1], m = q[2], d = q[3];        // key[0..3], key[4..7], meta0 meta1 ids[0..1], ids[2..5]
+        // key[0..3], key[4..7], meta0 meta1 ids[0..1], ids[2..5]  (key[4..7] only for a chunk of more than 16 bytes: keys are zero padded, an
+        // equal length and equal key[0..3] settle a shorter one)
+        const Quad a = q[0], c = (SPL_MEMO_SKIP_C && n <= 16) ? Quad{0u, 0u, 0u, 0u} : q[1], m = q[2], d = q[3];
         bool eq = (a.x == k[0]) & (a.y == k[1]) & (a.z == k[2]) & (a.w == k[3]) & (c.x == k[4]) & (c.y == k[5]) & (c.z == k[6]) & (c.w == k[7]) &
                   ((m.x & 0x8000003Fu) == (0x80000000u | nf));
         if (LONG && eq) {                                         // bytes 32..63 of the key
@@ -174,12 +185,22 @@ __global__ __launch_bounds__(LONG ? MEMO_FILL_NT2 : MEMO_FILL_NT) void k_memo_fi
     };
     const bool taken0 = (memo[slots[0]].meta0 >> 31) != 0u, taken1 = (memo[slots[1]].meta0 >> 31) != 0u;
     if ((taken0 && holds(slots[0])) || (taken0 && taken1 && holds(slots[1]))) return;
-    // the first slot if it is free, else the second if it is free, else the first slot's chunk gives way.  One writer per slot and launch
+    // the first slot if it is free, else the second if it is free, else a chunk gives way: a learned chunk in preference to a vocabulary key
+    // of the seed (a seeded entry answers a chunk of ANY text) -- the first slot's, unless that is a seed and the second slot's is not; where both
+    // are seeds the first goes, or the chunk would be logged for ever.  On every other fill the first slot's entry goes WHATEVER it is: two
+    // learned chunks, each held between a seed and the other's slot, would otherwise evict each other for ever (c2_wide: a fill every twenty
+    // launches, profiles/memo_first.txt); a seed that goes never comes back -- the vocabulary's own tables answer its key.  One writer per slot and launch
     // (claim[slot] == round: taken in this launch); a lane that loses both tries is logged again by a later launch.
     MemoEnt* me = nullptr;
     if (!taken0) { if (atomicExch(&claim[slots[0]], round) != round) me = memo + slots[0]; }
     if (!me && taken0 && !taken1) { if (atomicExch(&claim[slots[1]], round) != round) me = memo + slots[1]; }
-    if (!me && taken0 && taken1) { if (atomicExch(&claim[slots[0]], round) != round) me = memo + slots[0]; }
+    if (!me && taken0 && taken1) {
+        // (the seeds of the lowest ids -- a BPE vocabulary's most frequent tokens -- are spared on every fill: what goes one way over a long run
+        //  are first-slot seeds of the rarer keys only)
+        const bool spare_seed = (!(round & 1u) || memo[slots[0]].ids[0] < MEMO_SEED_KEEP_IDS) && (memo[slots[0]].meta0 & MEMO_SEEDED) && !(memo[slots[1]].meta0 & MEMO_SEEDED);
+        const uint32_t ev = slots[spare_seed ? 1 : 0];
+        if (atomicExch(&claim[ev], round) != round) me = memo + ev;
+    }
     if (!me) return;
     __shared__ uint32_t s_id[NMAX * NTF], s_rk[NMAX * NTF];
     MemoNodes<NTF> s{s_id + threadIdx.x, s_rk + threadIdx.x};
@@ -217,6 +238,30 @@ __global__ __launch_bounds__(LONG ? MEMO_FILL_NT2 : MEMO_FILL_NT) void k_memo_fi
     }
     me->meta0 = 0x80000000u | ((fits ? nt : 0u) << 8) | nf;
     if (stats) atomicAdd(&stats[fits ? 0 : 1], 1ull);
+}
+
+// The seed: when a context's memo is created, every vocabulary key of 2..64 bytes that found a slot goes in as a one-token entry, so that the
+// tile kernel can ask the memo FIRST (spl_k_pretok.h).  The host decides the placement (spl_tables.cpp memo_seed_plan: no slot twice) and
+// uploads one record per key -- slot, id | length << 24, the key's zero-padded words (8; LONG: 16) --; one lane per record, on the stream, before
+// any tile kernel reads the table.  The table is zeroed: only the words that differ are written.
+template <bool LONG>
+__global__ __launch_bounds__(256) void k_memo_seed(MemoEnt* memo, MemoHi* memo_hi, uint32_t mask, const uint32_t* list, uint32_t count) {
+    constexpr uint32_t RW = 2u + (LONG ? 16u : 8u);
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const uint32_t* r = list + (size_t)i * RW;
+    const uint32_t slot = r[0], id = r[1] & SPL_ID_MASK, n = r[1] >> 24;
+    if (slot > mask || n < (LONG ? (uint32_t)SPL_MEMO_MAX_LEN + 1u : 2u) || n > (uint32_t)(LONG ? SPL_MEMO_MAX_LEN2 : SPL_MEMO_MAX_LEN)) return;
+    MemoEnt* me = memo + slot;
+#pragma unroll
+    for (int w = 0; w < 8; w++) me->key[w] = r[2 + w];
+    if (LONG) {
+#pragma unroll
+        for (int w = 0; w < 8; w++) memo_hi[slot].k[w] = r[10 + w];
+    }
+    me->meta1 = 0u;
+    me->ids[0] = id;
+    me->meta0 = memo_meta0(LONG ? n - (uint32_t)SPL_MEMO_MAX_LEN : n, 1u) | MEMO_SEEDED;
 }
 
 }  // namespace spl

@@ -15,10 +15,11 @@ __device__ __forceinline__ uint32_t xcd_tile() {
     return x * q + (x < r ? x : r) + j;
 }
 // e_flags of k_pretok: which optional inputs exist, and the split pattern
-constexpr uint32_t PRETOK_E_TSTART = 1u, PRETOK_E_SKIP = 2u, PRETOK_E_GAPS = 4u, PRETOK_E_EXT = 8u, PRETOK_E_FUSE = 64u;
+constexpr uint32_t PRETOK_E_TSTART = 1u, PRETOK_E_SKIP = 2u, PRETOK_E_GAPS = 4u, PRETOK_E_EXT = 8u, PRETOK_E_FUSE = 64u, PRETOK_E_MEMO1 = 128u;
 inline uint32_t pretok_flags(const DeviceTables& T, const Batch& b) {
     return (b.tstart ? PRETOK_E_TSTART : 0u) | (b.skip ? PRETOK_E_SKIP : 0u) | (b.ext_gaps ? PRETOK_E_GAPS : 0u) |
-           (b.ext_starts ? PRETOK_E_EXT : 0u) | (T.pattern << 4) | (b.ftc ? PRETOK_E_FUSE : 0u) | (b.tile0 << 8);        // (bits 8..31: the launch's first tile)
+           (b.ext_starts ? PRETOK_E_EXT : 0u) | (T.pattern << 4) | (b.ftc ? PRETOK_E_FUSE : 0u) | ((b.memo_first && T.memo) ? PRETOK_E_MEMO1 : 0u) |
+           (b.tile0 << 8);        // (bits 8..31: the launch's first tile)
 }
 // the kernel-argument segment of k_pretok as the ABI lays it out (every argument at its natural alignment, in order)
 struct PretokKernargs {
@@ -574,6 +575,7 @@ void k_pretok(const uint8_t* e_text, const uint64_t* e_doc_off, uint32_t e_n_byt
         LdsAcc tx{s_rec, s_txt};
         const bool from_list = LIST_CHUNKS && !fast_starts;
         const int K = from_list ? (int)s_nch + 1 : (int)s_total;
+        const bool memo_first = (e_flags & PRETOK_E_MEMO1) != 0u;           // (set only where the launch has a memo)
         for (int k = tid; k + 1 < K; k += NT) {
             int p, n;
             if (from_list) {
@@ -584,22 +586,42 @@ void k_pretok(const uint8_t* e_text, const uint64_t* e_doc_off, uint32_t e_n_byt
                 if (ext ? ((s_sk[p >> 5] >> (p & 31)) & 1u) != 0u : (s_rec[p] & CB_CLASS) >= C_EOT) continue;   // a special-literal span / dropped bytes
                 n = (int)s_cpos[k + 1] - p;
             }
-            const uint32_t id = probe_chunk_tile(T, tx, p, n);
+            // Two lookups, the vocabulary's tables and the chunk memo (spl_k_memo.h), in the order the launch asks for.
+            auto memo_put = [&](int q, uint32_t tid_) { s_ids[q] = tid_; atomicOr(&s_tbits[q >> 5], 1u << (q & 31)); };
+            const bool m_short = T.memo && n > 1 && n <= SPL_MEMO_MAX_LEN && p + n <= Wv;
+            const bool m_long = T.memo2 && n > SPL_MEMO_MAX_LEN && n <= SPL_MEMO_MAX_LEN2 && p + n <= Wv;       // (few: long identifiers, URLs)
+            uint32_t id = SPL_NO_RANK;
+            int held = 0;                                     // the memo's answer (memo_probe)
+            if (memo_first) {
+                // Memo first (a memo seeded with the vocabulary, spl_launch.h memo_seed): ONE trip that depends on the text alone answers a
+                // vocabulary token and a learned chunk alike, and the vocabulary's tables -- prefix entry, filter entry, table entry, a long
+                // key's blob: each trip waits for the one before -- are read only by the lanes the memo could not answer: a wavefront
+                // without such a lane skips that branch.
+                if (n == 1) {                                 // one byte: its id, no table (a byte the vocabulary lacks has a pseudo id: no token)
+                    id = T.byte_id[s_txt[p]];
+                    if (id >= T.id_limit) id = SPL_NO_RANK;
+                } else {
+                    if (m_short) held = memo_probe<false>(T, tx, p, n, memo_put);
+                    else if (m_long) held = memo_probe<true>(T, tx, p, n, memo_put);
+                    // (held as "more than fourteen tokens": only a chunk the vocabulary missed is -- no probe of its tables)
+                    if (held == 0) id = probe_chunk_tile(T, tx, p, n);
+                }
+            } else {
+                // Vocabulary first: the memo sees only what the vocabulary missed
+                id = probe_chunk_tile(T, tx, p, n);
+                if (id == SPL_NO_RANK && n > 1) {
+                    held = m_short ? memo_probe<false>(T, tx, p, n, memo_put) : 0;
+                    if (m_long) held = memo_probe<true>(T, tx, p, n, memo_put);
+                }
+            }
+#ifdef SPL_MEMO_STATS      /* profiling: chunks the vocabulary's tables did not answer by what the memo said -- e_dbg[4..7]: not probed, not held, held, known as too long */
+            if (e_dbg && id == SPL_NO_RANK && n > 1) atomicAdd(&e_dbg[4 + ((m_short || m_long) ? 1 + held : 0)], 1ull);
+#endif
             if (id != SPL_NO_RANK) {
                 if (DIRECT) s_ids[p] = id;
                 else b.stage[w0 + p] = id;
                 atomicOr(&s_tbits[p >> 5], 1u << (p & 31));
-            } else if (n > 1) {
-                // the chunk memo (spl_k_memo.h): a chunk it holds is finished here -- its tokens go in place -- and never reaches the merge loops
-                auto memo_put = [&](int q, uint32_t tid_) { s_ids[q] = tid_; atomicOr(&s_tbits[q >> 5], 1u << (q & 31)); };
-                const bool m_short = T.memo && n <= SPL_MEMO_MAX_LEN && p + n <= Wv;
-                const bool m_long = T.memo2 && n > SPL_MEMO_MAX_LEN && n <= SPL_MEMO_MAX_LEN2 && p + n <= Wv;       // (few: long identifiers, URLs)
-                int held = m_short ? memo_probe<false>(T, tx, p, n, memo_put) : 0;
-                if (m_long) held = memo_probe<true>(T, tx, p, n, memo_put);
-#ifdef SPL_MEMO_STATS      /* profiling: chunks the vocabulary misses by what the memo said -- e_dbg[4..7]: not probed, not held, held, known as too long */
-                if (e_dbg) atomicAdd(&e_dbg[4 + ((m_short || m_long) ? 1 + held : 0)], 1ull);
-#endif
-                if (held == 1) continue;
+            } else if (n > 1 && held != 1) {
                 const uint32_t item = (uint32_t)p | ((uint32_t)n << 16) | (held == 2 ? MISS_KNOWN : 0u);
                 if (TILE_LIST) {
                     // tile-owned: every miss goes on ONE list and through the segment pass of the tail

@@ -140,6 +140,7 @@ struct Batch {
     // words each, their fill counters, and the word in pinned host memory that tells the host there is something to put in
     uint32_t* mlog; uint32_t* mlog_cnt; uint32_t mlog_cap; uint32_t* mflag;
     uint32_t* mlog2; uint32_t mlog2_cap;      // ... of chunks of 33..64 bytes (SPL_MEMO_LOG_WORDS2 words an entry; counters: mlog_cnt + SPL_MEMO_LOG_REGIONS; nullptr: not logged)
+    uint32_t memo_first;       // the tile kernel asks the (vocabulary-seeded) memo BEFORE the vocabulary's tables ("memo_first"; a flag of the launch: PRETOK_E_MEMO1)
     uint32_t id_limit;         // DeviceTables::id_limit, for the kernels that are given no tables
 };
 

@@ -17,7 +17,7 @@ int rx_launch(spl_tokenizer* tk, Ctx* c, const uint8_t* d_text, uint64_t n_bytes
               uint32_t* d_starts, uint32_t* d_gaps, uint32_t* d_status, hipStream_t s, const Batch* sp = nullptr, uint32_t sp_words = 0,
               uint32_t* d_status_host = nullptr, bool bad_sets_status = false);
 
-// The chunk memo of a context (spl_k_memo.h): built empty at the first launch; the tiles log what it did not hold and raise the pinned
+// The chunk memo of a context (spl_k_memo.h): built at the first launch -- empty, or ("memo_first") seeded with the vocabulary's keys; the tiles log what it did not hold and raise the pinned
 // flag; a launch that finds the flag raised first runs k_memo_fill on its stream -- encode the logged chunks, put them in -- and then
 // its own kernels: the memo is only ever written between two launches of the stream that reads it.
 // (the parts of the second table's one allocation)
@@ -33,7 +33,34 @@ void memo_tables(Ctx* t) {
     t->dt.memo2 = nullptr; t->dt.memo2_mask = 0; t->dt.memo2_ext = nullptr; t->dt.memo2_hi = nullptr;
     if (t->d_memo2.get()) { const Memo2Parts m = memo2_parts(t); t->dt.memo2 = m.ent; t->dt.memo2_mask = t->memo2_mask; t->dt.memo2_ext = m.ext; t->dt.memo2_hi = m.hi; }
 }
-int memo_ensure(spl_tokenizer* tk, Ctx* t) {
+// The seed of a NEW memo ("memo_first"): every vocabulary key of 2..64 bytes that finds one of its two slots free, as a one-token entry -- the
+// placement decided here (memo_seed_plan), one compact record per key uploaded and scattered by ONE launch per table on the stream, in front
+// of the first tile kernel that reads the table: "written only between launches" holds.  The copy is synchronous (the list is a local).
+const spl::MemoSeedPlan& memo_seed_planned(spl_tokenizer* tk, uint32_t bits, uint32_t long_bits) {      // (the caller holds tk->seed_mu)
+    if (!tk->seed_plan_valid || tk->seed_plan_bits != bits || tk->seed_plan_long_bits != long_bits) {
+        spl::memo_seed_plan(tk->ht, bits, long_bits, tk->seed_plan);
+        tk->seed_plan_bits = bits; tk->seed_plan_long_bits = long_bits; tk->seed_plan_valid = true;
+    }
+    return tk->seed_plan;
+}
+int memo_seed(spl_tokenizer* tk, Ctx* t, hipStream_t s) {
+    std::lock_guard<std::mutex> lock(tk->seed_mu);
+    const spl::MemoSeedPlan& plan = memo_seed_planned(tk, tk->memo_bits, t->d_memo2.get() ? tk->memo_long_bits : 0u);
+    t->memo_seed_placed = plan.placed; t->memo_seed_left = plan.left_out;
+    DevBuf<uint32_t> d_list;
+    const size_t n1 = plan.list.size(), n2 = plan.list2.size();
+    if (!(n1 + n2)) return SPL_OK;
+    SPL_TRY(d_list.alloc(n1 + n2));
+    HIP_TRY(hipStreamSynchronize(nullptr));        // (the tables' zero fill ran on the default stream)
+    if (n1) HIP_TRY(hipMemcpy(d_list.get(), plan.list.data(), n1 * 4, hipMemcpyHostToDevice));
+    if (n2) HIP_TRY(hipMemcpy(d_list.get() + n1, plan.list2.data(), n2 * 4, hipMemcpyHostToDevice));
+    const uint32_t c1 = (uint32_t)(n1 / 10), c2 = (uint32_t)(n2 / 18);
+    if (c1) hipLaunchKernelGGL(k_memo_seed<false>, dim3((c1 + 255) / 256), dim3(256), 0, s, t->d_memo.get(), (MemoHi*)nullptr, t->memo_mask, (const uint32_t*)d_list.get(), c1);
+    if (c2) { const Memo2Parts m = memo2_parts(t); hipLaunchKernelGGL(k_memo_seed<true>, dim3((c2 + 255) / 256), dim3(256), 0, s, m.ent, m.hi, t->memo2_mask, (const uint32_t*)(d_list.get() + n1), c2); }
+    HIP_TRY(hipStreamSynchronize(s));              // (the list is freed here; once per memo)
+    return SPL_OK;
+}
+int memo_ensure(spl_tokenizer* tk, Ctx* t, hipStream_t s) {
     if (t->d_memo.get()) return SPL_OK;
     const size_t slots = (size_t)1 << tk->memo_bits;
     SPL_TRY(t->d_memo.alloc_zeroed(slots));
@@ -59,11 +86,13 @@ int memo_ensure(spl_tokenizer* tk, Ctx* t) {
     t->memo_mask = (uint32_t)(slots - 1);
     memo_tables(t);
     t->memo_round = 0; t->memo_fills = 0; t->memo_since = 0;
+    t->memo_seed_placed = t->memo_seed_left = 0;
+    if (tk->memo_first) SPL_TRY(memo_seed(tk, t, s));
     return SPL_OK;
 }
 int memo_before_launch(spl_tokenizer* tk, Ctx* t, hipStream_t s) {
     if (!tk->memo) { t->dt.memo = nullptr; t->dt.memo2 = nullptr; return SPL_OK; }
-    int rc = memo_ensure(tk, t);
+    int rc = memo_ensure(tk, t, s);
     if (rc) return rc;
     memo_tables(t);
     t->memo_since++;
@@ -152,6 +181,7 @@ int launch_all(spl_tokenizer* tk, Ctx* t, const uint8_t* d_utf8, uint64_t n_byte
         if (rcm) return rcm;
         if (t->dt.memo) { b.mlog = t->d_mlog.get(); b.mlog_cnt = t->d_mlog_cnt.get(); b.mlog_cap = t->memo_cap; b.mflag = t->h_mflag.dev(); }
         if (t->dt.memo && t->d_memo2.get()) { b.mlog2 = memo2_parts(t).log; b.mlog2_cap = t->memo2_cap; }
+        b.memo_first = (t->dt.memo && tk->memo_first) ? 1u : 0u;
     }
 
     const bool pf = t->prof;

@@ -75,6 +75,35 @@ uint32_t load_le(const std::string& s, size_t off) {      // up to 4 bytes, zero
 
 }  // namespace
 
+void memo_seed_plan(const HostTables& t, uint32_t bits, uint32_t long_bits, MemoSeedPlan& out) {
+    out.list.clear(); out.list2.clear();
+    out.placed = out.left_out = 0;
+    const uint32_t mask = (1u << bits) - 1u, mask2 = long_bits ? (1u << long_bits) - 1u : 0u;
+    std::vector<uint8_t> used((size_t)mask + 1, 0), used2(long_bits ? (size_t)mask2 + 1 : 0, 0);
+    for (size_t i = 0; i < t.seed_id.size(); i++) {
+        const uint8_t* kb = t.seed_bytes.data() + t.seed_off[i];
+        const uint32_t n = t.seed_off[i + 1] - t.seed_off[i];
+        const bool lng = n > (uint32_t)SPL_MEMO_MAX_LEN;
+        if (lng && !long_bits) { out.left_out++; continue; }
+        uint32_t k[16] = {0};
+        for (uint32_t q = 0; q < n; q++) k[q >> 2] |= (uint32_t)kb[q] << (8 * (q & 3));
+        uint32_t h;
+        if (lng) h = hash_memo_w<16>(k, n);
+        else { uint32_t k8[8]; memcpy(k8, k, sizeof k8); h = hash_memo_w<8>(k8, n); }
+        const uint32_t m = lng ? mask2 : mask;
+        std::vector<uint8_t>& u = lng ? used2 : used;
+        uint32_t slot = h & m;
+        if (u[slot]) slot = memo_slot2(h, m);
+        if (u[slot]) { out.left_out++; continue; }
+        u[slot] = 1;
+        std::vector<uint32_t>& l = lng ? out.list2 : out.list;
+        l.push_back(slot);
+        l.push_back(t.seed_id[i] | n << 24);
+        l.insert(l.end(), k, k + (lng ? 16 : 8));
+        out.placed++;
+    }
+}
+
 uint32_t host_cp_class(const HostTables& t, uint32_t cp) {
     if (cp >= 0x110000u) return C_P;
     const uint32_t blk = t.ucls_stage1[cp >> t.ucls_shift];
@@ -329,6 +358,19 @@ int build_tables(const uint8_t* splv, size_t splv_len, const uint8_t* ucls, size
         for (int b = 0; b < 256; b++) if (out.byte_id[b] == SPL_NO_RANK) out.byte_id[b] = next++;
         if (next - 1 >= SPL_ID_MASK) { err = "token ids must be < 2^21 - 1 (with the pseudo ids of the single bytes the vocabulary lacks)"; return 1; }
         out.id_limit = max_rank_seen + 1;
+    }
+
+    {   // the chunk memo's seed: the very keys the tables below are built from, of 2..64 bytes, by ascending id
+        std::vector<std::pair<uint32_t, const std::string*>> ks;
+        for (const auto& kv : enc) if (kv.first.size() >= 2 && kv.first.size() <= (size_t)SPL_MEMO_MAX_LEN2) ks.emplace_back(kv.second, &kv.first);
+        std::sort(ks.begin(), ks.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+        out.seed_id.clear(); out.seed_bytes.clear();
+        out.seed_off.assign(1, 0u);
+        for (const auto& k : ks) {
+            out.seed_id.push_back(k.first);
+            out.seed_bytes.insert(out.seed_bytes.end(), k.second->begin(), k.second->end());
+            out.seed_off.push_back((uint32_t)out.seed_bytes.size());
+        }
     }
 
     // ---- short / long key tables ----------------------------------------------------------

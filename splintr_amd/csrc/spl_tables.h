@@ -51,7 +51,21 @@ struct HostTables {
     std::vector<uint32_t> tok_off;      // max_id + 2
     std::vector<uint8_t> tok_bytes;
     std::vector<uint8_t> tok_present;   // max_id + 1: 0 no such id, 1 a token, 2 (ByteLevel) a token whose key is emitted verbatim
+    // the chunk memo's seed (memo_seed_plan): the keys of 2..64 bytes the tables above were built from -- in the key space the kernels see --
+    // in ascending id order; key i is seed_bytes[seed_off[i], seed_off[i + 1])
+    std::vector<uint32_t> seed_id, seed_off;
+    std::vector<uint8_t> seed_bytes;
 };
+
+// Where the vocabulary's keys go in a NEW chunk memo of 2^bits entries (keys of 2..32 bytes) and 2^long_bits entries (33..64 bytes; 0: no
+// such table): in ascending id order -- the frequent low ids get their first slot --, each key into its first candidate slot if that is free,
+// else its second if that is free, else it is left out (the vocabulary's own tables answer it).  One record per placed key, as k_memo_seed reads
+// them: slot, id | length << 24, the key's zero-padded little-endian words (8 in `list`, 16 in `list2`).
+struct MemoSeedPlan {
+    std::vector<uint32_t> list, list2;
+    uint64_t placed = 0, left_out = 0;
+};
+void memo_seed_plan(const HostTables& t, uint32_t bits, uint32_t long_bits, MemoSeedPlan& out);
 
 // Returns 0 on success; on failure fills err.
 // `vocab` is either this repo's SPLV container or the reference's tiktoken text (autodetected by the
