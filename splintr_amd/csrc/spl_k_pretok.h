@@ -660,8 +660,16 @@ void k_pretok(const uint8_t* e_text, const uint64_t* e_doc_off, uint32_t e_n_byt
     // (scanner phases run at high priority, the merge loops below them: a workgroup that is still
     // scanning is never starved by older workgroups that already merge; +3 % on the bench batch)
     if (DIRECT) __builtin_amdgcn_s_setprio(SPL_MERGE_PRIO);
+    // A tile without a miss -- with the memo warm nearly every one -- has nothing to do here: no sort, no pull, no closing barrier (nothing
+    // was written since the probe's barrier, which made both counts final; as scalars, so that the branches below are branches).  With only
+    // medium misses the sort of the short list -- three barriers -- is skipped, with only short ones the medium pull.
+#ifndef SPL_MERGE_SKIP
+#define SPL_MERGE_SKIP 1         /* 0: every tile walks the whole phase (A/B) */
+#endif
+    const uint32_t m16 = TILE_LIST ? 0u : (uint32_t)__builtin_amdgcn_readfirstlane((int)s_nq[0]);
+    const uint32_t m64 = TILE_LIST ? 0u : (uint32_t)__builtin_amdgcn_readfirstlane((int)s_nq[1]);
+    const bool do_short = !SPL_MERGE_SKIP || m16 != 0u, do_medium = !SPL_MERGE_SKIP || m64 != 0u;
     if (!TILE_LIST) {
-        const uint32_t m16 = s_nq[0], m64 = s_nq[1];
         // Short misses sorted by length, longest first (counting sort into s_cpos, which is free
         // until the tile record): the four chunks a wavefront merges in lock step then have similar
         // lengths -- a round lasts as long as its longest chunk -- and the longest chains start first.
@@ -669,7 +677,7 @@ void k_pretok(const uint8_t* e_text, const uint64_t* e_doc_off, uint32_t e_n_byt
 #define SPL_SORT_SHORT 1         /* 0: the short misses in list order (A/B) */
 #endif
         constexpr bool SORT_SHORT = SPL_SORT_SHORT && Wv <= 1024;            // window index (10 bits) | n - 1 (4 bits) in 16 bits
-        if (SORT_SHORT) {
+        if (SORT_SHORT && do_short) {
             uint32_t my_item[(G::C16 + NT - 1) / NT], my_r[(G::C16 + NT - 1) / NT];
 #pragma unroll
             for (int q = 0; q < (G::C16 + NT - 1) / NT; q++) {
@@ -720,7 +728,7 @@ void k_pretok(const uint8_t* e_text, const uint64_t* e_doc_off, uint32_t e_n_byt
         uint32_t ws_nmed = 0, ws_nshort = 0;
         long long ws_wt[6] = {0, 0, 0, 0, 0, 0};
 #endif
-        for (;;) {
+        if (do_medium) for (;;) {
             // A wavefront takes TWO chunks per pull: if both have at most 32 bytes (of ASCII: no independent
             // segments to look for) each gets a half of the wavefront and they merge side by side -- a tile
             // with several long words (the slowest tiles of the bench batch are those) needs half the pulls.
@@ -776,7 +784,7 @@ void k_pretok(const uint8_t* e_text, const uint64_t* e_doc_off, uint32_t e_n_byt
         // 16-lane group's work of a pull: one chunk of the first kind, or two of the second, one per half of the group.
         const uint32_t first8 = (SPL_PAIR_SHORT && SORT_SHORT) ? s_scnt[8] : m16;
         const uint32_t nslots = first8 + (m16 - first8 + 1u) / 2u;
-        for (;;) {
+        if (do_short) for (;;) {
             uint32_t it = 0;
             if ((lane & 15) == 0) it = atomicAdd(&s_nq[2], 1u);
             it = __shfl(it, lane & ~15);
@@ -828,7 +836,7 @@ void k_pretok(const uint8_t* e_text, const uint64_t* e_doc_off, uint32_t e_n_byt
 #endif
     }
     SPL_STAMP(10);
-    __syncthreads();
+    if (TILE_LIST || do_short || do_medium) __syncthreads();
     SPL_STAMP(7);
     // chunk memo: what this tile had to merge goes into the handle's log (wavefront 3: in the fused mode it has nothing to do until the tile's
     // base is known; the lists are intact here -- the tail below overlays them)
