@@ -216,7 +216,8 @@ static int spl_encode_batch_device_impl(spl_tokenizer* t, const uint8_t* d_utf8,
         return fail(SPL_EINVAL, "spl_encode_batch_device: null argument");
     HIP_TRY(hipSetDevice(t->ctx[0]->device));
     if (t->regex) return encode_device_custom(t, t->ctx[0].get(), d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_capacity, d_out_off, (hipStream_t)hip_stream, nullptr);
-    return launch_all(t, t->ctx[0].get(), d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_capacity, d_out_off, (hipStream_t)hip_stream);
+    return launch_all(t, t->ctx[0].get(), {.text = d_utf8, .n_bytes = n_bytes, .doc_off = d_doc_off, .n_docs = n_docs, .flags = flags,
+                                           .ids = d_ids, .ids_cap = ids_capacity, .out_off = d_out_off, .stream = (hipStream_t)hip_stream});
 }
 
 static int spl_encode_batch_device_packed_impl(spl_tokenizer* t, const uint8_t* d_utf8, uint64_t n_bytes, const uint64_t* d_doc_off,
@@ -231,7 +232,8 @@ static int spl_encode_batch_device_packed_impl(spl_tokenizer* t, const uint8_t* 
     SlabOut so;
     so.d_slab = d_slab; so.cap_words = cap_words; so.max_docs = max_docs;
     if (t->regex) return encode_device_custom(t, t->ctx[0].get(), d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_capacity, d_out_off, (hipStream_t)hip_stream, &so);
-    return launch_all(t, t->ctx[0].get(), d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_capacity, d_out_off, (hipStream_t)hip_stream, &so);
+    return launch_all(t, t->ctx[0].get(), {.text = d_utf8, .n_bytes = n_bytes, .doc_off = d_doc_off, .n_docs = n_docs, .flags = flags,
+                                           .ids = d_ids, .ids_cap = ids_capacity, .out_off = d_out_off, .stream = (hipStream_t)hip_stream, .slab = &so});
 }
 
 int spl_encode_batch(spl_tokenizer* t, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, uint32_t flags,
@@ -474,12 +476,13 @@ int spl_debug_merge_timing(unsigned long long out[8], int reset) {
 int spl_memo_stats(spl_tokenizer* t, uint64_t out[4]) {
     if (!t || !out) return fail(SPL_EINVAL, "null argument");
     Ctx* c = t->ctx[0].get();
-    out[0] = c->memo_fills; out[1] = out[2] = 0; out[3] = c->d_memo.get() ? (uint64_t)c->memo_mask + 1 + (c->d_memo2.get() ? (uint64_t)c->memo2_mask + 1 : 0) : 0;
-    if (c->d_mstats.get()) {
+    const Memo& m = c->memo;
+    out[0] = m.fills; out[1] = out[2] = 0; out[3] = m ? (uint64_t)m.mask + 1 + (m.d_tab2 ? (uint64_t)m.mask2 + 1 : 0) : 0;
+    if (m) {
         HIP_TRY(hipSetDevice(c->device));
         HIP_TRY(hipDeviceSynchronize());
         unsigned long long st[2] = {0, 0};
-        HIP_TRY(hipMemcpy(st, c->d_mstats.get(), 16, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(st, m.d_stats.get(), 16, hipMemcpyDeviceToHost));
         out[1] = st[0]; out[2] = st[1];
     }
     return SPL_OK;
@@ -489,7 +492,7 @@ int spl_memo_seed_stats(spl_tokenizer* t, uint64_t out[2]) {
     if (!t || !out) return fail(SPL_EINVAL, "null argument");
     Ctx* c = t->ctx[0].get();
     out[0] = out[1] = 0;
-    if (c->d_memo.get()) { out[0] = c->memo_seed_placed; out[1] = c->memo_seed_left; }
+    if (c->memo) { out[0] = c->memo.seed_placed; out[1] = c->memo.seed_left; }
     else if (t->memo && t->memo_first) {                        // (no memo yet: what the next launch will seed -- the host's plan, no device state)
         std::lock_guard<std::mutex> lock(t->seed_mu);
         const spl::MemoSeedPlan& plan = memo_seed_planned(t, t->memo_bits, t->memo_long_bits);
@@ -504,15 +507,16 @@ int spl_debug_memo_entry(spl_tokenizer* t, int long_table, uint32_t slot, uint32
     if (!t || !out) return fail(SPL_EINVAL, "null argument");
     Ctx* c = t->ctx[0].get();
     const bool lng = long_table != 0;
-    if (!c->d_memo.get() || (lng && !c->d_memo2.get()) || slot > (lng ? c->memo2_mask : c->memo_mask)) return fail(SPL_EINVAL, "spl_debug_memo_entry: no such table or slot");
+    const Memo& m = c->memo;
+    if (!m || (lng && !m.d_tab2) || slot > (lng ? m.mask2 : m.mask)) return fail(SPL_EINVAL, "spl_debug_memo_entry: no such table or slot");
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(hipDeviceSynchronize());
     memset(out, 0, 24 * sizeof(uint32_t));
-    if (!lng) HIP_TRY(hipMemcpy(out, c->d_memo.get() + slot, sizeof(MemoEnt), hipMemcpyDeviceToHost));
+    if (!lng) HIP_TRY(hipMemcpy(out, m.d_tab.get() + slot, sizeof(MemoEnt), hipMemcpyDeviceToHost));
     else {
-        const Memo2Parts m = memo2_parts(c);
-        HIP_TRY(hipMemcpy(out, m.ent + slot, sizeof(MemoEnt), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(out + 16, m.hi + slot, sizeof(MemoHi), hipMemcpyDeviceToHost));
+        const Memo2Parts p = m.parts2();
+        HIP_TRY(hipMemcpy(out, p.ent + slot, sizeof(MemoEnt), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out + 16, p.hi + slot, sizeof(MemoHi), hipMemcpyDeviceToHost));
     }
     return SPL_OK;
 }
@@ -673,8 +677,8 @@ int spl_encode_chunks_device(spl_tokenizer* t, const uint8_t* d_utf8, uint64_t n
         HIP_TRY(hipSetDevice(t->ctx[0]->device));
         ExtIn ext;
         ext.d_starts = d_start_bits; ext.d_gaps = d_gap_bits;
-        return launch_all(t, t->ctx[0].get(), d_utf8, n_bytes, d_doc_off, n_docs, 0, d_ids, ids_capacity, d_out_off,
-                          (hipStream_t)hip_stream, nullptr, &ext);
+        return launch_all(t, t->ctx[0].get(), {.text = d_utf8, .n_bytes = n_bytes, .doc_off = d_doc_off, .n_docs = n_docs,
+                                               .ids = d_ids, .ids_cap = ids_capacity, .out_off = d_out_off, .stream = (hipStream_t)hip_stream, .ext = &ext});
     });
 }
 

@@ -1,6 +1,8 @@
-// spl_ctx.h -- what a handle IS: the per-GPU context (Ctx: tables, workspace, memo, staging, streams -- every GPU resource an owner from
-// spl_host_res.h), the handle, result and communicator structs of the C ABI, and what fills a context: upload_tables, upload_specials,
-// upload_decode, reserve, ensure_streams.  Needs spl_host_res.h and the kernels' types (spl_kernels.hip, spl_tables.h, spl_regex.h, spl_comm.h).
+// spl_ctx.h -- what a handle IS: the per-GPU context (Ctx: tables, workspace, staging, streams -- every GPU resource an owner from
+// spl_host_res.h -- and the chunk memo, one Memo that owns all of it), the handle, result and communicator structs of the C ABI, and what
+// fills a context: upload_tables, upload_specials, upload_decode, reserve, ensure_streams.  A context holds what lasts from call to call;
+// what one device call wants travels in its LaunchReq (spl_launch.h), never through a member here.
+// Needs spl_host_res.h and the kernels' types (spl_kernels.hip, spl_tables.h, spl_regex.h, spl_comm.h).
 #pragma once
 #include <mutex>
 namespace {
@@ -20,6 +22,33 @@ struct TableSet {
     DevBuf<uint64_t> pair_tab; DevBuf<uint32_t> byte_id, p8_tab; DevBuf<uint16_t> len_mask; DevBuf<PfxEnt> pfx; DevBuf<uint16_t> filt4;
     DevBuf<uint32_t> akind;
     DeviceTables view{};                       // what the kernels take by value (its memo fields stay empty: those are each context's own, Ctx::dt)
+};
+
+// The chunk memo of one context (spl_k_memo.h), everything of it: the table, the tiles' log of what it did not hold, one claim word per slot
+// for k_memo_fill, the pinned flag the tiles raise, the counters.  Built as a whole by memo_ensure (spl_launch.h) and only then moved into
+// the context; empty (false) until then and after Ctx::memo_drop.
+struct Memo2Parts { MemoEnt* ent; MemoExt* ext; MemoHi* hi; uint32_t* claim; uint32_t* log; };      // (the parts of the second table's one allocation)
+struct Memo {
+    DevBuf<MemoEnt> d_tab; DevBuf<MemoExt> d_ext; DevBuf<uint32_t> d_log, d_log_cnt, d_claim;
+    DevBuf<uint8_t> d_tab2;                   // the second table (chunks of 33..64 bytes), ONE allocation: entries | second lines | key bytes 32..63 | claim words | log
+    uint32_t mask = 0, cap = 0, mask2 = 0, cap2 = 0;      // slots - 1 of either table; logged misses per region and fill
+    DevBuf<unsigned long long> d_stats;
+    HostMapped<uint32_t> h_flag;
+    uint32_t round = 0;
+    uint64_t fills = 0, since = 0;
+    uint64_t seed_placed = 0, seed_left = 0;  // the vocabulary keys this memo was seeded with / that found neither slot free (memo_seed)
+    explicit operator bool() const { return (bool)d_tab; }
+    Memo2Parts parts2() const {
+        const size_t s2 = (size_t)mask2 + 1;
+        Memo2Parts m;
+        m.ent = (MemoEnt*)d_tab2.get(); m.ext = (MemoExt*)(m.ent + s2); m.hi = (MemoHi*)(m.ext + s2); m.claim = (uint32_t*)(m.hi + s2); m.log = m.claim + s2;
+        return m;
+    }
+    void tables(DeviceTables& dt) const {     // the memo fields of what the kernels take by value (all null for an empty memo)
+        dt.memo = d_tab.get(); dt.memo_mask = mask; dt.memo_ext = d_ext.get();
+        dt.memo2 = nullptr; dt.memo2_mask = 0; dt.memo2_ext = nullptr; dt.memo2_hi = nullptr;
+        if (d_tab2) { const Memo2Parts m = parts2(); dt.memo2 = m.ent; dt.memo2_mask = mask2; dt.memo2_ext = m.ext; dt.memo2_hi = m.hi; }
+    }
 };
 
 // Everything that lives on ONE GPU: lookup tables, workspace, and the host pipeline's streams and
@@ -60,22 +89,9 @@ struct Ctx {
     // array u32[FUSE_STRIDE]); a fused launch uses parity fpar and zeroes what the previous fused launch (fprev tiles) left in the other one
     DevBuf<uint8_t> d_fctl;
     uint32_t fpar = 0, fprev = 0;
-    // chunk memo (spl_k_memo.h): the table, the tiles' log of what it did not hold, one claim word per slot for k_memo_fill, the pinned flag
-    DevBuf<MemoEnt> d_memo; DevBuf<MemoExt> d_memo_ext; DevBuf<uint32_t> d_mlog, d_mlog_cnt, d_mclaim;
-    DevBuf<uint8_t> d_memo2;                  // the second table (chunks of 33..64 bytes), ONE allocation: entries | second lines | key bytes 32..63 | claim words | log
-    uint32_t memo2_mask = 0, memo2_cap = 0;
-    DevBuf<unsigned long long> d_mstats;
-    HostMapped<uint32_t> h_mflag;
-    uint32_t memo_round = 0, memo_cap = 0, memo_mask = 0;
-    uint64_t memo_fills = 0, memo_since = 0;
-    uint64_t memo_seed_placed = 0, memo_seed_left = 0;     // the vocabulary keys this memo was seeded with / that found neither slot free (memo_seed)
-    bool fuse_off = false;                    // set by the caller of launch_all for this call: the two-launch form (text read in place over PCIe, below)
-    uint64_t* off_host = nullptr;             // set by the caller of launch_all: where k_tile_out also stores the offsets (one-chunk host batches)
-    bool off_host_written = false;            // launch_all: the tile-owned mode did so
+    Memo memo;                                // chunk memo: empty until the first launch builds it (memo_ensure)
     // latency path (encode_small): text and offsets read where they lie in pinned host memory, completion by a word k_tile_out stores there
-    uint32_t* done_arm = nullptr;             // set by the caller of launch_all: device pointer of the completion word (this call only)
-    uint32_t done_seq = 0;
-    bool done_armed = false;                  // launch_all: k_tile_out will store it
+    uint32_t done_seq = 0;                    // the value the last call's completion word takes (it travels in that call's LaunchReq)
     HostMapped<uint8_t> h_small;              // pinned: [text 4096 + 64 | offsets 8 * 257 | completion word]
     uint32_t small_calls = 0;
     const void* dp_host[2] = {nullptr, nullptr}; void* dp_dev[2] = {nullptr, nullptr};   // device pointers of the last two pinned result buffers
@@ -145,11 +161,11 @@ struct Ctx {
         cap_bytes = cap_docs = 0;
     }
     void memo_drop() {                        // (a new geometry: the next launch builds an empty memo)
-        if (!d_memo) return;
+        if (!memo) return;
         if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return; }
         (void)hipDeviceSynchronize();
-        d_memo.reset(); d_memo_ext.reset(); d_mlog.reset(); d_mlog_cnt.reset(); d_mclaim.reset(); d_mstats.reset(); d_memo2.reset();
-        dt.memo = nullptr; dt.memo_mask = 0; dt.memo2 = nullptr; dt.memo2_mask = 0;
+        memo = Memo{};
+        memo.tables(dt);
     }
     void free_slots() {
         for (int i = 0; i < NSLOT; i++) { d_text[i].reset(); d_off[i].reset(); d_ext[i].reset(); d_extsp[i].reset(); }

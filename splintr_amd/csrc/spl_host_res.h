@@ -63,17 +63,18 @@ private:
     T* p_ = nullptr;
 };
 
-// One block of mapped pinned host memory (zero-filled) and the address the device sees it at.
+// One block of mapped pinned host memory (zero-filled) and the address the device sees it at.  Move-only, as DevBuf.
 template <class T> struct HostMapped {
     HostMapped() = default;
-    HostMapped(const HostMapped&) = delete;
-    HostMapped& operator=(const HostMapped&) = delete;
-    ~HostMapped() { if (h_) (void)hipHostFree(h_); }
+    HostMapped(HostMapped&& o) noexcept : h_(o.h_), d_(o.d_) { o.h_ = nullptr; o.d_ = nullptr; }
+    HostMapped& operator=(HostMapped&& o) noexcept { if (this != &o) { reset(); h_ = o.h_; d_ = o.d_; o.h_ = nullptr; o.d_ = nullptr; } return *this; }
+    ~HostMapped() { reset(); }
     T* host() const { return h_; }
     T* dev() const { return d_; }
     explicit operator bool() const { return h_ != nullptr; }
+    void reset() { if (h_) (void)hipHostFree(h_); h_ = nullptr; d_ = nullptr; }
     int alloc(size_t n, unsigned flags = hipHostMallocPortable) {
-        if (h_) { (void)hipHostFree(h_); h_ = nullptr; d_ = nullptr; }
+        reset();
         HIP_TRY(hipHostMalloc((void**)&h_, n * sizeof(T), flags));
         memset(h_, 0, n * sizeof(T));
         void* dp = nullptr;

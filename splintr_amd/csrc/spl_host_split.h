@@ -188,6 +188,9 @@ int encode_device_custom(spl_tokenizer* t, Ctx* c, const uint8_t* d_utf8, uint64
     SPL_TRY(c->d_rx_bits.grow(&c->rx_bits_cap, 2 * bw, 2 * bw + bw / 2));
     ExtIn ext;
     ext.d_starts = c->d_rx_bits.get(); ext.d_gaps = c->d_rx_bits.get() + bw;
+    // (every launch below is this call on these boundaries: only the part that runs differs)
+    LaunchReq rq{.text = d_utf8, .n_bytes = n_bytes, .doc_off = d_doc_off, .n_docs = n_docs, .flags = flags,
+                 .ids = d_ids, .ids_cap = ids_cap, .out_off = d_out_off, .stream = s, .slab = so, .ext = &ext};
     if (t->rx_device && !t->rx_image.empty()) {
         int rc = rx_ensure(t, c);
         if (rc) return rc;
@@ -197,13 +200,14 @@ int encode_device_custom(spl_tokenizer* t, Ctx* c, const uint8_t* d_utf8, uint64
         // optimistic: splitter and tile kernel go out together, ONE synchronisation to read what the splitter gave up on -- except with special
         // tokens (the literal scan's bitmap would keep the first tile pass's bits): there the splitter goes first, the tile kernel behind the check
         const bool two_phase = (flags & SPL_WITH_SPECIAL) && !t->specials.empty();
-        rc = launch_all(t, c, d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_cap, d_out_off, s, so, &ext, two_phase ? 1 : 0);
+        rq.part = two_phase ? LaunchPart::Front : LaunchPart::All;
+        rc = launch_all(t, c, rq);
         if (rc) return rc;
         uint32_t gave_up = 1;
         HIP_TRY(hipMemcpyAsync(&gave_up, c->d_rx_status.get() + c->rx_slot, 4, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         if (!gave_up && c->h_rx_bad.host()[0] == 0) {
-            if (two_phase) { rc = launch_all(t, c, d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_cap, d_out_off, s, so, &ext, 2); if (rc) return rc; HIP_TRY(hipStreamSynchronize(s)); }
+            if (two_phase) { rq.part = LaunchPart::Tiles; rc = launch_all(t, c, rq); if (rc) return rc; HIP_TRY(hipStreamSynchronize(s)); }
             return SPL_OK;
         }
         if (!gave_up) {
@@ -225,7 +229,8 @@ int encode_device_custom(spl_tokenizer* t, Ctx* c, const uint8_t* d_utf8, uint64
             if (rc) return rc;
             if (cerr != hipSuccess) return fail(SPL_EDEVICE, std::string("hipMemcpy: ") + hipGetErrorString(cerr));
             t->rx_fallbacks += n_patched;
-            rc = launch_all(t, c, d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_cap, d_out_off, s, so, &ext, 2);
+            rq.part = LaunchPart::Tiles;
+            rc = launch_all(t, c, rq);
             if (rc) return rc;
             HIP_TRY(hipStreamSynchronize(s));
             return SPL_OK;
@@ -254,7 +259,8 @@ int encode_device_custom(spl_tokenizer* t, Ctx* c, const uint8_t* d_utf8, uint64
         if (hipMemcpyAsync(d_hits.get(), hp.data(), n * 8, hipMemcpyHostToDevice, s) != hipSuccess) return fail(SPL_EDEVICE, "hipMemcpyAsync failed");
         ext.d_sp_pos = d_hits.get(); ext.d_sp_id = d_hits.get() + n; ext.n_sp = (uint32_t)n;
     }
-    rc = launch_all(t, c, d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_cap, d_out_off, s, so, &ext);
+    rq.part = LaunchPart::All;
+    rc = launch_all(t, c, rq);
     const hipError_t se = hipStreamSynchronize(s);           // (the vectors and the list die with this frame)
     if (rc) return rc;
     if (se != hipSuccess) return fail(SPL_EDEVICE, std::string("hipStreamSynchronize: ") + hipGetErrorString(se));

@@ -31,6 +31,7 @@
 
 #include "spl_common.h"
 #include "spl_lookup.h"
+#include "spl_mode.h"
 #include "spl_scan.h"
 #include "spl_scan_masks.h"
 #include "spl_scan_starts.h"
@@ -60,17 +61,7 @@ constexpr int RANK_BLK = 1024;           // positions per rank block (32 bitmap 
 #ifndef SPL_TILE_DIRECT_B
 #define SPL_TILE_DIRECT_B 864, 128
 #endif
-#ifndef SPL_DIRECT_A_MAX_BYTES
-#define SPL_DIRECT_A_MAX_BYTES (1280u * 1024u)
-#endif
-#ifndef SPL_DIRECT_MAX_MB
-#define SPL_DIRECT_MAX_MB 256
-#endif
-#ifndef SPL_QUEUE_MAX_MB
-#define SPL_QUEUE_MAX_MB 2047         /* 0: queue mode off (larger batches then run the multi-pass pipeline) */
-#endif
-constexpr uint64_t SPL_QUEUE_MAX_BYTES = (uint64_t)SPL_QUEUE_MAX_MB << 20;
-constexpr uint64_t SPL_DIRECT_MAX_BYTES = (uint64_t)SPL_DIRECT_MAX_MB << 20;   // batches up to this size: small tiles, tile-owned mode
+// (the size limits -- SPL_DIRECT_A_MAX_BYTES, SPL_DIRECT_MAX_BYTES, SPL_QUEUE_MAX_BYTES -- are spl_mode.h's)
 
 // What a tile of the tile-owned mode leaves behind for k_tile_out.
 struct TileDesc {

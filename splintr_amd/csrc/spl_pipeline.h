@@ -1,6 +1,8 @@
 // spl_pipeline.h -- spl_encode_batch's host side: lanes and chunks (lane_prepare, lane_submit), the latency path (encode_small) and
-// encode_host, which runs a batch as one chunk or as producers plus a consumer.  Needs launch_all (spl_launch.h), the host splitter and
-// rx_patch_docs (spl_host_split.h), pick_stream_beside (spl_streams.h).
+// encode_host, which runs a batch as one chunk or as producers plus a consumer.  Every device call is a LaunchReq built where it is made
+// -- which form, where the offsets also go, the completion word -- and what came of it a LaunchDone: nothing is parked in the context, so
+// an early return leaves nothing behind.  Needs launch_all (spl_launch.h), the host splitter and rx_patch_docs (spl_host_split.h),
+// pick_stream_beside (spl_streams.h).
 #pragma once
 namespace {
 
@@ -171,10 +173,16 @@ int lane_prepare(spl_tokenizer* tk, Lane& ln, const uint64_t* doc_off, uint64_t 
     return reserve(c, max_bytes, max_docs);
 }
 
-// producer: every chunk of one lane, in order (runs in the caller's thread for a single chunk)
-int lane_submit(spl_tokenizer* tk, Lane& ln, const uint8_t* utf8, const uint64_t* doc_off, uint32_t flags, bool src_pinned,
-                bool solo = false, uint32_t* ids_direct = nullptr, bool mapped = false) {
+// A batch of ONE chunk (encode_host finishes it on the compute stream itself): where the last kernel writes ids and offsets directly --
+// device pointers of the pinned result; null: the lane's buffers --, whether the tile kernel reads the text where it lies, and, back,
+// whether the offsets were written there.
+struct Solo { uint32_t* ids = nullptr; uint64_t* off = nullptr; bool mapped = false; bool off_written = false; };
+
+// producer: every chunk of one lane, in order (runs in the caller's thread for a single chunk: `one`)
+int lane_submit(spl_tokenizer* tk, Lane& ln, const uint8_t* utf8, const uint64_t* doc_off, uint32_t flags, bool src_pinned, Solo* one = nullptr) {
     Ctx* c = ln.c;
+    const bool solo = one != nullptr, mapped = solo && one->mapped;
+    uint32_t* const ids_direct = solo ? one->ids : nullptr;
     HIP_TRY(hipSetDevice(c->device));
     for (size_t k = 0; k < ln.chunks.size(); k++) {
         const Chunk& ch = ln.chunks[k];
@@ -208,14 +216,15 @@ int lane_submit(spl_tokenizer* tk, Lane& ln, const uint8_t* utf8, const uint64_t
         // ("direct_read": the one chunk of a batch whose text is pinned is not copied at all -- the tile kernel reads text and offsets over PCIe)
         const uint8_t* text_arg = c->d_text[sl].get();
         const uint64_t* off_arg = c->d_off[sl].get();
-        if (mapped && solo && nb) {
+        bool no_fuse = false;
+        if (mapped && nb) {
             void *tp = nullptr, *op = nullptr;
             HIP_TRY(hipHostGetDevicePointer(&tp, (void*)src, 0));
             HIP_TRY(hipHostGetDevicePointer(&op, rel, 0));
             text_arg = (const uint8_t*)tp; off_arg = (const uint64_t*)op;
             // (text that arrives over PCIe while the kernel runs: the tiles of the fused mode would wait for the last of it, polling -- 94 against 86 us
             //  per 1 MB call; with the text copied first it is 92 fused against 95.  profiles/r06_surface_bisect.txt)
-            c->fuse_off = true;
+            no_fuse = true;
         } else {
         if (nb) HIP_TRY(hipMemcpyAsync(c->d_text[sl].get(), src, nb, hipMemcpyHostToDevice, hs));
         HIP_TRY(hipMemcpyAsync(c->d_off[sl].get(), rel, (nd + 1) * 8, hipMemcpyHostToDevice, hs));
@@ -225,7 +234,6 @@ int lane_submit(spl_tokenizer* tk, Lane& ln, const uint8_t* utf8, const uint64_t
             HIP_TRY(hipStreamWaitEvent(w->s_cmp.get(), c->ev_h2d[sl].get(), 0));
         }
         uint64_t* oo = c->d_oo.get() + ch.oo_at;
-        if (!solo) { w->off_host = c->dh_oo + ch.oo_at; w->off_host_written = false; }
         c->solo_text = text_arg; c->solo_off = off_arg;          // (a one-chunk batch: where its tile kernel read text and offsets -- the per-document redo reads them again)
         ExtIn ext;
         if (tk->regex) {
@@ -268,6 +276,11 @@ int lane_submit(spl_tokenizer* tk, Lane& ln, const uint8_t* utf8, const uint64_t
         }
         int rc;
         const bool sp_flag = (flags & SPL_WITH_SPECIAL) && !tk->specials.empty();
+        // (the offsets also go where the host reads them: a pipeline chunk's into the lane's pinned h_oo, the one chunk's into the result)
+        LaunchReq rq{.text = text_arg, .n_bytes = nb, .doc_off = off_arg, .n_docs = nd, .flags = flags,
+                     .ids = ids_direct ? ids_direct : c->d_ids.get() + (ch.lo - ln.lo), .ids_cap = nb + 16, .out_off = oo, .stream = w->s_cmp.get(),
+                     .ext = tk->regex ? &ext : nullptr, .no_fuse = no_fuse, .off_host = solo ? one->off : c->dh_oo + ch.oo_at};
+        LaunchDone done;
         if (tk->regex && !ln.host_split && (!solo || sp_flag)) {
             // (a one-chunk batch runs optimistically instead -- splitter and tile kernel out together, one more tile pass if a document needs
             //  it: encode_host --, except with special tokens: the first tile pass would leave token bits in the bitmap the literal scan has
@@ -275,8 +288,9 @@ int lane_submit(spl_tokenizer* tk, Lane& ln, const uint8_t* utf8, const uint64_t
             // device split of a pipeline chunk, per-document fallback: the splitter first; the producer waits for it (the GPU has the
             // previous chunk's tile kernel to run meanwhile), has the documents of the listed blocks split on the host -- normally none --
             // and their bits patched, then the tile kernel follows
-            rc = launch_all(tk, c, text_arg, nb, off_arg, nd, flags, ids_direct ? ids_direct : c->d_ids.get() + (ch.lo - ln.lo), nb + 16, oo, c->s_cmp.get(),
-                            nullptr, &ext, 1);
+            // (a custom pattern has no twin: w is c here)
+            rq.part = LaunchPart::Front;
+            rc = launch_all(tk, c, rq);
             if (rc) return rc;
             HIP_TRY(hipEventRecord(c->ev_split.get(), c->s_cmp.get()));
             HIP_TRY(hipEventSynchronize(c->ev_split.get()));
@@ -290,20 +304,17 @@ int lane_submit(spl_tokenizer* tk, Lane& ln, const uint8_t* utf8, const uint64_t
                 ln.patched += n_patched;
                 c->h_rx_bad.host()[0] = 0;                          // (dealt with: the one-chunk caller looks at it again)
             }
-            rc = launch_all(tk, c, text_arg, nb, off_arg, nd, flags, ids_direct ? ids_direct : c->d_ids.get() + (ch.lo - ln.lo), nb + 16, oo, c->s_cmp.get(),
-                            nullptr, &ext, 2);
+            rq.part = LaunchPart::Tiles;
+            rc = launch_all(tk, c, rq, &done);
         } else
-            rc = launch_all(tk, w, text_arg, nb, off_arg, nd, flags, ids_direct ? ids_direct : c->d_ids.get() + (ch.lo - ln.lo),
-                            nb + 16, oo, w->s_cmp.get(), nullptr, tk->regex ? &ext : nullptr);
-        c->fuse_off = false;
+            rc = launch_all(tk, w, rq, &done);
         if (rc) return rc;
-        if (solo) break;                                   // (the batch is ONE chunk: the caller finishes on the compute stream itself)
+        if (solo) { one->off_written = done.off_host_written; break; }      // (the batch is ONE chunk: the caller finishes on the compute stream itself)
         HIP_TRY(hipEventRecord(c->ev_cmp[sl].get(), w->s_cmp.get()));
         // (the chunk's local offsets -- the last one is its token count -- are in pinned memory when the event fires: k_tile_out has written
         //  them there beside the device copy; up to round 4 an 8-byte copy fetched the count, a kernel rebased the offsets on the device and
         //  a second copy brought them back: three small operations and their launch gaps per chunk on the streams the kernels wait behind)
-        if (!w->off_host_written) HIP_TRY(hipMemcpyAsync((uint64_t*)c->h_oo.p + ch.oo_at, oo, (nd + 1) * 8, hipMemcpyDeviceToHost, w->s_cmp.get()));
-        w->off_host = nullptr;
+        if (!done.off_host_written) HIP_TRY(hipMemcpyAsync((uint64_t*)c->h_oo.p + ch.oo_at, oo, (nd + 1) * 8, hipMemcpyDeviceToHost, w->s_cmp.get()));
         HIP_TRY(hipEventRecord(c->ev_chunk[k].get(), w->s_cmp.get()));
         ln.submitted.store((uint32_t)k + 1, std::memory_order_release);
     }
@@ -346,13 +357,13 @@ int encode_small(spl_tokenizer* tk, const uint8_t* utf8, const uint64_t* doc_off
     uint32_t* const d_ids = (uint32_t*)dev_ptr_cached(c, r->ids);
     uint64_t* const d_off = (uint64_t*)dev_ptr_cached(c, r->off);
     if (!d_ids || !d_off) return fail(SPL_EDEVICE, "hipHostGetDevicePointer failed");
-    c->off_host = d_off; c->off_host_written = false;
     c->done_seq = c->done_seq + 1u ? c->done_seq + 1u : 1u;                  // (never 0: the word's resting value)
-    c->done_arm = (uint32_t*)(c->h_small.dev() + SMALL_TEXT + SMALL_OFF); c->done_armed = false;
-    rc = launch_all(tk, c, c->h_small.dev(), n_bytes, (const uint64_t*)(c->h_small.dev() + SMALL_TEXT), n_docs, flags, d_ids, n_bytes + 16, c->d_oo.get(), c->s_cmp.get());
-    const bool armed = c->done_armed, offs = c->off_host_written;
-    c->off_host = nullptr; c->done_arm = nullptr;
+    LaunchDone ld;
+    rc = launch_all(tk, c, {.text = c->h_small.dev(), .n_bytes = n_bytes, .doc_off = (const uint64_t*)(c->h_small.dev() + SMALL_TEXT), .n_docs = n_docs, .flags = flags,
+                            .ids = d_ids, .ids_cap = n_bytes + 16, .out_off = c->d_oo.get(), .stream = c->s_cmp.get(), .off_host = d_off,
+                            .done_word = (uint32_t*)(c->h_small.dev() + SMALL_TEXT + SMALL_OFF), .done_seq = c->done_seq}, &ld);
     if (rc) return rc;
+    const bool armed = ld.done_armed, offs = ld.off_host_written;
     if (!offs) HIP_TRY(hipMemcpyAsync(r->off, c->d_oo.get(), (n_docs + 1) * 8, hipMemcpyDeviceToHost, c->s_cmp.get()));
     bool seen = false;
     if (armed && offs) {
@@ -459,16 +470,15 @@ int encode_host(spl_tokenizer* tk, const uint8_t* utf8, const uint64_t* doc_off,
             // ... and the offsets into the pinned result as well: no copy back at all
             void* optr = nullptr;
             HIP_TRY(hipHostGetDevicePointer(&optr, r->off, 0));
-            c->off_host = (uint64_t*)optr; c->off_host_written = false;
             // (not with a custom pattern: the device splitter's kernels read the text as well -- in place it would cross PCIe two or three times:
             //  216 against 182 us per 1 MB call, profiles/r06_surface_bisect.txt; round 5 had it on: the 5.50 -> 4.99 GB/s of VERDICT r05)
             const bool mapped = tk->direct_read && src_pinned && ((uintptr_t)(utf8 + ch.lo) & 15) == 0 && !tk->regex;
             // (completion by k_tile_out's word in pinned memory instead of the stream synchronisation -- what the latency path does for a handful of
             //  tiles -- was measured here too: 150 us against 93 for the 1 MB batch; 1250 workgroups each pay a system-scope fence.  Not adopted.)
-            int rc = lane_submit(tk, ln, utf8, doc_off, flags, src_pinned, true, (uint32_t*)dptr, mapped);
-            c->off_host = nullptr;
+            Solo one{.ids = (uint32_t*)dptr, .off = (uint64_t*)optr, .mapped = mapped};
+            int rc = lane_submit(tk, ln, utf8, doc_off, flags, src_pinned, &one);
             if (rc) return rc;
-            if (!c->off_host_written) HIP_TRY(hipMemcpyAsync(r->off, c->d_oo.get() + ch.oo_at, (nd + 1) * 8, hipMemcpyDeviceToHost, c->s_cmp.get()));
+            if (!one.off_written) HIP_TRY(hipMemcpyAsync(r->off, c->d_oo.get() + ch.oo_at, (nd + 1) * 8, hipMemcpyDeviceToHost, c->s_cmp.get()));
             HT_T(ht2);
             HT_ACC(1, ht1, ht2);
             HIP_TRY(hipStreamSynchronize(c->s_cmp.get()));
@@ -485,9 +495,9 @@ int encode_host(spl_tokenizer* tk, const uint8_t* utf8, const uint64_t* doc_off,
                 ExtIn ext;
                 ext.d_starts = c->d_ext[0].get(); ext.d_gaps = c->d_ext[0].get() + bw;
                 ext.d_status = c->d_rx_status.get() + c->rx_slot; ext.d_status_host = c->h_rx_status.dev();
-                c->off_host = (uint64_t*)optr; c->off_host_written = false;
-                rc = launch_all(tk, c, c->solo_text, nb, c->solo_off, nd, flags, (uint32_t*)dptr, nb + 16, c->d_oo.get() + ch.oo_at, c->s_cmp.get(), nullptr, &ext, 2);
-                c->off_host = nullptr;
+                rc = launch_all(tk, c, {.text = c->solo_text, .n_bytes = nb, .doc_off = c->solo_off, .n_docs = nd, .flags = flags,
+                                        .ids = (uint32_t*)dptr, .ids_cap = nb + 16, .out_off = c->d_oo.get() + ch.oo_at, .stream = c->s_cmp.get(),
+                                        .ext = &ext, .part = LaunchPart::Tiles, .off_host = (uint64_t*)optr});
                 if (rc) return rc;
                 HIP_TRY(hipStreamSynchronize(c->s_cmp.get()));
                 ln.patched = n_patched;
@@ -505,7 +515,8 @@ int encode_host(spl_tokenizer* tk, const uint8_t* utf8, const uint64_t* doc_off,
             return SPL_OK;
         }
         // ids copied back speculatively (a guess of their number), the rest -- if any -- after the count is known
-        int rc = lane_submit(tk, ln, utf8, doc_off, flags, src_pinned, true);
+        Solo one;
+        int rc = lane_submit(tk, ln, utf8, doc_off, flags, src_pinned, &one);
         if (rc) return rc;
         const uint64_t spec = std::min<uint64_t>(r->ids_cap / 4, n_bytes);
         HIP_TRY(hipMemcpyAsync(r->off, c->d_oo.get() + ch.oo_at, (nd + 1) * 8, hipMemcpyDeviceToHost, c->s_cmp.get()));
