@@ -481,6 +481,51 @@ int spl_decode_batch_device(spl_tokenizer* t, const void* d_ids, uint64_t n_ids_
                             uint64_t* d_out_off /* [n_docs+1] */, void* hip_stream);
 uint32_t spl_max_token_bytes(const spl_tokenizer* t);   /* longest byte string any id decodes to (computed once, again after spl_add_special) */
 
+/* Where every id lies in the text spl_decode_batch_device writes for the same input: per id slot a byte span and a character span counted
+ * from its document's start, and the documents' global offsets.  A pure function of the ids -- the decode tables and a
+ * segmented running sum, no text -- so it serves what the encoder leaves and what a sampler leaves alike.  d_ids, n_ids_cap, d_ids_off,
+ * d_len, n_docs and o mean exactly what they mean for spl_decode_batch_device (CSR mode and rows mode, SPL_DECODE_I64 / _PAD_LEFT /
+ * _SKIP_SPECIAL, the clamping to n_ids_cap).  slots = n_ids_cap in CSR mode, n_docs * row_len in rows mode.
+ *
+ * For slot i of document d (a CSR range or a row): len(i) = the bytes the device decode emits for the slot (0 for an invalid, skipped or
+ * unknown one); nch(i) = how many of them START a character ((b & 0xC0) != 0x80); cont(i) = 1 if len(i) > 0 and the first byte is a
+ * continuation byte; bs(i) / cs(i) = the sums of len(j) / nch(j) over the slots j < i of the same document.
+ *   d_byte_span[i] = (bs(i), bs(i) + len(i))
+ *   d_char_span[i] = (cs(i) - (cont(i) && cs(i) > 0 ? 1 : 0), cs(i) + nch(i))
+ *   d_byte_off[d], d_char_off[d], d = 0 .. n_docs: the sums over ALL slots below the clamped start of document d (entry 0 = 0)
+ * The character start is tiktoken's decode_with_offsets rule (a token that begins inside a character starts at that character), the
+ * character end counts every character the token touches; for valid UTF-8 both index a Python str.  A zero-length slot gets the empty
+ * span at its position.  d_byte_off equals spl_decode_batch_device's d_out_off entry for entry: the byte span of slot i of document d
+ * indexes that call's d_bytes at d_byte_off[d] + start .. d_byte_off[d] + end.
+ *
+ * Checking a result: the spans describe the DECODED text.  Compare d_byte_off[d + 1] - d_byte_off[d] with the length of the text the ids
+ * came from: they differ where an encode dropped bytes (a custom pattern that leaves gaps, a vocabulary that lacks a single byte, a
+ * ByteLevel key that is not ByteLevel text), and the spans of such a document do not index the original text.
+ *
+ * Every span entry of every slot below `slots` is written exactly once; a slot at or beyond the clamped end (CSR mode: d_ids_off[n_docs]
+ * clamped to n_ids_cap) belongs to no document and gets (0, 0).  Nothing at or beyond `slots` is written.  Every one of the n_docs + 1
+ * offsets is written exactly once; n_docs == 0 writes only d_*_off[0] = 0.  Span entries are int32 pairs, or int64 pairs with
+ * SPL_SPANS_I64; int32 entries saturate at INT32_MAX (a document beyond 2^31 - 1 bytes), the u64 offsets stay exact.  d_byte_span,
+ * d_char_span and d_char_off may each be NULL (not wanted).
+ *
+ * Four launches on hip_stream, no atomics and no wait between workgroups.  Scratch: 16 bytes per 1 024 ids, grow-only, an allocation of
+ * its own; spl_decode_reserve_device sizes it together with the decode's, and a call within that size neither allocates nor synchronises.
+ * Span calls of ONE handle share that scratch: they need stream order among themselves, none with decode or encode calls beyond producer
+ * and consumer.
+ *
+ * SPL_EINVAL, with the cause in spl_last_error() and before anything touches the device: everything spl_decode_batch_device refuses for
+ * t, d_ids, n_ids_cap, d_ids_off, d_len, n_docs and o; an unknown span_flags bit; a null d_byte_off; d_byte_span or d_char_span not
+ * 16-byte aligned; a handle with a token longer than 32 767 bytes. */
+#define SPL_SPANS_I64 1u   /* span entries are int64; default int32 */
+int spl_token_spans_device(spl_tokenizer* t, const void* d_ids, uint64_t n_ids_cap,
+                           const uint64_t* d_ids_off, const int32_t* d_len, uint64_t n_docs,
+                           const spl_decode_opts* o, uint32_t span_flags,
+                           void* d_byte_span    /* [slots, 2], NULL ok */,
+                           void* d_char_span    /* [slots, 2], NULL ok */,
+                           uint64_t* d_byte_off /* [n_docs+1], required */,
+                           uint64_t* d_char_off /* [n_docs+1], NULL ok */,
+                           void* hip_stream);
+
 /* Host-side lookup of ONE id, for consumers that decode token by token on the CPU -- the streaming
  * decoders (src/core/streaming.rs, src/python/bindings.rs:465-834 take clones of Tokenizer::decoder
  * and special_tokens_decoder).  *bytes / *len = what decode_bytes emits for the id; the pointer

@@ -30,12 +30,13 @@ SYMBOLS = [
     "spl_allgather_slabs", "spl_allgather_slabs_p2p", "spl_gatherv_unpack_at", "spl_allgatherv_csr", "spl_split_host", "spl_encode_chunks_device",
     "spl_split_device", "spl_device_split_fallbacks", "spl_small_path_calls", "spl_pick_stream", "spl_memo_stats", "spl_memo_seed_stats", "spl_debug_memo_entry",
     "spl_pad_device", "spl_pack_device", "spl_window_work_bytes", "spl_window_device",
-    "spl_decode_reserve_device", "spl_decode_batch_device", "spl_max_token_bytes",
+    "spl_decode_reserve_device", "spl_decode_batch_device", "spl_max_token_bytes", "spl_token_spans_device",
 ]
 SPL_PATTERN_CUSTOM = 3
 SPL_OPT_BYTE_LEVEL = 1
 SPL_COLLATE_I64, SPL_COLLATE_PAD_LEFT, SPL_COLLATE_KEEP_TAIL, SPL_COLLATE_BOS, SPL_COLLATE_EOS = 1, 2, 4, 8, 16
 SPL_DECODE_I64, SPL_DECODE_PAD_LEFT, SPL_DECODE_SKIP_SPECIAL = 1, 2, 4
+SPL_SPANS_I64 = 1
 
 
 class SplOpts(ctypes.Structure):
@@ -170,6 +171,8 @@ def lib() -> ctypes.CDLL:
                                           ctypes.c_uint64, vp, vp]
     L.spl_max_token_bytes.restype = ctypes.c_uint32
     L.spl_max_token_bytes.argtypes = [vp]
+    L.spl_token_spans_device.argtypes = [vp, vp, ctypes.c_uint64, vp, vp, ctypes.c_uint64, ctypes.POINTER(SplDecodeOpts), ctypes.c_uint32,
+                                         vp, vp, vp, vp, vp]
     _lib = L
     return L
 

@@ -1,7 +1,7 @@
 // spl_api.hip -- the C ABI (include/splintr_hip.h): the root of the library's one HIP translation unit.  It includes the kernels
 // (spl_kernels.hip) and the host side, one file per concern and each building on the ones before it -- spl_host_res.h (resource owners,
 // pinned pool), spl_ctx.h (per-GPU context, handle, uploads), spl_streams.h (stream probe), spl_launch.h (memo, launch order, device
-// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_window_host.h, spl_decode_dev_host.h -- and holds the entry points.
+// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h -- and holds the entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -42,6 +42,7 @@ using namespace spl;
 #include "spl_collate_host.h"
 #include "spl_window_host.h"
 #include "spl_decode_dev_host.h"
+#include "spl_spans_host.h"
 
 namespace {
 // No exception crosses the C ABI: every entry point that allocates (std::bad_alloc), starts threads or grows
@@ -411,6 +412,14 @@ int spl_decode_batch_device(spl_tokenizer* t, const void* d_ids, uint64_t n_ids_
 }
 
 uint32_t spl_max_token_bytes(const spl_tokenizer* t) { return t ? max_token_bytes(t) : 0u; }
+
+int spl_token_spans_device(spl_tokenizer* t, const void* d_ids, uint64_t n_ids_cap, const uint64_t* d_ids_off, const int32_t* d_len,
+                           uint64_t n_docs, const spl_decode_opts* o, uint32_t span_flags, void* d_byte_span, void* d_char_span,
+                           uint64_t* d_byte_off, uint64_t* d_char_off, void* hip_stream) {
+    return guarded("spl_token_spans_device", [&] {
+        return token_spans_device(t, d_ids, n_ids_cap, d_ids_off, d_len, n_docs, o, span_flags, d_byte_span, d_char_span, d_byte_off,
+                                  d_char_off, (hipStream_t)hip_stream); });
+}
 
 int spl_pack_device(spl_tokenizer* t, const uint32_t* d_ids, const uint64_t* d_out_off, uint64_t n_docs, const spl_collate_opts* o,
                     void* d_rows, uint64_t rows_cap, int32_t* d_doc, int32_t* d_pos, uint64_t* d_n, void* hip_stream) {

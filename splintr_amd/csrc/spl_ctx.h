@@ -63,8 +63,10 @@ struct Ctx {
     uint32_t dec_max_id = 0;
     DevBuf<uint32_t> d_dec_sp_ids, d_dec_sp_off; uint32_t dec_n_sp = 0;   // specials beyond the vocabulary's ids
     DevBuf<uint32_t> d_dec_spbits;             // one bit per id of the dense table: only the special map holds it (SPL_DECODE_SKIP_SPECIAL)
+    DevBuf<uint16_t> d_dec_nch, d_dec_sp_nch;  // spl_token_spans_device: characters per dense id / per side-table entry (spl_k_spans.h: sn_entry)
     bool dec_uploaded = false;
     DevBuf<uint64_t> d_ddblk; uint64_t ddblk_cap = 0;   // spl_decode_batch_device: block sums, 8 bytes per 1 024 ids (grow-only; shared with nothing)
+    DevBuf<uint64_t> d_snblk; uint64_t snblk_cap = 0;   // spl_token_spans_device: block sums of bytes and of characters, 16 bytes per 1 024 ids (grow-only; shared with nothing)
     DevBuf<uint8_t> d_sp_lits;                 // uploaded lazily; invalidated by spl_add_special
     bool sp_uploaded = false;
     // workspace
@@ -408,12 +410,19 @@ int upload_decode(spl_tokenizer* tk, Ctx* t) {
         bytes.insert(bytes.end(), f->lit.begin(), f->lit.end());
     }
     sp_off.push_back((uint32_t)bytes.size());
+    // characters per id (spl_token_spans_device), from the same bytes
+    std::vector<uint16_t> nch(max_id + 1, 0), sp_nch(sp_ids.size(), 0);
+    auto entry = [&](uint32_t a, uint32_t b) { return b - a > SN_MAX_TOKEN_BYTES ? (uint16_t)0 : sn_entry(bytes.data() + a, b - a); };      // (such a handle is refused there)
+    for (uint32_t id = 0; id <= max_id; id++) nch[id] = entry(off[id], off[id + 1]);
+    for (size_t k = 0; k < sp_ids.size(); k++) sp_nch[k] = entry(sp_off[k], sp_off[k + 1]);
     HIP_TRY(hipDeviceSynchronize());
     SPL_TRY(t->d_tok_off.upload(off));
     SPL_TRY(t->d_tok_bytes.upload(bytes));
     SPL_TRY(t->d_dec_sp_ids.upload(sp_ids));
     SPL_TRY(t->d_dec_sp_off.upload(sp_off));
     SPL_TRY(t->d_dec_spbits.upload(sp_bits));
+    SPL_TRY(t->d_dec_nch.upload(nch));
+    SPL_TRY(t->d_dec_sp_nch.upload(sp_nch));
     t->dec_n_sp = (uint32_t)sp_ids.size();
     t->dec_max_id = max_id;
     t->dec_uploaded = true;

@@ -28,20 +28,27 @@ int decode_dev_prepare(spl_tokenizer* t, Ctx* c, uint64_t max_ids) {
     return c->d_ddblk.grow(&c->ddblk_cap, need, need + need / 4 + 64);
 }
 
+// spl_token_spans_device's block sums of bytes and of characters for max_ids ids (Ctx::d_snblk): two arrays of n_blk + 1 (the total behind
+// the sums) in one allocation, grow-only, shared with nothing
+int spans_scratch(Ctx* c, uint64_t max_ids) {
+    const uint64_t need = 2 * (dd_n_blocks(max_ids, DD_BLK) + 1);
+    return c->d_snblk.grow(&c->snblk_cap, need, need + need / 4 + 128);
+}
+
 int decode_reserve_device(spl_tokenizer* t, uint64_t max_ids) {
     const std::string who = "spl_decode_reserve_device";
     if (!t) return fail(SPL_EINVAL, who + ": null handle");
     if (max_ids >= DD_MAX_IDS) return fail(SPL_EINVAL, who + ": max_ids is 2^41 or more");
-    return decode_dev_prepare(t, t->ctx[0].get(), max_ids);
+    SPL_TRY(decode_dev_prepare(t, t->ctx[0].get(), max_ids));
+    return spans_scratch(t->ctx[0].get(), max_ids);
 }
 
-int decode_batch_device(spl_tokenizer* t, const void* d_ids, uint64_t n_ids_cap, const uint64_t* d_ids_off, const int32_t* d_len,
-                        uint64_t n_docs, const spl_decode_opts* o, uint8_t* d_bytes, uint64_t bytes_capacity, uint64_t* d_out_off,
-                        hipStream_t st) {
-    const std::string who = "spl_decode_batch_device";
+// What spl_decode_batch_device and spl_token_spans_device refuse about their INPUT (the ids, their offsets or lengths, the options), in
+// the decode's order; *slots_out = the slots the grid covers.  The handle and the device are not touched.
+int decode_dev_check_in(const std::string& who, const spl_tokenizer* t, const void* d_ids, uint64_t n_ids_cap, const uint64_t* d_ids_off,
+                        const int32_t* d_len, uint64_t n_docs, const spl_decode_opts* o, uint64_t* slots_out) {
     if (!t) return fail(SPL_EINVAL, who + ": null handle");
     if (!o) return fail(SPL_EINVAL, who + ": the options are null");
-    if (!d_out_off) return fail(SPL_EINVAL, who + ": d_out_off is null");
     const uint32_t have = o->struct_size;         // the caller's struct may be longer than this library's: only the fields known here are read
     if (have < sizeof(spl_decode_opts) || have > 4096)
         return fail(SPL_EINVAL, who + ": spl_decode_opts.struct_size is not set: it is shorter than the struct's three fields (12 bytes) or above 4096");
@@ -51,7 +58,7 @@ int decode_batch_device(spl_tokenizer* t, const void* d_ids, uint64_t n_ids_cap,
         snprintf(b, sizeof b, ": unknown flag bit 0x%x", o->flags & ~known);
         return fail(SPL_EINVAL, who + b);
     }
-    const bool rows = o->row_len != 0, i64 = (o->flags & SPL_DECODE_I64) != 0;
+    const bool rows = o->row_len != 0;
     if (n_docs >= (1ull << 31)) return fail(SPL_EINVAL, who + ": n_docs >= 2^31");
     if (!rows) {
         if (o->flags & SPL_DECODE_PAD_LEFT) return fail(SPL_EINVAL, who + ": SPL_DECODE_PAD_LEFT is a rows-mode flag (row_len is 0: CSR mode)");
@@ -63,18 +70,48 @@ int decode_batch_device(spl_tokenizer* t, const void* d_ids, uint64_t n_ids_cap,
     const uint64_t slots = rows ? n_docs * o->row_len : n_ids_cap;      // (n_docs < 2^31, row_len < 2^32: no overflow)
     if (slots >= DD_MAX_IDS) return fail(SPL_EINVAL, who + (rows ? ": n_docs * row_len is 2^41 or more" : ": n_ids_cap is 2^41 or more"));
     if (!d_ids && slots && n_docs) return fail(SPL_EINVAL, who + ": d_ids is null");
-    if (!d_bytes && bytes_capacity) return fail(SPL_EINVAL, who + ": d_bytes is null with bytes_capacity > 0");
-    if (col_misaligned(d_bytes, 16)) return fail(SPL_EINVAL, who + ": d_bytes is not 16-byte aligned");
+    *slots_out = slots;
+    return SPL_OK;
+}
+// ... and the last of them (the decode refuses its d_bytes between the two)
+int decode_dev_check_ids_aligned(const std::string& who, const void* d_ids, const spl_decode_opts* o) {
+    const bool i64 = (o->flags & SPL_DECODE_I64) != 0;
     if (col_misaligned(d_ids, i64 ? 32 : 16))
         return fail(SPL_EINVAL, who + (i64 ? ": d_ids is not 32-byte aligned (four int64 ids)" : ": d_ids is not 16-byte aligned (four 32-bit ids)"));
+    return SPL_OK;
+}
 
-    Ctx* c = t->ctx[0].get();
-    SPL_TRY(decode_dev_prepare(t, c, slots));
+// the kernels' view of a call's input and of the context's decode tables
+DecIn decode_dev_in(const void* d_ids, uint64_t n_ids_cap, const uint64_t* d_ids_off, const int32_t* d_len, uint64_t n_docs, const spl_decode_opts* o) {
     DecIn a{};
-    a.ids = d_ids; a.ids_off = d_ids_off; a.len = d_len; a.n_docs = n_docs; a.n_cap = rows ? 0 : n_ids_cap; a.row_len = o->row_len; a.flags = o->flags;
+    a.ids = d_ids; a.ids_off = d_ids_off; a.len = d_len; a.n_docs = n_docs; a.n_cap = o->row_len ? 0 : n_ids_cap; a.row_len = o->row_len; a.flags = o->flags;
+    return a;
+}
+DecTab decode_dev_tab(const Ctx* c) {
     DecTab tab{};
     tab.tok_off = c->d_tok_off.get(); tab.tok_bytes = c->d_tok_bytes.get(); tab.max_id = c->dec_max_id;
     tab.sp_ids = c->d_dec_sp_ids.get(); tab.sp_off = c->d_dec_sp_off.get(); tab.n_sp = c->dec_n_sp; tab.sp_bits = c->d_dec_spbits.get();
+    return tab;
+}
+
+int decode_batch_device(spl_tokenizer* t, const void* d_ids, uint64_t n_ids_cap, const uint64_t* d_ids_off, const int32_t* d_len,
+                        uint64_t n_docs, const spl_decode_opts* o, uint8_t* d_bytes, uint64_t bytes_capacity, uint64_t* d_out_off,
+                        hipStream_t st) {
+    const std::string who = "spl_decode_batch_device";
+    if (!t) return fail(SPL_EINVAL, who + ": null handle");
+    if (!o) return fail(SPL_EINVAL, who + ": the options are null");
+    if (!d_out_off) return fail(SPL_EINVAL, who + ": d_out_off is null");
+    uint64_t slots = 0;
+    SPL_TRY(decode_dev_check_in(who, t, d_ids, n_ids_cap, d_ids_off, d_len, n_docs, o, &slots));
+    if (!d_bytes && bytes_capacity) return fail(SPL_EINVAL, who + ": d_bytes is null with bytes_capacity > 0");
+    if (col_misaligned(d_bytes, 16)) return fail(SPL_EINVAL, who + ": d_bytes is not 16-byte aligned");
+    SPL_TRY(decode_dev_check_ids_aligned(who, d_ids, o));
+    const bool i64 = (o->flags & SPL_DECODE_I64) != 0;
+
+    Ctx* c = t->ctx[0].get();
+    SPL_TRY(decode_dev_prepare(t, c, slots));
+    const DecIn a = decode_dev_in(d_ids, n_ids_cap, d_ids_off, d_len, n_docs, o);
+    const DecTab tab = decode_dev_tab(c);
     const uint64_t n_blk = dd_n_blocks(slots, DD_BLK);
     const dim3 grid((uint32_t)std::min<uint64_t>(n_blk, 0x7FFFFFFFull)), wg(DD_NT);
     uint64_t* blk = c->d_ddblk.get();

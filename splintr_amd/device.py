@@ -278,6 +278,59 @@ def decode_rows_device(tok: Tokenizer, rows: torch.Tensor, lengths: Optional[tor
     return _decode_call(tok, rows, 0, None, lengths, n_docs, _ffi.SplDecodeOpts(flags, row_len), max_bytes)
 
 
+# ---------------------------------------------------------------------------------------------- token spans (byte and character offsets per id)
+def _span_dtype(dtype) -> int:
+    if dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"dtype must be torch.int32 or torch.int64, not {dtype}")
+    return _ffi.SPL_SPANS_I64 if dtype == torch.int64 else 0
+
+
+def _spans_call(tok: Tokenizer, ids: torch.Tensor, n_ids_cap: int, offsets, lengths, n_docs: int, o, slots: int, chars: bool, dtype):
+    dev = ids.device
+    new = lambda *shape, dt: torch.empty(*shape, dtype=dt, device=dev)          # (every entry is written by the kernels)
+    byte_span = new(slots, 2, dt=dtype)
+    char_span = new(slots, 2, dt=dtype) if chars else None
+    byte_off = new(n_docs + 1, dt=torch.int64)
+    char_off = new(n_docs + 1, dt=torch.int64) if chars else None
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    rc = _ffi.lib().spl_token_spans_device(tok.handle, ptr(ids), n_ids_cap, ptr(offsets), ptr(lengths), n_docs, ctypes.byref(o),
+                                           _span_dtype(dtype), ptr(byte_span), ptr(char_span), byte_off.data_ptr(), ptr(char_off),
+                                           torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise (ValueError if rc == -1 else RuntimeError)(f"spl_token_spans_device failed ({rc}): {_ffi.last_error()}")
+    return byte_span, char_span, byte_off, char_off
+
+
+def spans_device(tok: Tokenizer, ids: torch.Tensor, offsets: torch.Tensor, *, chars: bool = True, dtype=torch.int32,
+                 skip_special_tokens: bool = False):
+    """Where every id of a CSR in HBM (decode_device's input: what encode_device leaves) lies in the text decode_device writes for it, on
+    torch's current stream (spl_token_spans_device); nothing synchronises.  Returns (byte_span [ids.numel(), 2], char_span or None,
+    byte_off int64 [n_docs + 1], char_off or None): a span counts from its document's start -- bytes, and characters by tiktoken's
+    decode_with_offsets rule (str indices for valid UTF-8) -- and byte_off is decode_device's out_off, entry for entry.  Slots at or
+    beyond offsets[-1] hold (0, 0).  The spans describe the DECODED text: where an encode dropped bytes, byte_off[d + 1] - byte_off[d]
+    differs from the text's length."""
+    _span_dtype(dtype)
+    check_decode_args(ids, offsets, rows=False)
+    flags = (_ffi.SPL_DECODE_I64 if ids.dtype == torch.int64 else 0) | (_ffi.SPL_DECODE_SKIP_SPECIAL if skip_special_tokens else 0)
+    return _spans_call(tok, ids, ids.numel(), offsets, None, offsets.shape[0] - 1, _ffi.SplDecodeOpts(flags, 0), ids.numel(), chars, dtype)
+
+
+def spans_rows_device(tok: Tokenizer, rows: torch.Tensor, lengths: Optional[torch.Tensor] = None, *, padding_side: str = "right",
+                      chars: bool = True, dtype=torch.int32, skip_special_tokens: bool = False):
+    """spans_device for rows [batch, steps] (decode_rows_device's input), one document per row: spans [batch * steps, 2] in row-major
+    order; a padding entry is a zero-length slot of its row (the empty span at its position)."""
+    _span_dtype(dtype)
+    check_decode_args(rows, None, lengths, rows=True, padding_side=padding_side)
+    flags = (_ffi.SPL_DECODE_I64 if rows.dtype == torch.int64 else 0) | (_ffi.SPL_DECODE_SKIP_SPECIAL if skip_special_tokens else 0) | \
+        (_ffi.SPL_DECODE_PAD_LEFT if padding_side == "left" else 0)
+    n_docs, row_len = int(rows.shape[0]), int(rows.shape[1])
+    if row_len == 0:                                  # (no entry anywhere: every document is empty; row_len 0 would mean CSR mode)
+        z = lambda: torch.zeros(n_docs + 1, dtype=torch.int64, device=rows.device)
+        e = lambda: torch.empty(0, 2, dtype=dtype, device=rows.device)
+        return e(), (e() if chars else None), z(), (z() if chars else None)
+    return _spans_call(tok, rows, 0, None, lengths, n_docs, _ffi.SplDecodeOpts(flags, row_len), n_docs * row_len, chars, dtype)
+
+
 class Comm:
     """One rank of the library's own RCCL communicator (include/splintr_hip.h: spl_comm_*).  The 128-byte id is
     made by rank 0 and handed to the others by whatever the caller has; `from_torch_group` uses an existing

@@ -331,6 +331,46 @@ class Tokenizer:
         n_rows = int(n[0].item())
         return rows[:n_rows], mask[:n_rows], lens[:n_rows], doc[:n_rows], start[:n_rows], row_off
 
+    def encode_batch_with_offsets(self, texts: Sequence[str], *, unit: str = "char", with_special: bool = False):
+        """Extension: encode_batch plus WHERE every token lies in its text -- (ids list[list[int]], spans list[list[(start, end)]]), a
+        span in characters (unit="char": Python str indices, Hugging Face's offset_mapping; a token that begins inside a character
+        starts at that character -- tiktoken's decode_with_offsets -- and ends behind the last character it touches) or in bytes of the
+        UTF-8 text (unit="byte": text.encode()[start:end] is the token).  The encode and the spans (splintr_amd.device.spans_device)
+        run on the device on torch's current stream; the offsets come back first (the one synchronisation), then the ids and the spans
+        of exactly the tokens there are in one copy.  ValueError naming the first document whose ids do not decode to its text (a custom
+        pattern that leaves gaps, a vocabulary that lacks a byte): its spans would not index the text."""
+        if unit not in ("char", "byte"):
+            raise ValueError(f"unit must be 'char' or 'byte', not {unit!r}")
+        import torch
+        dv, batch = self._encode_on_device(texts, with_special)
+        byte_span, char_span, byte_off, _ = dv.spans_device(self, batch.ids, batch.out_off, chars=unit == "char")
+        off = torch.stack([batch.out_off, byte_off]).cpu().numpy()
+        tok_off, got = off[0], np.diff(off[1])
+        want = np.diff(batch.host_offsets.astype(np.int64))
+        if not np.array_equal(got, want):
+            d = int(np.argmax(got != want))
+            raise ValueError(f"encode_batch_with_offsets: document {d} is {int(want[d])} bytes of UTF-8 but its ids decode to {int(got[d])}: "
+                             "the encode dropped or changed bytes, spans would not index the text")
+        n = int(tok_off[-1])
+        span = char_span if unit == "char" else byte_span
+        flat = torch.cat([batch.ids[:n].reshape(n, 1), span[:n]], dim=1).cpu().numpy()
+        ids, spans = flat[:, 0].view(np.uint32).tolist(), list(zip(flat[:, 1].tolist(), flat[:, 2].tolist()))
+        cuts = tok_off.tolist()
+        return [ids[a:b] for a, b in zip(cuts, cuts[1:])], [spans[a:b] for a, b in zip(cuts, cuts[1:])]
+
+    def decode_with_offsets(self, tokens: Sequence[int]):
+        """tiktoken's decode_with_offsets: (text, the character index at which each token starts); a token that begins inside a
+        character starts at that character.  Strict as decode (ValueError on invalid UTF-8); an id of neither map contributes nothing
+        and starts where the next token does.  The starts come from the device (splintr_amd.device.spans_rows_device, one row)."""
+        text = self.decode(tokens)
+        if not len(tokens):
+            return text, []
+        import torch
+        from . import device as dv
+        row = torch.tensor([list(tokens)], dtype=torch.int64, device=torch.device("cuda", self._device))
+        _, char_span, _, _ = dv.spans_rows_device(self, row)
+        return text, char_span[:, 0].cpu().tolist()
+
     # ------------------------------------------------------------------ decode (test helper / "next" row)
     def decode_bytes(self, tokens: Sequence[int]) -> bytes:
         """src/python/bindings.rs:313-315."""
