@@ -326,6 +326,68 @@ int spl_pack_device(spl_tokenizer* t, const uint32_t* d_ids, const uint64_t* d_o
                     const spl_collate_opts* o, void* d_rows /* [rows_cap*row_len] */, uint64_t rows_cap,
                     int32_t* d_doc /* NULL ok */, int32_t* d_pos /* NULL ok */, uint64_t* d_n /* [2] */, void* hip_stream);
 
+/* PAIRS: two CSRs joined into one row per pair of documents -- what a cross-encoder, a reranker, an NLI / QA model or an "instruction +
+ * input" template reads, and what Hugging Face tokenizers call text_pair, with token_type_ids and the longest_first / only_first /
+ * only_second truncation strategies.  The reference has no counterpart, as for pad and pack; the same conventions hold: one launch, fully
+ * asynchronous on `hip_stream`, nothing allocated, nothing synchronised, the handle used only for its device, ANY CSRs in device memory,
+ * ids as bit patterns (SPL_COLLATE_I64 zero-extends).  The two texts are encoded SEPARATELY (joining the strings first changes the
+ * tokens at the seam), and a document that many pairs name -- one query against a thousand candidates -- is encoded once and read by each.
+ *
+ * Offsets   document i of a side is ids[off[i] .. off[i + 1]), i < n; the offsets are ABSOLUTE into that side's ids array and off[0] need
+ *           not be 0.  The two sides may therefore be two slices of ONE encode result of n_a + n_b documents: d_a_ids = d_b_ids = its
+ *           d_ids, d_a_off = its d_out_off, d_b_off = its d_out_off + n_a -- one encode launch for both sides.
+ * Pairs     pair p takes document ia = d_a_idx ? d_a_idx[p] : p of A and ib = d_b_idx ? d_b_idx[p] : p of B (d_a_idx / d_b_idx
+ *           [n_pairs], device memory).  An index that is negative, or at or beyond its side's document count, names an EMPTY document
+ *           for that pair, and d_status[0] is set to 1 (a plain store of 1; the caller clears the word before the call and a call without
+ *           such an index leaves it alone).  Nothing is read out of range.
+ * Row       k = n_prefix + n_middle + n_suffix, B = row_len - k (the budget of the two documents together).  Row p is
+ *           prefix + A' + middle + B' + suffix, then pad_id -- padding on the right, or on the left with SPL_COLLATE_PAD_LEFT.  The
+ *           fixed segments (HOST arrays in the options, passed to the kernel by value) are on every row and never cut away:
+ *           [CLS] a [SEP] b [SEP] is prefix = {CLS}, middle = {SEP}, suffix = {SEP}; RoBERTa's <s> a </s></s> b </s> has a middle of two ids.
+ * Cut       la, lb = the two documents' lengths; a', b' = the ids kept.  la + lb <= B: both whole.  Otherwise, by `trunc`:
+ *             SPL_PAIR_ONLY_SECOND    a' = min(la, B), b' = min(lb, B - a')
+ *             SPL_PAIR_ONLY_FIRST     b' = min(lb, B), a' = min(la, B - b')
+ *             SPL_PAIR_LONGEST_FIRST  Hugging Face's sequential rule: while a' + b' > B remove one id from the longer side, from B on a
+ *                                     tie.  Evaluated in closed form, with hA = ceil(B / 2) and hB = floor(B / 2): la < hA gives
+ *                                     (la, B - la); otherwise lb <= hB gives (B - lb, lb); otherwise (hA, hB).
+ *           A' is the HEAD of document ia (its first a' ids), with SPL_PAIR_KEEP_TAIL_A its tail (its last a'); B' likewise with _B.
+ * Outputs   every output is optional (NULL: not wanted) except d_rows; every element of every array that is given is written and
+ *           nothing is written at or beyond n_pairs rows.  d_rows[p, c]: the row.  d_mask[p, c] = 1 where the entry is not padding.
+ *           d_type[p, c] = 0 over prefix + A' + middle, 1 over B' + suffix, 0 on padding (BERT's token_type_ids).  d_special[p, c] = 1
+ *           on the entries of the fixed segments and on padding, 0 on ids that come from a document (Hugging Face's special_tokens_mask
+ *           after padding).  d_len[p] = k + a' + b'.  d_kept[2p], d_kept[2p + 1] = a', b': compare them with the documents' lengths to
+ *           see what was truncated.  n_pairs == 0: nothing to do.
+ *
+ * SPL_EINVAL, with the cause in spl_last_error() and before anything touches the handle or the device: a null handle, null options, a
+ * null d_rows, d_a_off, d_b_off or d_status (always), null d_a_ids or d_b_ids with n_pairs > 0; a struct_size shorter than the struct
+ * or above 4096 (a longer struct up to that is accepted, its tail ignored); an unknown flag bit; SPL_COLLATE_KEEP_TAIL, _BOS or _EOS
+ * (the fixed segments and SPL_PAIR_KEEP_TAIL_A / _B take their place); trunc > 2; a segment count above SPL_PAIR_MAX_FIXED; row_len == 0
+ * or row_len < k; n_a, n_b or n_pairs >= 2^31; a NULL index array with n_pairs above that side's document count; n_pairs * row_len beyond
+ * 2^63; d_rows, d_len or d_kept not 16-byte aligned; d_mask, d_type, d_special, d_a_idx or d_b_idx not 4-byte aligned. */
+#define SPL_PAIR_MAX_FIXED   32u    /* ids per fixed segment */
+#define SPL_PAIR_KEEP_TAIL_A 32u    /* truncation drops the FRONT of side A (default: the head is kept) */
+#define SPL_PAIR_KEEP_TAIL_B 64u
+/* also accepted: SPL_COLLATE_I64, SPL_COLLATE_PAD_LEFT (same values, same meaning) */
+#define SPL_PAIR_LONGEST_FIRST 0u
+#define SPL_PAIR_ONLY_FIRST    1u
+#define SPL_PAIR_ONLY_SECOND   2u
+
+typedef struct spl_pair_opts {
+    uint32_t struct_size;                 /* sizeof the struct as the CALLER was compiled: versioned exactly like spl_collate_opts */
+    uint32_t flags, row_len, pad_id, trunc;
+    uint32_t n_prefix, n_middle, n_suffix;          /* each 0 .. SPL_PAIR_MAX_FIXED */
+    uint32_t prefix[32], middle[32], suffix[32];    /* HOST values, passed to the kernel by value */
+} spl_pair_opts;
+
+int spl_pair_device(spl_tokenizer* t,
+                    const uint32_t* d_a_ids, const uint64_t* d_a_off, uint64_t n_a,
+                    const uint32_t* d_b_ids, const uint64_t* d_b_off, uint64_t n_b,
+                    const int32_t* d_a_idx /* [n_pairs], NULL: identity */, const int32_t* d_b_idx /* same */,
+                    uint64_t n_pairs, const spl_pair_opts* o,
+                    void* d_rows /* [n_pairs*row_len] */, uint8_t* d_mask, uint8_t* d_type, uint8_t* d_special,
+                    int32_t* d_len /* [n_pairs] */, int32_t* d_kept /* [n_pairs*2] */,
+                    uint32_t* d_status /* one word, cleared by the caller */, void* hip_stream);
+
 /* SLIDING WINDOWS over the CSR: every document alone and complete, as rows of row_len that overlap by `overlap` ids -- the one
  * per-document layout that loses nothing (pad mode truncates, pack mode joins documents), and what Hugging Face tokenizers call
  * return_overflowing_tokens with stride = overlap.  The reference has no counterpart, as for pad and pack; the same conventions hold:

@@ -29,12 +29,14 @@ SYMBOLS = [
     "spl_comm_unique_id", "spl_comm_create", "spl_comm_destroy", "spl_comm_rank", "spl_comm_world",
     "spl_allgather_slabs", "spl_allgather_slabs_p2p", "spl_gatherv_unpack_at", "spl_allgatherv_csr", "spl_split_host", "spl_encode_chunks_device",
     "spl_split_device", "spl_device_split_fallbacks", "spl_small_path_calls", "spl_pick_stream", "spl_memo_stats", "spl_memo_seed_stats", "spl_debug_memo_entry",
-    "spl_pad_device", "spl_pack_device", "spl_window_work_bytes", "spl_window_device",
+    "spl_pad_device", "spl_pack_device", "spl_pair_device", "spl_window_work_bytes", "spl_window_device",
     "spl_decode_reserve_device", "spl_decode_batch_device", "spl_max_token_bytes", "spl_token_spans_device",
 ]
 SPL_PATTERN_CUSTOM = 3
 SPL_OPT_BYTE_LEVEL = 1
 SPL_COLLATE_I64, SPL_COLLATE_PAD_LEFT, SPL_COLLATE_KEEP_TAIL, SPL_COLLATE_BOS, SPL_COLLATE_EOS = 1, 2, 4, 8, 16
+SPL_PAIR_MAX_FIXED, SPL_PAIR_KEEP_TAIL_A, SPL_PAIR_KEEP_TAIL_B = 32, 32, 64
+SPL_PAIR_LONGEST_FIRST, SPL_PAIR_ONLY_FIRST, SPL_PAIR_ONLY_SECOND = 0, 1, 2
 SPL_DECODE_I64, SPL_DECODE_PAD_LEFT, SPL_DECODE_SKIP_SPECIAL = 1, 2, 4
 SPL_SPANS_I64 = 1
 
@@ -54,6 +56,18 @@ class SplCollateOpts(ctypes.Structure):
 
     def __init__(self, flags=0, row_len=0, pad_id=0, bos_id=0, eos_id=0):
         super().__init__(ctypes.sizeof(SplCollateOpts), flags, row_len, pad_id, bos_id, eos_id)
+
+
+class SplPairOpts(ctypes.Structure):
+    """spl_pair_opts (include/splintr_hip.h): what spl_pair_device is told about a row -- the three fixed segments are HOST values."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("row_len", ctypes.c_uint32), ("pad_id", ctypes.c_uint32),
+                ("trunc", ctypes.c_uint32), ("n_prefix", ctypes.c_uint32), ("n_middle", ctypes.c_uint32), ("n_suffix", ctypes.c_uint32),
+                ("prefix", ctypes.c_uint32 * 32), ("middle", ctypes.c_uint32 * 32), ("suffix", ctypes.c_uint32 * 32)]
+
+    def __init__(self, flags=0, row_len=0, pad_id=0, trunc=0, prefix=(), middle=(), suffix=()):
+        seg = ctypes.c_uint32 * 32
+        super().__init__(ctypes.sizeof(SplPairOpts), flags, row_len, pad_id, trunc, len(prefix), len(middle), len(suffix),
+                         seg(*prefix[:32]), seg(*middle[:32]), seg(*suffix[:32]))
 
 
 class SplDecodeOpts(ctypes.Structure):
@@ -162,6 +176,8 @@ def lib() -> ctypes.CDLL:
                                      u64p, u64p, vp]
     L.spl_pad_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.POINTER(SplCollateOpts), vp, vp, vp, vp]
     L.spl_pack_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.POINTER(SplCollateOpts), vp, ctypes.c_uint64, vp, vp, vp, vp]
+    L.spl_pair_device.argtypes = [vp, vp, vp, ctypes.c_uint64, vp, vp, ctypes.c_uint64, vp, vp, ctypes.c_uint64, ctypes.POINTER(SplPairOpts),
+                                  vp, vp, vp, vp, vp, vp, vp, vp]
     L.spl_window_work_bytes.restype = ctypes.c_uint64
     L.spl_window_work_bytes.argtypes = [ctypes.c_uint64]
     L.spl_window_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.POINTER(SplCollateOpts), ctypes.c_uint32, vp, ctypes.c_uint64,

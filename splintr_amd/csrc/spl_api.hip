@@ -1,7 +1,7 @@
 // spl_api.hip -- the C ABI (include/splintr_hip.h): the root of the library's one HIP translation unit.  It includes the kernels
 // (spl_kernels.hip) and the host side, one file per concern and each building on the ones before it -- spl_host_res.h (resource owners,
 // pinned pool), spl_ctx.h (per-GPU context, handle, uploads), spl_streams.h (stream probe), spl_launch.h (memo, launch order, device
-// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h -- and holds the entry points.
+// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_pair_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h -- and holds the entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -40,6 +40,7 @@ using namespace spl;
 #include "spl_decode_host.h"
 #include "spl_collective.h"
 #include "spl_collate_host.h"
+#include "spl_pair_host.h"
 #include "spl_window_host.h"
 #include "spl_decode_dev_host.h"
 #include "spl_spans_host.h"
@@ -425,6 +426,15 @@ int spl_pack_device(spl_tokenizer* t, const uint32_t* d_ids, const uint64_t* d_o
                     void* d_rows, uint64_t rows_cap, int32_t* d_doc, int32_t* d_pos, uint64_t* d_n, void* hip_stream) {
     return guarded("spl_pack_device", [&] {
         return pack_device(t, d_ids, d_out_off, n_docs, o, d_rows, rows_cap, d_doc, d_pos, d_n, (hipStream_t)hip_stream); });
+}
+
+int spl_pair_device(spl_tokenizer* t, const uint32_t* d_a_ids, const uint64_t* d_a_off, uint64_t n_a, const uint32_t* d_b_ids,
+                    const uint64_t* d_b_off, uint64_t n_b, const int32_t* d_a_idx, const int32_t* d_b_idx, uint64_t n_pairs,
+                    const spl_pair_opts* o, void* d_rows, uint8_t* d_mask, uint8_t* d_type, uint8_t* d_special, int32_t* d_len,
+                    int32_t* d_kept, uint32_t* d_status, void* hip_stream) {
+    return guarded("spl_pair_device", [&] {
+        return pair_device(t, d_a_ids, d_a_off, n_a, d_b_ids, d_b_off, n_b, d_a_idx, d_b_idx, n_pairs, o, d_rows, d_mask, d_type, d_special,
+                           d_len, d_kept, d_status, (hipStream_t)hip_stream); });
 }
 
 uint64_t spl_window_work_bytes(uint64_t n_docs) { return window_work_bytes(n_docs); }

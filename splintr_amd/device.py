@@ -183,6 +183,122 @@ def window_device(tok: Tokenizer, batch: DeviceBatch, max_length: int, *, overla
     return rows, mask, lens, row_doc, row_start, row_off, n
 
 
+# ---------------------------------------------------------------------------------------------- pairs: two CSRs, one row per pair
+_TRUNCATION = {"longest_first": _ffi.SPL_PAIR_LONGEST_FIRST, "only_first": _ffi.SPL_PAIR_ONLY_FIRST, "only_second": _ffi.SPL_PAIR_ONLY_SECOND}
+
+
+def _segment(name: str, ids) -> Tuple[int, ...]:
+    if isinstance(ids, (str, bytes)) or not isinstance(ids, (list, tuple)):
+        raise ValueError(f"{name} must be a list or tuple of ids, not {type(ids).__name__}")
+    if len(ids) > _ffi.SPL_PAIR_MAX_FIXED:
+        raise ValueError(f"{name} holds {len(ids)} ids: a fixed segment holds at most {_ffi.SPL_PAIR_MAX_FIXED}")
+    for v in ids:
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < (1 << 32):
+            raise ValueError(f"every id of {name} must be an integer that fits 32 bits, not {v!r}")
+    return tuple(int(v) for v in ids)
+
+
+def _pair_opts(row_len: int, pad_id: int, prefix, middle, suffix, truncation: str, truncation_side_a: str, truncation_side_b: str,
+               padding_side: str, dtype):
+    """spl_pair_opts for one call; ValueError for what the Python surface can refuse by itself."""
+    if dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"dtype must be torch.int32 or torch.int64, not {dtype}")
+    if truncation not in _TRUNCATION:
+        raise ValueError(f"truncation must be 'longest_first', 'only_first' or 'only_second', not {truncation!r}")
+    flags = (_ffi.SPL_COLLATE_I64 if dtype == torch.int64 else 0) | \
+        (_ffi.SPL_COLLATE_PAD_LEFT if _side("padding_side", padding_side) else 0) | \
+        (_ffi.SPL_PAIR_KEEP_TAIL_A if _side("truncation_side_a", truncation_side_a) else 0) | \
+        (_ffi.SPL_PAIR_KEEP_TAIL_B if _side("truncation_side_b", truncation_side_b) else 0)
+    if isinstance(pad_id, bool) or not isinstance(pad_id, (int, np.integer)) or not 0 <= int(pad_id) < (1 << 32):
+        raise ValueError("pad_id must fit 32 bits")
+    segs = [_segment(n, v) for n, v in (("prefix", prefix), ("middle", middle), ("suffix", suffix))]
+    if isinstance(row_len, bool) or not isinstance(row_len, (int, np.integer)) or int(row_len) <= 0 or int(row_len) >= (1 << 32):
+        raise ValueError("the row length must be in 1 .. 2**32 - 1")
+    if int(row_len) < sum(map(len, segs)):
+        raise ValueError(f"the row length {int(row_len)} is smaller than the {sum(map(len, segs))} ids of prefix + middle + suffix every row holds")
+    return _ffi.SplPairOpts(flags, int(row_len), int(pad_id), _TRUNCATION[truncation], *segs)
+
+
+def check_pair_args(row_len: int, pad_id: int, prefix=(), middle=(), suffix=(), truncation: str = "longest_first",
+                    truncation_side_a: str = "right", truncation_side_b: str = "right", padding_side: str = "right",
+                    dtype=torch.int32) -> None:
+    """ValueError for a dtype, truncation or side string, id, fixed segment or row length that pair_device would refuse -- for callers
+    that want to know before they put a batch on the device."""
+    _pair_opts(row_len, pad_id, prefix, middle, suffix, truncation, truncation_side_a, truncation_side_b, padding_side, dtype)
+
+
+def _pair_index(name: str, index, dev) -> Optional[torch.Tensor]:
+    if index is None:
+        return None
+    if not isinstance(index, torch.Tensor):
+        index = torch.as_tensor(np.asarray(index, dtype=np.int64).astype(np.int32), device=dev)
+    if index.dtype != torch.int32 or index.dim() != 1 or not index.is_contiguous() or index.device != dev:
+        raise ValueError(f"{name} must be a contiguous int32 tensor of rank 1 on the device of the ids (or a sequence of integers)")
+    return index
+
+
+def pair_csr_device(tok: Tokenizer, a_ids: torch.Tensor, a_off: torch.Tensor, n_a: int, b_ids: torch.Tensor, b_off: torch.Tensor,
+                    n_b: int, max_length: int, *, pad_id: int, prefix=(), middle=(), suffix=(), a_index=None, b_index=None,
+                    truncation: str = "longest_first", truncation_side_a: str = "right", truncation_side_b: str = "right",
+                    padding_side: str = "right", dtype: torch.dtype = torch.int32):
+    """pair_device's low-level form: each side is (ids int32 [capacity], offsets int64 [at least n + 1], n documents), the offsets
+    ABSOLUTE into ids and offsets[0] any value -- so the two sides may be two slices of ONE encode result: a = (ids, out_off, n_a),
+    b = (ids, out_off[n_a:], n_b).  Same return as pair_device."""
+    o = _pair_opts(max_length, pad_id, prefix, middle, suffix, truncation, truncation_side_a, truncation_side_b, padding_side, dtype)
+    n_a, n_b = int(n_a), int(n_b)
+    for name, ids, off, n in (("a", a_ids, a_off, n_a), ("b", b_ids, b_off, n_b)):
+        if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or ids.dim() != 1 or not ids.is_contiguous():
+            raise ValueError(f"{name}_ids must be a contiguous int32 tensor of rank 1")
+        if not isinstance(off, torch.Tensor) or off.dtype != torch.int64 or off.dim() != 1 or not off.is_contiguous() or \
+                n < 0 or off.shape[0] < n + 1:
+            raise ValueError(f"{name}_off must be a contiguous int64 tensor of at least n_{name} + 1 entries")
+        if not ids.is_cuda or off.device != ids.device:
+            raise ValueError(f"{name}_ids and {name}_off must be on one GPU")
+    dev = a_ids.device
+    if b_ids.device != dev:
+        raise ValueError("the two sides must be on one GPU")
+    a_index, b_index = _pair_index("a_index", a_index, dev), _pair_index("b_index", b_index, dev)
+    if a_index is not None and b_index is not None and a_index.shape[0] != b_index.shape[0]:
+        raise ValueError(f"a_index names {a_index.shape[0]} pairs, b_index {b_index.shape[0]}")
+    if a_index is None and b_index is None and n_a != n_b:
+        raise ValueError(f"without an index pair i is (a_i, b_i): the sides must hold equally many documents, not {n_a} and {n_b}")
+    n_pairs = int(a_index.shape[0]) if a_index is not None else int(b_index.shape[0]) if b_index is not None else n_a
+    if (a_index is None and n_pairs > n_a) or (b_index is None and n_pairs > n_b):
+        raise ValueError(f"{n_pairs} pairs, but the side without an index holds fewer documents")
+    new = lambda *shape, dt: torch.empty(*shape, dtype=dt, device=dev)          # (every element is written by the kernel)
+    rows = new(n_pairs, o.row_len, dt=dtype)
+    mask, ttype, special = (new(n_pairs, o.row_len, dt=torch.uint8) for _ in range(3))
+    lens, kept = new(n_pairs, dt=torch.int32), new(n_pairs, 2, dt=torch.int32)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    # (d_rows may never be null; without a pair nothing is written, and an empty tensor has no address: any aligned one stands in)
+    rc = _ffi.lib().spl_pair_device(tok.handle, a_ids.data_ptr(), a_off.data_ptr(), n_a, b_ids.data_ptr(), b_off.data_ptr(), n_b,
+                                    ptr(a_index), ptr(b_index), n_pairs, ctypes.byref(o), rows.data_ptr() if n_pairs else status.data_ptr(),
+                                    ptr(mask), ptr(ttype), ptr(special), ptr(lens), ptr(kept), status.data_ptr(),
+                                    torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise (ValueError if rc == -1 else RuntimeError)(f"spl_pair_device failed ({rc}): {_ffi.last_error()}")
+    return rows, mask, ttype, special, lens, kept, status
+
+
+def pair_device(tok: Tokenizer, batch_a: DeviceBatch, batch_b: DeviceBatch, max_length: int, *, pad_id: int, prefix=(), middle=(),
+                suffix=(), a_index=None, b_index=None, truncation: str = "longest_first", truncation_side_a: str = "right",
+                truncation_side_b: str = "right", padding_side: str = "right", dtype: torch.dtype = torch.int32):
+    """Two CSRs (encode_device on each batch; batch_b may be batch_a itself) as ONE ROW PER PAIR, one launch on torch's current stream
+    (spl_pair_device): row p = prefix + A' + middle + B' + suffix padded with pad_id, where A' / B' are document a_index[p] of batch_a
+    and b_index[p] of batch_b (int32 device tensors or sequences; None: document p) cut to max_length - len(prefix + middle + suffix)
+    ids together -- "longest_first" (Hugging Face's rule: one id at a time from the longer side, from B on a tie), "only_first" or
+    "only_second"; truncation_side_a / _b "right" keeps that side's head, "left" its tail.  The fixed segments are never cut away:
+    BERT's [CLS] a [SEP] b [SEP] is prefix=[cls], middle=[sep], suffix=[sep].  Returns (input_ids [n_pairs, L], attention_mask uint8,
+    token_type_ids uint8 (0 over prefix + A' + middle, 1 over B' + suffix, 0 on padding), special_tokens_mask uint8 (1 on the fixed
+    segments and on padding), lengths int32 [n_pairs], kept int32 [n_pairs, 2] (the ids of each side that are in the row), status int32
+    [1] (1: an index named no document -- that side of the pair is empty)); all device tensors, nothing synchronises."""
+    return pair_csr_device(tok, batch_a.ids, batch_a.out_off, batch_a.n_docs, batch_b.ids, batch_b.out_off, batch_b.n_docs, max_length,
+                           pad_id=pad_id, prefix=prefix, middle=middle, suffix=suffix, a_index=a_index, b_index=b_index,
+                           truncation=truncation, truncation_side_a=truncation_side_a, truncation_side_b=truncation_side_b,
+                           padding_side=padding_side, dtype=dtype)
+
+
 # ---------------------------------------------------------------------------------------------- device-resident decode
 def _decode_error(rc: int) -> Exception:
     return (ValueError if rc == -1 else RuntimeError)(f"spl_decode_batch_device failed ({rc}): {_ffi.last_error()}")

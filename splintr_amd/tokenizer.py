@@ -331,6 +331,49 @@ class Tokenizer:
         n_rows = int(n[0].item())
         return rows[:n_rows], mask[:n_rows], lens[:n_rows], doc[:n_rows], start[:n_rows], row_off
 
+    def encode_batch_pairs(self, texts_a: Sequence[str], texts_b: Sequence[str], max_length: int, *, pad_id: int, cross: bool = False,
+                           a_index=None, b_index=None, with_special: bool = False, prefix=(), middle=(), suffix=(),
+                           truncation: str = "longest_first", truncation_side_a: str = "right", truncation_side_b: str = "right",
+                           padding_side: str = "right", dtype=None, check: bool = False):
+        """Extension: PAIRS of texts as one row each ON THE GPU (Hugging Face's text_pair) -- row p = prefix + A' + middle + B' + suffix
+        padded to max_length, the two texts encoded SEPARATELY (joining the strings first changes the tokens at the seam) and cut to the
+        row by `truncation` ("longest_first", "only_first", "only_second"; the fixed segments are never cut away).  texts_a + texts_b
+        are ONE device batch and one encode; one more launch (splintr_amd.device.pair_device) builds the rows from its two slices.  By
+        default pair i = (texts_a[i], texts_b[i]) and the two lists must be equally long; cross=True builds the whole len(a) x len(b)
+        grid, row i * len(b) + j = (a_i, b_j) -- a query is encoded once however many candidates it meets; a_index / b_index (int32
+        device tensors or sequences) name each pair's texts themselves.  Returns (input_ids [n_pairs, max_length], attention_mask uint8,
+        token_type_ids uint8, special_tokens_mask uint8, lengths int32 [n_pairs], kept int32 [n_pairs, 2], status int32 [1]), torch
+        tensors on this tokenizer's device; nothing synchronises.  An index that names no text gives an empty side and status[0] = 1;
+        check=True reads status (ONE synchronisation) and raises IndexError instead."""
+        import torch
+        from . import device as dv
+        dtype = torch.int32 if dtype is None else dtype
+        dv.check_pair_args(max_length, pad_id, prefix, middle, suffix, truncation, truncation_side_a, truncation_side_b, padding_side,
+                           dtype)                    # (before anything goes to the device)
+        for name, texts in (("texts_a", texts_a), ("texts_b", texts_b)):
+            if isinstance(texts, (str, bytes)) or not hasattr(texts, "__len__"):
+                raise ValueError(f"{name} must be a sequence of str, not {type(texts).__name__}")
+        n_a, n_b = len(texts_a), len(texts_b)
+        if cross and (a_index is not None or b_index is not None):
+            raise ValueError("cross=True builds both index arrays itself: give it, or a_index / b_index, not both")
+        if not cross and a_index is None and b_index is None and n_a != n_b:
+            raise ValueError(f"pair i is (texts_a[i], texts_b[i]): the lists must be equally long, not {n_a} and {n_b} "
+                             "(cross=True pairs every a with every b; a_index / b_index name the pairs)")
+        if cross and n_a * n_b >= (1 << 31):
+            raise ValueError("cross=True: the grid must hold fewer than 2**31 pairs")
+        dv, batch = self._encode_on_device(list(texts_a) + list(texts_b), with_special)
+        dev = batch.ids.device
+        if cross:                                    # (made on the device: nothing is copied, nothing synchronises)
+            a_index = torch.arange(n_a, dtype=torch.int32, device=dev).repeat_interleave(n_b)
+            b_index = torch.arange(n_b, dtype=torch.int32, device=dev).repeat(n_a)
+        out = dv.pair_csr_device(self, batch.ids, batch.out_off, n_a, batch.ids, batch.out_off[n_a:], n_b, max_length, pad_id=pad_id,
+                                 prefix=prefix, middle=middle, suffix=suffix, a_index=a_index, b_index=b_index, truncation=truncation,
+                                 truncation_side_a=truncation_side_a, truncation_side_b=truncation_side_b, padding_side=padding_side,
+                                 dtype=dtype)
+        if check and int(out[-1].item()):
+            raise IndexError(f"encode_batch_pairs: an entry of a_index / b_index names no text (valid: 0 .. {n_a - 1} for a, 0 .. {n_b - 1} for b)")
+        return out
+
     def encode_batch_with_offsets(self, texts: Sequence[str], *, unit: str = "char", with_special: bool = False):
         """Extension: encode_batch plus WHERE every token lies in its text -- (ids list[list[int]], spans list[list[(start, end)]]), a
         span in characters (unit="char": Python str indices, Hugging Face's offset_mapping; a token that begins inside a character
