@@ -143,6 +143,8 @@ uint32_t spl_n_devices(const spl_tokenizer* t);
  *   "decode_chunk_ids"       >= 1024 (2^21): spl_decode_batch pipelines batches of at least three such chunks through two slots
  *   "window_totals_chunk"    1..256 (256; for tests): the span totals spl_window_device's second scan launch takes per round, so that a batch
  *                            of a few thousand documents reaches its second round
+ *   "stream_one_max"         0..1024 (64): spl_stream_decode_device takes its one-launch form up to this many sequences, the three-launch
+ *                            form beyond (0: always three; profiles/stream_decode.txt has the measured crossing)
  *   "slab_pack24"            0/1 (0): the ids of the all-gather slabs travel three bytes each; every rank alike; refused (SPL_EINVAL) when an
  *                            id of the tokenizer -- vocabulary or special token -- does not fit 24 bits
  * Unknown names and values out of range: SPL_EINVAL. */
@@ -587,6 +589,59 @@ int spl_token_spans_device(spl_tokenizer* t, const void* d_ids, uint64_t n_ids_c
                            uint64_t* d_byte_off /* [n_docs+1], required */,
                            uint64_t* d_char_off /* [n_docs+1], NULL ok */,
                            void* hip_stream);
+
+/* ONE STEP of n_seqs streaming decoders at once, everything in DEVICE memory: the reference's StreamingDecoder /
+ * ByteLevelStreamingDecoder (src/core/streaming.rs; find_valid_utf8_len and is_incomplete_utf8, src/python/bindings.rs:591-640) as the pure
+ * function  (state_in[b], ids[b, 0 .. row_len), len[b]) -> (bytes CSR, state_out[b]).  A sampler's step -- one id per live sequence, or a
+ * few under speculative decoding -- goes in as rows; only complete UTF-8 characters come out.
+ *
+ * Per sequence the stream S is the pending bytes of its state followed by the bytes spl_decode_batch_device emits in rows mode for the
+ * row's first clamp(d_len[b], 0, row_len) entries (d_len NULL: all of them): raw bytes for a ByteLevel vocabulary, the key itself for a key
+ * that is not ByteLevel text, a special id's literal; nothing for an unknown id, for a value outside 0 .. 2^32 - 1 under SPL_DECODE_I64 and
+ * for an id skipped under SPL_DECODE_SKIP_SPECIAL.  Well-formed is Unicode's table: leads C2 .. F4, the second byte narrowed after E0, ED,
+ * F0 and F4.
+ *
+ * The state word (uint64; 0 is a fresh decoder, so a reset is the caller zeroing words; every bit not named is 0):
+ *     bits 0..23  the pending bytes, first byte lowest     bits 24..25  their count     bit 26  stalled     bits 32..63  held
+ * The reference's pending_bytes is the count where the sequence is not stalled and held where it is.
+ *
+ * Hold mode (default; the reference, step for step).  A stalled sequence emits nothing, held grows by the bytes added (saturating at
+ * 2^32 - 1).  Otherwise the longest valid prefix of S is emitted; if nothing is left the state is 0; if what is left is the well-formed
+ * beginning of one character that reaches the end of S (1 to 3 bytes) it is the new pending; anything else STALLS the sequence -- stalled
+ * = 1, held = the bytes left, pending 0 -- and it never emits again, which is what the reference does (feed it a lone 0x80).
+ * SPL_STREAM_REPLACE: S is cut into units from the left -- an ASCII byte; a lead with as many following bytes as conform to its row of the
+ * table (all of them: a character, copied; the end of S first: the new pending; a non-conforming byte first: a maximal invalid subpart,
+ * emitted as EF BF BD); any other byte (EF BF BD) -- which is Python's incremental decoder with errors="replace".  Never stalls.
+ * Final -- d_final[b] != 0, or SPL_STREAM_FINAL_ALL for every sequence -- is applied behind the call's ids: a sequence that is not stalled
+ * and has pending bytes emits one EF BF BD and its state becomes 0; a stalled one emits nothing and keeps its state (the caller reads the
+ * flag; what the reference would flush is the lossy decode of the ids fed since, which the caller has).  d_len[b] == 0 without final
+ * leaves d_state_out[b] == d_state_in[b] bit for bit.
+ *
+ * Output as the device decode's: d_out_off[b] = where sequence b's bytes start, d_out_off[n_seqs] = the byte count NEEDED; bytes at or beyond
+ * bytes_capacity are dropped and nothing at or beyond min(need, capacity) is written; every offset and EVERY STATE WORD is written exactly
+ * once whatever the capacity.  The state advances even where bytes were dropped: a caller that may have to repeat a call with a larger
+ * buffer keeps d_state_in (passes another array as d_state_out).  d_state_out == d_state_in is allowed otherwise.
+ *
+ * Up to 64 sequences ("stream_one_max"; the two forms' medians cross between 64 and 80, profiles/stream_decode.txt) the call is ONE launch
+ * of one workgroup, beyond that three.  spl_stream_reserve_device uploads
+ * the decode tables (synchronises once) and sizes the scratch -- 8 bytes per sequence and 8 per 16 of them, grow-only, shared with nothing;
+ * after it a call within that size neither allocates nor synchronises.  Streaming calls of ONE handle share the scratch: they need stream
+ * order among themselves.
+ *
+ * SPL_EINVAL, with the cause in spl_last_error() and before anything touches the device: a null t, o, d_state_in, d_state_out or d_out_off;
+ * a null d_ids with n_seqs > 0; a null d_bytes with bytes_capacity > 0; struct_size below the struct's three fields or above 4096; an
+ * unknown bit in o->flags or in stream_flags; row_len == 0 (rows mode only); SPL_DECODE_PAD_LEFT; d_bytes not 16-byte aligned;
+ * n_seqs >= 2^31. */
+#define SPL_STREAM_REPLACE   1u  /* replace mode: invalid bytes leave as U+FFFD, no sequence ever stalls */
+#define SPL_STREAM_FINAL_ALL 2u  /* every sequence is final in this call */
+int spl_stream_reserve_device(spl_tokenizer* t, uint64_t max_seqs);
+int spl_stream_decode_device(spl_tokenizer* t, const void* d_ids /* [n_seqs, o->row_len] */,
+                             const int32_t* d_len /* [n_seqs], NULL: all valid */, uint64_t n_seqs,
+                             const spl_decode_opts* o, uint32_t stream_flags,
+                             const uint8_t* d_final /* [n_seqs], NULL ok */,
+                             const uint64_t* d_state_in, uint64_t* d_state_out,
+                             uint8_t* d_bytes, uint64_t bytes_capacity,
+                             uint64_t* d_out_off /* [n_seqs+1] */, void* hip_stream);
 
 /* Host-side lookup of ONE id, for consumers that decode token by token on the CPU -- the streaming
  * decoders (src/core/streaming.rs, src/python/bindings.rs:465-834 take clones of Tokenizer::decoder

@@ -31,6 +31,7 @@ SYMBOLS = [
     "spl_split_device", "spl_device_split_fallbacks", "spl_small_path_calls", "spl_pick_stream", "spl_memo_stats", "spl_memo_seed_stats", "spl_debug_memo_entry",
     "spl_pad_device", "spl_pack_device", "spl_pair_device", "spl_window_work_bytes", "spl_window_device",
     "spl_decode_reserve_device", "spl_decode_batch_device", "spl_max_token_bytes", "spl_token_spans_device",
+    "spl_stream_reserve_device", "spl_stream_decode_device",
 ]
 SPL_PATTERN_CUSTOM = 3
 SPL_OPT_BYTE_LEVEL = 1
@@ -39,6 +40,7 @@ SPL_PAIR_MAX_FIXED, SPL_PAIR_KEEP_TAIL_A, SPL_PAIR_KEEP_TAIL_B = 32, 32, 64
 SPL_PAIR_LONGEST_FIRST, SPL_PAIR_ONLY_FIRST, SPL_PAIR_ONLY_SECOND = 0, 1, 2
 SPL_DECODE_I64, SPL_DECODE_PAD_LEFT, SPL_DECODE_SKIP_SPECIAL = 1, 2, 4
 SPL_SPANS_I64 = 1
+SPL_STREAM_REPLACE, SPL_STREAM_FINAL_ALL = 1, 2
 
 
 class SplOpts(ctypes.Structure):
@@ -189,6 +191,9 @@ def lib() -> ctypes.CDLL:
     L.spl_max_token_bytes.argtypes = [vp]
     L.spl_token_spans_device.argtypes = [vp, vp, ctypes.c_uint64, vp, vp, ctypes.c_uint64, ctypes.POINTER(SplDecodeOpts), ctypes.c_uint32,
                                          vp, vp, vp, vp, vp]
+    L.spl_stream_reserve_device.argtypes = [vp, ctypes.c_uint64]
+    L.spl_stream_decode_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.POINTER(SplDecodeOpts), ctypes.c_uint32, vp, vp, vp, vp,
+                                           ctypes.c_uint64, vp, vp]
     _lib = L
     return L
 

@@ -1,7 +1,7 @@
 // spl_api.hip -- the C ABI (include/splintr_hip.h): the root of the library's one HIP translation unit.  It includes the kernels
 // (spl_kernels.hip) and the host side, one file per concern and each building on the ones before it -- spl_host_res.h (resource owners,
 // pinned pool), spl_ctx.h (per-GPU context, handle, uploads), spl_streams.h (stream probe), spl_launch.h (memo, launch order, device
-// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_pair_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h -- and holds the entry points.
+// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_pair_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h, spl_stream_host.h -- and holds the entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -44,6 +44,7 @@ using namespace spl;
 #include "spl_window_host.h"
 #include "spl_decode_dev_host.h"
 #include "spl_spans_host.h"
+#include "spl_stream_host.h"
 
 namespace {
 // No exception crosses the C ABI: every entry point that allocates (std::bad_alloc), starts threads or grows
@@ -151,6 +152,7 @@ int spl_set_option(spl_tokenizer* t, const char* name, int64_t value) {
     else if (k == "decode_chunk_ids" && value >= 1024) t->dec_chunk_ids = (uint64_t)value;
     else if (k == "sdma_d2h") t->sdma_d2h = value != 0;        // (where the HSA runtime or the device's agent cannot be found: hipMemcpyAsync, silently)
     else if (k == "window_totals_chunk" && value >= 1 && value <= (int64_t)WIN_CHUNK) t->win_chunk = (uint32_t)value;
+    else if (k == "stream_one_max" && value >= 0 && value <= (int64_t)ST_ONE_MAX) t->stream_one_max = (uint32_t)value;
     else if (k == "slab_pack24") {
         if (value && std::max(t->ht.max_id, t->max_special_id) >= (1u << 24))
             return fail(SPL_EINVAL, "slab_pack24: an id of this tokenizer does not fit three bytes (vocabulary or special-token ids >= 2^24)");
@@ -420,6 +422,19 @@ int spl_token_spans_device(spl_tokenizer* t, const void* d_ids, uint64_t n_ids_c
     return guarded("spl_token_spans_device", [&] {
         return token_spans_device(t, d_ids, n_ids_cap, d_ids_off, d_len, n_docs, o, span_flags, d_byte_span, d_char_span, d_byte_off,
                                   d_char_off, (hipStream_t)hip_stream); });
+}
+
+int spl_stream_reserve_device(spl_tokenizer* t, uint64_t max_seqs) {
+    return guarded("spl_stream_reserve_device", [&] { return stream_reserve_device(t, max_seqs); });
+}
+
+int spl_stream_decode_device(spl_tokenizer* t, const void* d_ids, const int32_t* d_len, uint64_t n_seqs, const spl_decode_opts* o,
+                             uint32_t stream_flags, const uint8_t* d_final, const uint64_t* d_state_in, uint64_t* d_state_out, uint8_t* d_bytes,
+                             uint64_t bytes_capacity, uint64_t* d_out_off, void* hip_stream) {
+    return guarded("spl_stream_decode_device", [&] {
+        return stream_decode_device(t, {.ids = d_ids, .len = d_len, .n_seqs = n_seqs, .o = o, .stream_flags = stream_flags, .fin = d_final,
+                                        .state_in = d_state_in, .state_out = d_state_out, .bytes = d_bytes, .bytes_cap = bytes_capacity,
+                                        .out_off = d_out_off, .stream = (hipStream_t)hip_stream}); });
 }
 
 int spl_pack_device(spl_tokenizer* t, const uint32_t* d_ids, const uint64_t* d_out_off, uint64_t n_docs, const spl_collate_opts* o,

@@ -447,6 +447,177 @@ def spans_rows_device(tok: Tokenizer, rows: torch.Tensor, lengths: Optional[torc
     return _spans_call(tok, rows, 0, None, lengths, n_docs, _ffi.SplDecodeOpts(flags, row_len), n_docs * row_len, chars, dtype)
 
 
+# ---------------------------------------------------------------------------------------------- batched streaming decode (per-sequence UTF-8 state)
+def _stream_mode(errors: str) -> int:
+    if errors not in ("hold", "replace"):
+        raise ValueError(f"errors must be 'hold' or 'replace', not {errors!r}")
+    return _ffi.SPL_STREAM_REPLACE if errors == "replace" else 0
+
+
+def check_stream_args(ids, lengths, state, *, errors: str = "hold", final=None, max_bytes=0, state_out=None) -> None:
+    """ValueError for a mode string, dtype, rank, shape, layout, size or device that stream_decode_device would refuse -- before anything goes
+    to the device."""
+    _stream_mode(errors)
+    _max_bytes(max_bytes)
+    if not isinstance(ids, torch.Tensor) or ids.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"the ids must be a torch tensor of dtype int32 or int64, not {getattr(ids, 'dtype', type(ids))}")
+    if ids.dim() not in (1, 2):
+        raise ValueError(f"the ids must have rank 1 ([batch]: one id per sequence) or 2 ([batch, steps]), not {ids.dim()}")
+    if not ids.is_contiguous():
+        raise ValueError("the ids must be contiguous")
+    B = int(ids.shape[0])
+    if ids.dim() == 2 and not 1 <= ids.shape[1] < (1 << 32):
+        raise ValueError("a row must hold at least one id and fewer than 2**32")
+    if B >= (1 << 31):
+        raise ValueError("the sequences must be fewer than 2**31")
+    others = []
+
+    def vec(name, t, dtypes, what):
+        if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or t.dim() != 1 or t.shape[0] != B or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {what} tensor of shape [batch]")
+        others.append((name, t))
+
+    if lengths is not None:
+        vec("lengths", lengths, (torch.int32,), "int32")
+    vec("state", state, (torch.int64,), "int64")
+    if state_out is not None:
+        vec("state_out", state_out, (torch.int64,), "int64")
+    if final is not None and not isinstance(final, bool):
+        vec("final", final, (torch.uint8, torch.bool), "uint8 or bool")
+    if not ids.is_cuda:
+        raise ValueError("the ids must be on a GPU (the device-side streaming decode takes no host tensor)")
+    for name, t in others:
+        if t.device != ids.device:
+            raise ValueError(f"{name} must be on the device of the ids")
+
+
+def stream_reserve(tok: Tokenizer, max_seqs: int) -> None:
+    """spl_stream_reserve_device: the decode tables on the device and scratch for max_seqs sequences; stream_decode_device calls within that
+    size then neither allocate nor synchronise."""
+    rc = _ffi.lib().spl_stream_reserve_device(tok.handle, int(max_seqs))
+    if rc != 0:
+        raise (ValueError if rc == -1 else RuntimeError)(f"spl_stream_reserve_device failed ({rc}): {_ffi.last_error()}")
+
+
+def stream_decode_device(tok: Tokenizer, ids: torch.Tensor, lengths: Optional[torch.Tensor], state: torch.Tensor, *, errors: str = "hold",
+                         final=None, max_bytes: int, skip_special_tokens: bool = False,
+                         state_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """One step of B streaming decoders on the GPU (spl_stream_decode_device), on torch's current stream; nothing synchronises.  ids [B] or
+    [B, K] int32 / int64 (what a sampler leaves: a sequence's first lengths[b] entries count, all of them with lengths None; an int64
+    value outside 0 .. 2**32 - 1 is no id); state int64 [B], one word per sequence as include/splintr_hip.h lays it out (0: a fresh
+    decoder).  errors "hold" is the host StreamingDecoder step for step (invalid bytes stall a sequence for ever), "replace" emits U+FFFD
+    for them.  final: None, True (every sequence) or a uint8 / bool tensor [B]: pending bytes leave as one U+FFFD behind this step's ids.
+    Returns (bytes uint8 [max_bytes rounded up to 16], out_off int64 [B + 1], state_out int64 [B]); out_off[-1] is the byte count NEEDED,
+    bytes beyond the buffer are dropped -- and the state has advanced all the same: pass a state_out other than state where the call may
+    have to be repeated with a larger buffer (state_out None: a new tensor; state_out may be state itself)."""
+    check_stream_args(ids, lengths, state, errors=errors, final=final, max_bytes=max_bytes, state_out=state_out)
+    dev = ids.device
+    B = int(ids.shape[0])
+    K = int(ids.shape[1]) if ids.dim() == 2 else 1
+    flags = (_ffi.SPL_DECODE_I64 if ids.dtype == torch.int64 else 0) | (_ffi.SPL_DECODE_SKIP_SPECIAL if skip_special_tokens else 0)
+    sflags = _stream_mode(errors) | (_ffi.SPL_STREAM_FINAL_ALL if final is True else 0)
+    out = torch.empty(_max_bytes(max_bytes), dtype=torch.uint8, device=dev)
+    out_off = torch.empty(B + 1, dtype=torch.int64, device=dev)                # (every offset and every state word is written by the kernels)
+    if state_out is None:
+        state_out = torch.empty(B, dtype=torch.int64, device=dev)
+    ptr = lambda t: t.data_ptr() if isinstance(t, torch.Tensor) and t.numel() else None
+    o = _ffi.SplDecodeOpts(flags, K)
+    # (a null state pointer is refused by the library: an empty batch passes the offsets' address, which nothing dereferences)
+    rc = _ffi.lib().spl_stream_decode_device(tok.handle, ptr(ids), ptr(lengths), B, ctypes.byref(o), sflags, ptr(final),
+                                             ptr(state) or out_off.data_ptr(), ptr(state_out) or out_off.data_ptr(), ptr(out), out.numel(),
+                                             out_off.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise (ValueError if rc == -1 else RuntimeError)(f"spl_stream_decode_device failed ({rc}): {_ffi.last_error()}")
+    return out, out_off, state_out
+
+
+class DeviceStreamingDecoder:
+    """`tokenizer.device_streaming_decoder(batch_size)`: B streaming decoders whose state lives on the GPU, one word per sequence.  The
+    host classes of splintr_amd.streaming decode one id per Python call; this one takes a whole step of the batch as a device tensor.
+    errors "hold" emits exactly what B host decoders emit (ByteLevel vocabularies: byte_level_streaming_decoder, others:
+    streaming_decoder); "replace" never stalls."""
+
+    BYTES_PER_ID = 8           # first guess of a step's buffer; a short buffer repeats the step once with the exact need
+
+    def __init__(self, tok: Tokenizer, batch_size: int, *, errors: str = "hold", skip_special_tokens: bool = False):
+        _stream_mode(errors)
+        if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)) or not 0 <= int(batch_size) < (1 << 31):
+            raise ValueError(f"batch_size must be an integer in 0 .. 2**31 - 1, not {batch_size!r}")
+        self._tok, self._errors, self._skip = tok, errors, bool(skip_special_tokens)
+        self.batch_size = int(batch_size)
+        dev = torch.device("cuda", tok._device)
+        self._state = torch.zeros(self.batch_size, dtype=torch.int64, device=dev)      # the current words ...
+        self._spare = torch.zeros(self.batch_size, dtype=torch.int64, device=dev)      # ... and where the next step leaves its own
+        stream_reserve(tok, self.batch_size)
+
+    def step_device(self, ids: torch.Tensor, lengths: Optional[torch.Tensor] = None, *, final=None, max_bytes: Optional[int] = None):
+        """Tensors only, nothing synchronises: one step -> (bytes, out_off int64 [B + 1]) on the device; out_off[-1] is the need.  The
+        state advances whatever max_bytes is (default 8 bytes per id, 16 at least)."""
+        if isinstance(ids, torch.Tensor) and ids.shape[:1] != (self.batch_size,):
+            raise ValueError(f"the ids must have {self.batch_size} rows")
+        if max_bytes is None:
+            max_bytes = max(16, self.BYTES_PER_ID * ids.numel()) if isinstance(ids, torch.Tensor) else 16
+        out, off, _ = stream_decode_device(self._tok, ids, lengths, self._state, errors=self._errors, final=final, max_bytes=max_bytes,
+                                           skip_special_tokens=self._skip, state_out=self._spare)
+        self._prev_args = (ids, lengths, final)
+        self._state, self._spare = self._spare, self._state
+        return out, off
+
+    def _texts(self, out, off):
+        need = int(off[-1].item())
+        if need > out.numel():                                     # the step once more from the kept state_in, with the exact need
+            ids, lengths, final = self._prev_args
+            out, off, _ = stream_decode_device(self._tok, ids, lengths, self._spare, errors=self._errors, final=final, max_bytes=need,
+                                               skip_special_tokens=self._skip, state_out=self._state)
+        raw = out[:need].cpu().numpy().tobytes()
+        o = off.cpu().tolist()
+        return [raw[o[i]:o[i + 1]].decode("utf-8") if o[i + 1] > o[i] else None for i in range(len(o) - 1)]
+
+    def add_tokens(self, ids: torch.Tensor, lengths: Optional[torch.Tensor] = None, *, max_bytes: Optional[int] = None):
+        """ids [B] or [B, K] on the GPU -> list of B entries: the text that leaves for sequence b now, None where nothing does (as the host
+        class).  One copy of the bytes and one of the offsets to the host."""
+        return self._texts(*self.step_device(ids, lengths, max_bytes=max_bytes))
+
+    def flush(self, rows=None):
+        """What is pending leaves as U+FFFD -- for every sequence, or for those of `rows` (a uint8 / bool tensor [B], or indices) -- and
+        their state becomes fresh; a stalled sequence (errors "hold") gives None and stays stalled (see `stalled`; reset it)."""
+        dev = self._state.device
+        none = torch.zeros(self.batch_size, dtype=torch.int32, device=dev)
+        ids = torch.zeros((self.batch_size, 1), dtype=torch.int32, device=dev)
+        return self._texts(*self.step_device(ids, none, final=True if rows is None else self._mask(rows)))
+
+    def _mask(self, rows):
+        dev = self._state.device
+        if isinstance(rows, torch.Tensor) and rows.dtype in (torch.uint8, torch.bool) and rows.shape == (self.batch_size,):
+            return rows.to(dev).contiguous()
+        m = torch.zeros(self.batch_size, dtype=torch.uint8, device=dev)
+        m[torch.as_tensor(rows, dtype=torch.long, device=dev)] = 1
+        return m
+
+    def reset(self, rows=None) -> None:
+        if rows is None:
+            self._state.zero_()
+        else:
+            self._state[self._mask(rows).bool()] = 0
+
+    @property
+    def state(self) -> torch.Tensor:
+        return self._state
+
+    @property
+    def pending_bytes(self) -> torch.Tensor:
+        """int64 [B] on the device: the host class's pending_bytes per sequence"""
+        s = self._state
+        return torch.where((s >> 26) & 1 != 0, (s >> 32) & 0xFFFFFFFF, (s >> 24) & 3)
+
+    @property
+    def stalled(self) -> torch.Tensor:
+        return ((self._state >> 26) & 1).bool()
+
+    def __repr__(self) -> str:
+        return f"DeviceStreamingDecoder(batch_size={self.batch_size}, errors={self._errors!r})"
+
+
 class Comm:
     """One rank of the library's own RCCL communicator (include/splintr_hip.h: spl_comm_*).  The 128-byte id is
     made by rank 0 and handed to the others by whatever the caller has; `from_torch_group` uses an existing

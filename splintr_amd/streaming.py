@@ -4,7 +4,8 @@ Mirrors the reference's PyStreamingDecoder / PyByteLevelStreamingDecoder
 (src/python/bindings.rs:465-834; core: src/core/streaming.rs): token bytes are appended to a
 buffer and only complete UTF-8 characters leave it.  This is sequential CPU work by nature (one
 token at a time, as an LLM emits them); the id -> bytes lookups go to the handle's host tables
-(spl_token_bytes), nothing runs on the GPU.
+(spl_token_bytes), nothing runs on the GPU.  For a BATCH of sequences decoded in step -- what a sampler on the GPU produces -- the
+device form is Tokenizer.device_streaming_decoder (splintr_amd.device.DeviceStreamingDecoder, spl_stream_decode_device).
 """
 from __future__ import annotations
 

@@ -507,6 +507,14 @@ class Tokenizer:
         from .streaming import ByteLevelStreamingDecoder
         return ByteLevelStreamingDecoder(lambda t: self._token_bytes(t, True))
 
+    def device_streaming_decoder(self, batch_size: int, *, errors: str = "hold", skip_special_tokens: bool = False):
+        """Extension: batch_size streaming decoders whose state lives ON THE GPU (splintr_amd.device.DeviceStreamingDecoder): a sampler's
+        step -- ids [B] or [B, K] as a device tensor -- goes in, the text that may leave comes back, one launch per step for small
+        batches.  errors "hold": what byte_level_streaming_decoder (ByteLevel vocabularies) / streaming_decoder emit, step for step;
+        "replace": U+FFFD for invalid bytes, no sequence ever stalls."""
+        from . import device as dv
+        return dv.DeviceStreamingDecoder(self, batch_size, errors=errors, skip_special_tokens=skip_special_tokens)
+
     # ------------------------------------------------------------------ cheap surface
     @property
     def vocab_size(self) -> int:
