@@ -145,10 +145,15 @@ uint32_t spl_n_devices(const spl_tokenizer* t);
  *                            of a few thousand documents reaches its second round
  *   "stream_one_max"         0..1024 (64): spl_stream_decode_device takes its one-launch form up to this many sequences, the three-launch
  *                            form beyond (0: always three; profiles/stream_decode.txt has the measured crossing)
+ *   "stop_one_max"           0..1024 (64): spl_stop_match_device takes its one-launch form up to this many sequences, the three-launch form
+ *                            beyond (0: always three; profiles/stop_match.txt has the measured crossing)
  *   "slab_pack24"            0/1 (0): the ids of the all-gather slabs travel three bytes each; every rank alike; refused (SPL_EINVAL) when an
  *                            id of the tokenizer -- vocabulary or special token -- does not fit 24 bits
  * Unknown names and values out of range: SPL_EINVAL. */
 int spl_set_option(spl_tokenizer* t, const char* name, int64_t value);
+/* The current value of a switch of spl_set_option (every name above but "memo_clear", which holds nothing).  A null argument or an
+ * unknown name: SPL_EINVAL, *value untouched. */
+int spl_get_option(const spl_tokenizer* t, const char* name, int64_t* value);
 
 /* One entry of the special_tokens map (src/core/tokenizer.rs:304, 429-434).  Call before the first
  * encode.  Literals are non-empty and at most 255 bytes; adding a literal again replaces its id.
@@ -642,6 +647,69 @@ int spl_stream_decode_device(spl_tokenizer* t, const void* d_ids /* [n_seqs, o->
                              const uint64_t* d_state_in, uint64_t* d_state_out,
                              uint8_t* d_bytes, uint64_t bytes_capacity,
                              uint64_t* d_out_off /* [n_seqs+1] */, void* hip_stream);
+
+/* STOP STRINGS for n_seqs streaming sequences at once, everything in DEVICE memory: what a serving loop does with the
+ * text of a step -- compare it against the request's stop strings, hold back what may still become one -- as the pure function
+ * (state_in[b], the new bytes of b, mask[b], final[b]) -> (bytes CSR, hit[b], state_out[b]).  A stop string is text, not an id: it may
+ * begin in the middle of one token and end in the middle of another, steps apart.
+ *
+ * The rule, per sequence, is one of the WHOLE text and does not depend on where the steps cut it.  T = every byte fed so far, S = the
+ * stops its mask selects.  HIT: the smallest end e such that some s of S is a suffix of T[:e]; of the stops that end at e the longest wins
+ * (its start is p), of equal strings the lowest slot.  The released text is T[:p] -- T[:e] under SPL_STOP_INCLUDE --, d_hit[b] is the slot,
+ * and the sequence is STOPPED from then on: it ignores further input (the rest of the call that hit included), emits nothing, and its row
+ * stays as it is bit for bit.  NO HIT: the released text is T[:|T| - h], h the length of the longest suffix of T that is a PROPER prefix of
+ * some s of S (h <= 63) -- exactly the text that may still become a stop is held back, so nothing a client was shown is ever taken back and
+ * the released length never decreases.  FINAL -- d_final[b] != 0, or SPL_STOP_FINAL_ALL -- is applied behind the call's bytes: without a
+ * hit the held bytes leave too, h = 0, and the text is CLOSED: the tail is emptied, bytes fed later are matched as a new text (`released`
+ * goes on counting).  A call's output for a sequence is its released text now less its released text before the call.  A sequence with no
+ * new bytes and no final keeps its row bit for bit.  Where the stops and T are valid UTF-8 every cut is a character boundary.
+ *
+ * The table (SPL_STOP_TABLE_BYTES of device memory, the CALLER's): slot s is bytes [64 s, 64 s + len[s]), and uint8 len[64] lies behind the
+ * 64 slots; a slot of length 0 or above 64 never matches.  d_mask[b] bit s: slot s applies to sequence b (NULL: every slot to everyone).  The
+ * caller may rewrite a slot with a stream-ordered copy of its own -- a continuous-batching loop reusing a finished request's slots --, but
+ * ONLY WHILE NO LIVE SEQUENCE'S MASK NAMES IT: a sequence's held bytes were held for the stops its mask named.
+ *
+ * The state row (SPL_STOP_STATE_WORDS uint64 per sequence; all zero is a fresh sequence, so a reset is the caller zeroing rows; every bit
+ * not named is 0 and the tail's bytes from tail_len on are 0, so rows compare bit for bit):
+ *     word 0      bits 0..6 tail_len     bits 8..14 held (h)     bit 16 stopped     bits 24..29 the slot that hit
+ *     word 1      released: the bytes released so far; once stopped, the offset of the cut in the sequence's text
+ *     words 2..9  the tail: the last min(|T|, 63) bytes of T (of T[:e] once stopped), the first byte lowest
+ *
+ * Input: any bytes CSR in device memory -- spl_stream_decode_device's d_bytes and d_out_off as they are.  An offset above in_capacity counts
+ * as in_capacity and bytes beyond it are not read (an overflowed producer's convention).  Output as the streaming decode's: d_out_off[b] =
+ * where sequence b's bytes start, d_out_off[n_seqs] = the byte count NEEDED; bytes at or beyond out_capacity are dropped and nothing at or
+ * beyond min(need, capacity) is written; every offset, every hit (-1, or the slot: sticky) and EVERY STATE WORD is written exactly once
+ * whatever the capacity.  The state advances even where bytes were dropped: a caller that may have to repeat a call keeps d_state_in
+ * (passes another array as d_state_out); d_state_out == d_state_in is allowed otherwise.  That is the ONLY overlap allowed: the write pass
+ * reads d_in_bytes, d_in_off, d_table, d_mask and d_final again while other workgroups write, so none of d_out_bytes, d_out_off, d_hit and
+ * d_state_out may overlap any input (nor one another), and d_state_out may overlap d_state_in only as the same array.
+ *
+ * Up to 64 sequences ("stop_one_max"; the two forms' medians cross between 64 and 80, profiles/stop_match.txt) the call is ONE launch of
+ * one workgroup, beyond that three.  The call is asynchronous on hip_stream; the handle is used for its device and its scratch only (no
+ * table of the tokenizer is read).  spl_stop_reserve_device sizes the scratch -- 24 bytes per sequence and 8 per 16 of them, grow-only,
+ * shared with nothing; after it a call within that size neither allocates nor synchronises.  Stop calls of ONE handle share the scratch:
+ * they need stream order among themselves.
+ *
+ * SPL_EINVAL, with the cause in spl_last_error() and before anything touches the device: a null t, d_table, d_state_in, d_state_out,
+ * d_out_off, d_hit or d_in_off; a null d_in_bytes with in_capacity > 0; a null d_out_bytes with out_capacity > 0; d_out_bytes not 16-byte
+ * aligned; an unknown bit in stop_flags; n_seqs >= 2^31. */
+#define SPL_STOP_SLOTS       64
+#define SPL_STOP_MAX_LEN     64
+#define SPL_STOP_TABLE_BYTES (64 * 64 + 64)
+#define SPL_STOP_STATE_WORDS 10
+#define SPL_STOP_INCLUDE     1u  /* the stop string itself is released with the text in front of it */
+#define SPL_STOP_FINAL_ALL   2u  /* every sequence is final in this call */
+int spl_stop_reserve_device(spl_tokenizer* t, uint64_t max_seqs);
+int spl_stop_match_device(spl_tokenizer* t,
+                          const uint8_t* d_in_bytes, uint64_t in_capacity,
+                          const uint64_t* d_in_off /* [n_seqs+1] */, uint64_t n_seqs,
+                          const uint8_t* d_table /* SPL_STOP_TABLE_BYTES */,
+                          const uint64_t* d_mask /* [n_seqs], NULL: all */,
+                          const uint8_t* d_final /* [n_seqs], NULL ok */, uint32_t stop_flags,
+                          const uint64_t* d_state_in, uint64_t* d_state_out /* [n_seqs, 10] */,
+                          uint8_t* d_out_bytes, uint64_t out_capacity,
+                          uint64_t* d_out_off /* [n_seqs+1] */,
+                          int32_t* d_hit /* [n_seqs] */, void* hip_stream);
 
 /* Host-side lookup of ONE id, for consumers that decode token by token on the CPU -- the streaming
  * decoders (src/core/streaming.rs, src/python/bindings.rs:465-834 take clones of Tokenizer::decoder

@@ -32,6 +32,7 @@ SYMBOLS = [
     "spl_pad_device", "spl_pack_device", "spl_pair_device", "spl_window_work_bytes", "spl_window_device",
     "spl_decode_reserve_device", "spl_decode_batch_device", "spl_max_token_bytes", "spl_token_spans_device",
     "spl_stream_reserve_device", "spl_stream_decode_device",
+    "spl_get_option", "spl_stop_reserve_device", "spl_stop_match_device",
 ]
 SPL_PATTERN_CUSTOM = 3
 SPL_OPT_BYTE_LEVEL = 1
@@ -41,6 +42,8 @@ SPL_PAIR_LONGEST_FIRST, SPL_PAIR_ONLY_FIRST, SPL_PAIR_ONLY_SECOND = 0, 1, 2
 SPL_DECODE_I64, SPL_DECODE_PAD_LEFT, SPL_DECODE_SKIP_SPECIAL = 1, 2, 4
 SPL_SPANS_I64 = 1
 SPL_STREAM_REPLACE, SPL_STREAM_FINAL_ALL = 1, 2
+SPL_STOP_SLOTS, SPL_STOP_MAX_LEN, SPL_STOP_TABLE_BYTES, SPL_STOP_STATE_WORDS = 64, 64, 64 * 64 + 64, 10
+SPL_STOP_INCLUDE, SPL_STOP_FINAL_ALL = 1, 2
 
 
 class SplOpts(ctypes.Structure):
@@ -194,6 +197,10 @@ def lib() -> ctypes.CDLL:
     L.spl_stream_reserve_device.argtypes = [vp, ctypes.c_uint64]
     L.spl_stream_decode_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.POINTER(SplDecodeOpts), ctypes.c_uint32, vp, vp, vp, vp,
                                            ctypes.c_uint64, vp, vp]
+    L.spl_get_option.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64)]
+    L.spl_stop_reserve_device.argtypes = [vp, ctypes.c_uint64]
+    L.spl_stop_match_device.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp, vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint64,
+                                        vp, vp, vp]
     _lib = L
     return L
 

@@ -1,7 +1,7 @@
 // spl_api.hip -- the C ABI (include/splintr_hip.h): the root of the library's one HIP translation unit.  It includes the kernels
 // (spl_kernels.hip) and the host side, one file per concern and each building on the ones before it -- spl_host_res.h (resource owners,
 // pinned pool), spl_ctx.h (per-GPU context, handle, uploads), spl_streams.h (stream probe), spl_launch.h (memo, launch order, device
-// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_pair_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h, spl_stream_host.h -- and holds the entry points.
+// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_pair_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h, spl_stream_host.h, spl_stop_host.h -- and holds the entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -45,6 +45,7 @@ using namespace spl;
 #include "spl_decode_dev_host.h"
 #include "spl_spans_host.h"
 #include "spl_stream_host.h"
+#include "spl_stop_host.h"
 
 namespace {
 // No exception crosses the C ABI: every entry point that allocates (std::bad_alloc), starts threads or grows
@@ -153,6 +154,7 @@ int spl_set_option(spl_tokenizer* t, const char* name, int64_t value) {
     else if (k == "sdma_d2h") t->sdma_d2h = value != 0;        // (where the HSA runtime or the device's agent cannot be found: hipMemcpyAsync, silently)
     else if (k == "window_totals_chunk" && value >= 1 && value <= (int64_t)WIN_CHUNK) t->win_chunk = (uint32_t)value;
     else if (k == "stream_one_max" && value >= 0 && value <= (int64_t)ST_ONE_MAX) t->stream_one_max = (uint32_t)value;
+    else if (k == "stop_one_max" && value >= 0 && value <= (int64_t)SP_ONE_MAX) t->stop_one_max = (uint32_t)value;
     else if (k == "slab_pack24") {
         if (value && std::max(t->ht.max_id, t->max_special_id) >= (1u << 24))
             return fail(SPL_EINVAL, "slab_pack24: an id of this tokenizer does not fit three bytes (vocabulary or special-token ids >= 2^24)");
@@ -160,6 +162,24 @@ int spl_set_option(spl_tokenizer* t, const char* name, int64_t value) {
     }
     else return fail(SPL_EINVAL, "spl_set_option: unknown option or bad value: " + k);
     return SPL_OK;
+}
+
+int spl_get_option(const spl_tokenizer* t, const char* name, int64_t* value) {
+    if (!t || !name || !value) return fail(SPL_EINVAL, "spl_get_option: null argument");
+    const std::string k(name);
+    const std::pair<const char*, int64_t> all[] = {
+        {"chunk_bytes", (int64_t)t->chunk_bytes}, {"single_chunk_max_bytes", (int64_t)t->single_max}, {"result_estimate_div", t->est_div},
+        {"subdoc_split", t->subdoc}, {"direct_write", t->direct_write}, {"device_split", t->rx_device}, {"small_path", t->small_path},
+        {"direct_read", t->direct_read}, {"chunk_ramp", t->chunk_ramp}, {"twin_streams", t->twin_streams}, {"pick_streams", t->pick_streams},
+        {"fuse", t->fuse}, {"group_scan_min", t->group_scan_min}, {"range_tiles", t->range_tiles}, {"range_streams", t->range_streams},
+        {"memo", t->memo}, {"memo_first", t->memo_first}, {"memo_bits", t->memo_bits}, {"memo_long_bits", t->memo_long_bits},
+        {"memo_log_cap", t->memo_log_cap}, {"fuse_max_tiles", t->fuse_max_tiles}, {"copy_threads", t->copy_threads},
+        {"decode_chunk_ids", (int64_t)t->dec_chunk_ids}, {"sdma_d2h", t->sdma_d2h}, {"window_totals_chunk", t->win_chunk},
+        {"stream_one_max", t->stream_one_max}, {"stop_one_max", t->stop_one_max}, {"slab_pack24", t->slab_pack24},
+    };
+    for (const auto& e : all)
+        if (k == e.first) { *value = e.second; return SPL_OK; }
+    return fail(SPL_EINVAL, "spl_get_option: unknown option: " + k);
 }
 
 static int spl_add_special_impl(spl_tokenizer* t, const uint8_t* literal, size_t len, uint32_t id) {
@@ -435,6 +455,21 @@ int spl_stream_decode_device(spl_tokenizer* t, const void* d_ids, const int32_t*
         return stream_decode_device(t, {.ids = d_ids, .len = d_len, .n_seqs = n_seqs, .o = o, .stream_flags = stream_flags, .fin = d_final,
                                         .state_in = d_state_in, .state_out = d_state_out, .bytes = d_bytes, .bytes_cap = bytes_capacity,
                                         .out_off = d_out_off, .stream = (hipStream_t)hip_stream}); });
+}
+
+int spl_stop_reserve_device(spl_tokenizer* t, uint64_t max_seqs) {
+    return guarded("spl_stop_reserve_device", [&] { return stop_reserve_device(t, max_seqs); });
+}
+
+int spl_stop_match_device(spl_tokenizer* t, const uint8_t* d_in_bytes, uint64_t in_capacity, const uint64_t* d_in_off, uint64_t n_seqs,
+                          const uint8_t* d_table, const uint64_t* d_mask, const uint8_t* d_final, uint32_t stop_flags,
+                          const uint64_t* d_state_in, uint64_t* d_state_out, uint8_t* d_out_bytes, uint64_t out_capacity, uint64_t* d_out_off,
+                          int32_t* d_hit, void* hip_stream) {
+    return guarded("spl_stop_match_device", [&] {
+        return stop_match_device(t, {.in = d_in_bytes, .in_cap = in_capacity, .in_off = d_in_off, .n_seqs = n_seqs, .table = d_table,
+                                     .mask = d_mask, .fin = d_final, .flags = stop_flags, .state_in = d_state_in, .state_out = d_state_out,
+                                     .out = d_out_bytes, .out_cap = out_capacity, .out_off = d_out_off, .hit = d_hit,
+                                     .stream = (hipStream_t)hip_stream}); });
 }
 
 int spl_pack_device(spl_tokenizer* t, const uint32_t* d_ids, const uint64_t* d_out_off, uint64_t n_docs, const spl_collate_opts* o,

@@ -67,6 +67,7 @@ struct Ctx {
     bool dec_uploaded = false;
     DevBuf<uint64_t> d_ddblk; uint64_t ddblk_cap = 0;   // spl_decode_batch_device: block sums, 8 bytes per 1 024 ids (grow-only; shared with nothing)
     DevBuf<uint64_t> d_stblk; uint64_t stblk_cap = 0;   // spl_stream_decode_device: block sums and per-sequence counts, 8 bytes per sequence and 8 per 16 of them (grow-only; shared with nothing)
+    DevBuf<uint64_t> d_spblk; uint64_t spblk_cap = 0;   // spl_stop_match_device: block sums and per-sequence count, cut and hit, 24 bytes per sequence and 8 per 16 of them (grow-only; shared with nothing)
     DevBuf<uint64_t> d_snblk; uint64_t snblk_cap = 0;   // spl_token_spans_device: block sums of bytes and of characters, 16 bytes per 1 024 ids (grow-only; shared with nothing)
     DevBuf<uint8_t> d_sp_lits;                 // uploaded lazily; invalidated by spl_add_special
     bool sp_uploaded = false;
@@ -211,6 +212,7 @@ struct spl_tokenizer {
     int small_path = 1;                       // batches of up to 4 KB take the latency path (encode_small)
     int slab_pack24 = 0;                      // the ids of the all-gather slabs travel three bytes each (spl_set_option "slab_pack24": every rank alike)
     uint32_t stream_one_max = ST_ONE_DEFAULT;    // "stream_one_max": most sequences spl_stream_decode_device takes in its one-launch form
+    uint32_t stop_one_max = SP_ONE_DEFAULT;      // "stop_one_max": most sequences spl_stop_match_device takes in its one-launch form
     uint32_t win_chunk = WIN_CHUNK;          // "window_totals_chunk" (tests): span totals k_window_totals scans per round, so that a few thousand documents reach its second round
     int sdma_d2h = 0;                         // (measured, +0.5..3 %: not the default) pipeline chunks: their ids leave through hsa_amd_memory_async_copy (an SDMA engine) instead of hipMemcpyAsync
     uint64_t dec_chunk_ids = 2ull << 20;      // decode pipeline: ids per chunk (batches of fewer than three such chunks are decoded in one piece; C3: 28.3 GB/s at 1 M, 30.5 at 2 M, 29.6 at 3 M)

@@ -531,28 +531,153 @@ def stream_decode_device(tok: Tokenizer, ids: torch.Tensor, lengths: Optional[to
     return out, out_off, state_out
 
 
+# ---------------------------------------------------------------------------------------------- stop strings (per-sequence match state)
+def _stop_table_host(stops) -> np.ndarray:
+    if isinstance(stops, (str, bytes, bytearray)) or not hasattr(stops, "__iter__"):
+        raise ValueError("stops must be a list of str or bytes")
+    stops = list(stops)
+    if len(stops) > _ffi.SPL_STOP_SLOTS:
+        raise ValueError(f"at most {_ffi.SPL_STOP_SLOTS} stops fit the table, not {len(stops)}")
+    tab = np.zeros(_ffi.SPL_STOP_TABLE_BYTES, dtype=np.uint8)
+    for s, x in enumerate(stops):
+        if isinstance(x, str):
+            x = x.encode("utf-8")
+        elif not isinstance(x, (bytes, bytearray)):
+            raise ValueError(f"stop {s} must be str or bytes, not {type(x).__name__}")
+        if not 1 <= len(x) <= _ffi.SPL_STOP_MAX_LEN:
+            raise ValueError(f"stop {s} must have 1 .. {_ffi.SPL_STOP_MAX_LEN} bytes, not {len(x)}")
+        tab[_ffi.SPL_STOP_MAX_LEN * s:_ffi.SPL_STOP_MAX_LEN * s + len(x)] = np.frombuffer(bytes(x), dtype=np.uint8)
+        tab[_ffi.SPL_STOP_SLOTS * _ffi.SPL_STOP_MAX_LEN + s] = len(x)
+    return tab
+
+
+def stop_table(stops, device=None) -> torch.Tensor:
+    """The stop table of spl_stop_match_device on the device (default: the current GPU): uint8 [4160], slot s = stops[s] (str: its UTF-8).
+    ValueError for an empty stop, one over 64 bytes, or more than 64 stops.  The tensor is the caller's: a slot may be rewritten (a
+    stream-ordered copy) only while no live sequence's mask names it."""
+    tab = _stop_table_host(stops)
+    return torch.from_numpy(tab).to(torch.device("cuda") if device is None else device)
+
+
+def check_stop_args(in_bytes, in_off, state, table, *, mask=None, final=None, max_bytes=0, state_out=None) -> None:
+    """ValueError for a dtype, rank, shape, layout, size or device that stop_match_device would refuse -- before anything goes to the
+    device."""
+    _max_bytes(max_bytes)
+    if not isinstance(in_bytes, torch.Tensor) or in_bytes.dtype != torch.uint8 or in_bytes.dim() != 1 or not in_bytes.is_contiguous():
+        raise ValueError("in_bytes must be a contiguous uint8 tensor of rank 1")
+    if not isinstance(in_off, torch.Tensor) or in_off.dtype != torch.int64 or in_off.dim() != 1 or in_off.shape[0] < 1 or not in_off.is_contiguous():
+        raise ValueError("in_off must be a contiguous int64 tensor of shape [batch + 1]")
+    B = int(in_off.shape[0]) - 1
+    if B >= (1 << 31):
+        raise ValueError("the sequences must be fewer than 2**31")
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.uint8 or table.shape != (_ffi.SPL_STOP_TABLE_BYTES,) or not table.is_contiguous():
+        raise ValueError(f"table must be a contiguous uint8 tensor of shape [{_ffi.SPL_STOP_TABLE_BYTES}] (stop_table)")
+    others = [("in_off", in_off), ("table", table)]
+
+    def rows(name, t):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.shape != (B, _ffi.SPL_STOP_STATE_WORDS) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous int64 tensor of shape [batch, {_ffi.SPL_STOP_STATE_WORDS}]")
+        others.append((name, t))
+
+    def vec(name, t, dtypes, what):
+        if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or t.dim() != 1 or t.shape[0] != B or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {what} tensor of shape [batch]")
+        others.append((name, t))
+
+    rows("state", state)
+    if state_out is not None:
+        rows("state_out", state_out)
+    if mask is not None:
+        vec("mask", mask, (torch.int64,), "int64")
+    if final is not None and not isinstance(final, bool):
+        vec("final", final, (torch.uint8, torch.bool), "uint8 or bool")
+    if not in_bytes.is_cuda:
+        raise ValueError("in_bytes must be on a GPU (the device-side stop match takes no host tensor)")
+    for name, t in others:
+        if t.device != in_bytes.device:
+            raise ValueError(f"{name} must be on the device of in_bytes")
+
+
+def stop_reserve(tok: Tokenizer, max_seqs: int) -> None:
+    """spl_stop_reserve_device: scratch for max_seqs sequences; stop_match_device calls within that size then neither allocate nor
+    synchronise."""
+    rc = _ffi.lib().spl_stop_reserve_device(tok.handle, int(max_seqs))
+    if rc != 0:
+        raise (ValueError if rc == -1 else RuntimeError)(f"spl_stop_reserve_device failed ({rc}): {_ffi.last_error()}")
+
+
+def stop_match_device(tok: Tokenizer, in_bytes: torch.Tensor, in_off: torch.Tensor, state: torch.Tensor, table: torch.Tensor, *, mask=None,
+                      final=None, include_stop: bool = False, max_bytes: int,
+                      state_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Stop strings for B streaming sequences on the GPU (spl_stop_match_device), on torch's current stream; nothing synchronises.
+    in_bytes uint8 / in_off int64 [B + 1]: a bytes CSR -- stream_decode_device's as it is (offsets beyond in_bytes are clamped); state int64
+    [B, 10], one row per sequence as include/splintr_hip.h lays it out (zeros: fresh); table: stop_table(...); mask int64 [B], bit s: slot
+    s applies to the sequence (None: every slot to everyone).  final: None, True (every sequence) or a uint8 / bool tensor [B]: the held
+    bytes leave too.  Returns (bytes uint8 [max_bytes rounded up to 16], out_off int64 [B + 1], hit int32 [B]: -1 or the slot, state_out
+    int64 [B, 10]); out_off[-1] is the byte count NEEDED, bytes beyond the buffer are dropped -- and the state has advanced all the same:
+    pass a state_out other than state where the call may have to be repeated (None: a new tensor; state_out may be state itself)."""
+    check_stop_args(in_bytes, in_off, state, table, mask=mask, final=final, max_bytes=max_bytes, state_out=state_out)
+    dev = in_bytes.device
+    B = int(in_off.shape[0]) - 1
+    flags = (_ffi.SPL_STOP_INCLUDE if include_stop else 0) | (_ffi.SPL_STOP_FINAL_ALL if final is True else 0)
+    out = torch.empty(_max_bytes(max_bytes), dtype=torch.uint8, device=dev)
+    out_off = torch.empty(B + 1, dtype=torch.int64, device=dev)                # (every offset, hit and state word is written by the kernels)
+    hit = torch.empty(max(B, 1), dtype=torch.int32, device=dev)[:B]
+    if state_out is None:
+        state_out = torch.empty((B, _ffi.SPL_STOP_STATE_WORDS), dtype=torch.int64, device=dev)
+    ptr = lambda t: t.data_ptr() if isinstance(t, torch.Tensor) and t.numel() else None
+    # (null state and hit pointers are refused by the library: an empty batch passes the offsets' address, which nothing dereferences)
+    rc = _ffi.lib().spl_stop_match_device(tok.handle, ptr(in_bytes), in_bytes.numel(), in_off.data_ptr(), B, table.data_ptr(), ptr(mask),
+                                          ptr(final), flags, ptr(state) or out_off.data_ptr(), ptr(state_out) or out_off.data_ptr(),
+                                          ptr(out), out.numel(), out_off.data_ptr(), ptr(hit) or out_off.data_ptr(),
+                                          torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise (ValueError if rc == -1 else RuntimeError)(f"spl_stop_match_device failed ({rc}): {_ffi.last_error()}")
+    return out, out_off, hit, state_out
+
+
 class DeviceStreamingDecoder:
     """`tokenizer.device_streaming_decoder(batch_size)`: B streaming decoders whose state lives on the GPU, one word per sequence.  The
     host classes of splintr_amd.streaming decode one id per Python call; this one takes a whole step of the batch as a device tensor.
     errors "hold" emits exactly what B host decoders emit (ByteLevel vocabularies: byte_level_streaming_decoder, others:
-    streaming_decoder); "replace" never stalls."""
+    streaming_decoder); "replace" never stalls.  stop: stop strings (stop_table's rules) -- every step's text then goes through
+    stop_match_device on the same stream: the text is cut at the first stop (include_stop_str_in_output: behind it), text that may still
+    become one is held back, a sequence that hit emits nothing more, and `finished` / `stop_hit` are device tensors."""
 
     BYTES_PER_ID = 8           # first guess of a step's buffer; a short buffer repeats the step once with the exact need
 
-    def __init__(self, tok: Tokenizer, batch_size: int, *, errors: str = "hold", skip_special_tokens: bool = False):
+    def __init__(self, tok: Tokenizer, batch_size: int, *, errors: str = "hold", skip_special_tokens: bool = False, stop=None,
+                 include_stop_str_in_output: bool = False):
         _stream_mode(errors)
         if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)) or not 0 <= int(batch_size) < (1 << 31):
             raise ValueError(f"batch_size must be an integer in 0 .. 2**31 - 1, not {batch_size!r}")
+        stop_tab = None if stop is None else _stop_table_host(stop)
         self._tok, self._errors, self._skip = tok, errors, bool(skip_special_tokens)
         self.batch_size = int(batch_size)
         dev = torch.device("cuda", tok._device)
         self._state = torch.zeros(self.batch_size, dtype=torch.int64, device=dev)      # the current words ...
         self._spare = torch.zeros(self.batch_size, dtype=torch.int64, device=dev)      # ... and where the next step leaves its own
         stream_reserve(tok, self.batch_size)
+        self._stop_table = None
+        if stop_tab is not None:
+            rows = (self.batch_size, _ffi.SPL_STOP_STATE_WORDS)
+            self._stop_table = torch.from_numpy(stop_tab).to(dev)
+            self._include = bool(include_stop_str_in_output)
+            self._sstate = torch.zeros(rows, dtype=torch.int64, device=dev)             # the stop rows, kept the same way
+            self._sspare = torch.zeros(rows, dtype=torch.int64, device=dev)
+            self._smask = None                                                          # (every slot applies to every sequence)
+            self._prev_decoded = (torch.empty(0, dtype=torch.uint8, device=dev), torch.zeros(1, dtype=torch.int64, device=dev))
+            stop_reserve(tok, self.batch_size)
 
     def step_device(self, ids: torch.Tensor, lengths: Optional[torch.Tensor] = None, *, final=None, max_bytes: Optional[int] = None):
         """Tensors only, nothing synchronises: one step -> (bytes, out_off int64 [B + 1]) on the device; out_off[-1] is the need.  The
-        state advances whatever max_bytes is (default 8 bytes per id, 16 at least)."""
+        state advances whatever max_bytes is (default 8 bytes per id, 16 at least).  With stops the two calls run back to back on the
+        current stream and what comes back is the RELEASED text (its buffer holds max_bytes and the 63 bytes a sequence can have held).
+        The match reads what the decode WROTE: if the decode needed more than max_bytes, the text beyond it never reached the match, the
+        stop rows have advanced on the cut text, and the returned out_off[-1] does not show it.  `decode_overflowed` (a device bool, no
+        synchronisation) is that signal, `decode_need` the bytes the decode needed; a caller of this path either sizes max_bytes for the
+        worst case -- ids per sequence x Tokenizer's longest token, x B -- or reads the flag with whatever it reads next and repeats
+        the step from a state it kept (add_tokens does exactly that)."""
         if isinstance(ids, torch.Tensor) and ids.shape[:1] != (self.batch_size,):
             raise ValueError(f"the ids must have {self.batch_size} rows")
         if max_bytes is None:
@@ -561,26 +686,48 @@ class DeviceStreamingDecoder:
                                            skip_special_tokens=self._skip, state_out=self._spare)
         self._prev_args = (ids, lengths, final)
         self._state, self._spare = self._spare, self._state
+        if self._stop_table is None:
+            return out, off
+        self._prev_decoded = (out, off)
+        out, off = self._stop_step(out, off, final, out.numel() + (_ffi.SPL_STOP_MAX_LEN - 1) * self.batch_size, self._sstate, self._sspare)
+        self._sstate, self._sspare = self._sspare, self._sstate
+        return out, off
+
+    def _stop_step(self, out, off, final, max_bytes, state, state_out):
+        out, off, _, _ = stop_match_device(self._tok, out, off, state, self._stop_table, mask=self._smask, final=final,
+                                           include_stop=self._include, max_bytes=max_bytes, state_out=state_out)
         return out, off
 
     def _texts(self, out, off):
-        need = int(off[-1].item())
-        if need > out.numel():                                     # the step once more from the kept state_in, with the exact need
-            ids, lengths, final = self._prev_args
-            out, off, _ = stream_decode_device(self._tok, ids, lengths, self._spare, errors=self._errors, final=final, max_bytes=need,
-                                               skip_special_tokens=self._skip, state_out=self._state)
+        if self._stop_table is not None:
+            d_out, d_off = self._prev_decoded
+            d_need, need = torch.stack((d_off[-1], off[-1])).tolist()
+            if d_need > d_out.numel() or need > out.numel():       # both calls once more from the kept states: the decode with its exact need,
+                ids, lengths, final = self._prev_args              # the match with what that and the held bytes can come to at most
+                d_out, d_off, _ = stream_decode_device(self._tok, ids, lengths, self._spare, errors=self._errors, final=final,
+                                                       max_bytes=d_need, skip_special_tokens=self._skip, state_out=self._state)
+                out, off = self._stop_step(d_out, d_off, final, d_need + (_ffi.SPL_STOP_MAX_LEN - 1) * self.batch_size, self._sspare,
+                                           self._sstate)
+                need = int(off[-1].item())                         # (a match that read a cut input has counted less)
+        else:
+            need = int(off[-1].item())
+            if need > out.numel():                                     # the step once more from the kept state_in, with the exact need
+                ids, lengths, final = self._prev_args
+                out, off, _ = stream_decode_device(self._tok, ids, lengths, self._spare, errors=self._errors, final=final, max_bytes=need,
+                                                   skip_special_tokens=self._skip, state_out=self._state)
         raw = out[:need].cpu().numpy().tobytes()
         o = off.cpu().tolist()
         return [raw[o[i]:o[i + 1]].decode("utf-8") if o[i + 1] > o[i] else None for i in range(len(o) - 1)]
 
     def add_tokens(self, ids: torch.Tensor, lengths: Optional[torch.Tensor] = None, *, max_bytes: Optional[int] = None):
-        """ids [B] or [B, K] on the GPU -> list of B entries: the text that leaves for sequence b now, None where nothing does (as the host
-        class).  One copy of the bytes and one of the offsets to the host."""
+        """ids [B] or [B, K] on the GPU -> list of B entries: the text that leaves for sequence b now (with stops: the released text), None
+        where nothing does (as the host class).  One copy of the bytes and one of the offsets to the host."""
         return self._texts(*self.step_device(ids, lengths, max_bytes=max_bytes))
 
     def flush(self, rows=None):
         """What is pending leaves as U+FFFD -- for every sequence, or for those of `rows` (a uint8 / bool tensor [B], or indices) -- and
-        their state becomes fresh; a stalled sequence (errors "hold") gives None and stays stalled (see `stalled`; reset it)."""
+        their state becomes fresh; a stalled sequence (errors "hold") gives None and stays stalled (see `stalled`; reset it).  With stops
+        the text held back leaves too (a sequence that hit stays finished and gives None)."""
         dev = self._state.device
         none = torch.zeros(self.batch_size, dtype=torch.int32, device=dev)
         ids = torch.zeros((self.batch_size, 1), dtype=torch.int32, device=dev)
@@ -597,12 +744,69 @@ class DeviceStreamingDecoder:
     def reset(self, rows=None) -> None:
         if rows is None:
             self._state.zero_()
+            if self._stop_table is not None:
+                self._sstate.zero_()
         else:
-            self._state[self._mask(rows).bool()] = 0
+            m = self._mask(rows).bool()
+            self._state[m] = 0
+            if self._stop_table is not None:
+                self._sstate[m] = 0
+
+    def _need_stops(self):
+        if self._stop_table is None:
+            raise ValueError("this decoder was made without stop strings (stop=None)")
+
+    def set_stop_mask(self, rows, mask) -> None:
+        """Which stops apply to the sequences of `rows` (a uint8 / bool tensor [B], or indices; None: all): mask is an int whose bit s
+        says that stop s applies, or an int64 tensor of one such word per selected sequence.  For sequences that are fresh (reset):
+        what a live sequence holds back was held for the stops its mask named."""
+        self._need_stops()
+        if self._smask is None:
+            self._smask = torch.full((self.batch_size,), -1, dtype=torch.int64, device=self._state.device)
+        if isinstance(mask, (int, np.integer)) and not isinstance(mask, bool):
+            mask = int(mask) & 0xFFFFFFFFFFFFFFFF
+            mask = mask - (1 << 64) if mask >= (1 << 63) else mask
+        elif not isinstance(mask, torch.Tensor) or mask.dtype != torch.int64:
+            raise ValueError("mask must be an int or an int64 tensor")
+        if rows is None:
+            self._smask[:] = mask
+        else:
+            self._smask[self._mask(rows).bool()] = mask
 
     @property
     def state(self) -> torch.Tensor:
         return self._state
+
+    @property
+    def stop_state(self) -> torch.Tensor:
+        """int64 [B, 10] on the device: the stop rows (include/splintr_hip.h)"""
+        self._need_stops()
+        return self._sstate
+
+    @property
+    def decode_need(self) -> torch.Tensor:
+        """int64 scalar on the device (no synchronisation): the bytes the last step's DECODE needed -- what out_off[-1] is without stops"""
+        self._need_stops()
+        return self._prev_decoded[1][-1]
+
+    @property
+    def decode_overflowed(self) -> torch.Tensor:
+        """bool scalar on the device (no synchronisation): the last step's decode needed more than its buffer, so the match saw cut text"""
+        self._need_stops()
+        return self._prev_decoded[1][-1] > self._prev_decoded[0].numel()
+
+    @property
+    def finished(self) -> torch.Tensor:
+        """bool [B] on the device, read from the stop rows (no synchronisation): the sequence has hit a stop"""
+        self._need_stops()
+        return ((self._sstate[:, 0] >> 16) & 1).bool()
+
+    @property
+    def stop_hit(self) -> torch.Tensor:
+        """int32 [B] on the device, read from the stop rows (no synchronisation): the stop that was hit, -1 where none was"""
+        self._need_stops()
+        w = self._sstate[:, 0]
+        return torch.where((w >> 16) & 1 != 0, (w >> 24) & 63, torch.full_like(w, -1)).to(torch.int32)
 
     @property
     def pending_bytes(self) -> torch.Tensor:

@@ -507,13 +507,16 @@ class Tokenizer:
         from .streaming import ByteLevelStreamingDecoder
         return ByteLevelStreamingDecoder(lambda t: self._token_bytes(t, True))
 
-    def device_streaming_decoder(self, batch_size: int, *, errors: str = "hold", skip_special_tokens: bool = False):
+    def device_streaming_decoder(self, batch_size: int, *, errors: str = "hold", skip_special_tokens: bool = False, stop=None,
+                                 include_stop_str_in_output: bool = False):
         """Extension: batch_size streaming decoders whose state lives ON THE GPU (splintr_amd.device.DeviceStreamingDecoder): a sampler's
         step -- ids [B] or [B, K] as a device tensor -- goes in, the text that may leave comes back, one launch per step for small
         batches.  errors "hold": what byte_level_streaming_decoder (ByteLevel vocabularies) / streaming_decoder emit, step for step;
-        "replace": U+FFFD for invalid bytes, no sequence ever stalls."""
+        "replace": U+FFFD for invalid bytes, no sequence ever stalls.  stop: up to 64 stop strings (str or bytes, 1 .. 64 bytes each): the
+        text is cut at the first of them, what may still become one is held back, and `finished` / `stop_hit` stay on the device."""
         from . import device as dv
-        return dv.DeviceStreamingDecoder(self, batch_size, errors=errors, skip_special_tokens=skip_special_tokens)
+        return dv.DeviceStreamingDecoder(self, batch_size, errors=errors, skip_special_tokens=skip_special_tokens, stop=stop,
+                                         include_stop_str_in_output=include_stop_str_in_output)
 
     # ------------------------------------------------------------------ cheap surface
     @property
