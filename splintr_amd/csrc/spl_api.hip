@@ -1,7 +1,7 @@
 // spl_api.hip -- the C ABI (include/splintr_hip.h): the root of the library's one HIP translation unit.  It includes the kernels
 // (spl_kernels.hip) and the host side, one file per concern and each building on the ones before it -- spl_host_res.h (resource owners,
 // pinned pool), spl_ctx.h (per-GPU context, handle, uploads), spl_streams.h (stream probe), spl_launch.h (memo, launch order, device
-// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_pair_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h, spl_stream_host.h, spl_stop_host.h -- and holds the entry points.
+// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_pair_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h, spl_seqscan_host.h, spl_stream_host.h, spl_stop_host.h -- and holds the entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -44,6 +44,7 @@ using namespace spl;
 #include "spl_window_host.h"
 #include "spl_decode_dev_host.h"
 #include "spl_spans_host.h"
+#include "spl_seqscan_host.h"
 #include "spl_stream_host.h"
 #include "spl_stop_host.h"
 
@@ -73,7 +74,7 @@ spl_tokenizer* spl_create(const void* vocab, size_t vocab_len, const void* uclas
     // the caller's struct may be older (smaller) than this library's: only the bytes it has are read
     spl_opts o{};
     const uint32_t have = opts_in->struct_size;
-    if (have < 8 || have > 4096) { fail(SPL_EINVAL, "spl_create: spl_opts.struct_size is not set"); return nullptr; }
+    if (refuse_struct_size("spl_create", "spl_opts", have, 8, nullptr) != SPL_OK) return nullptr;
     memcpy(&o, opts_in, std::min<size_t>(have, sizeof o));
     const spl_opts* opts = &o;
     try {

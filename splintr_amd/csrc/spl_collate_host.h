@@ -7,6 +7,19 @@ static_assert(COL_I64 == SPL_COLLATE_I64 && COL_PAD_LEFT == SPL_COLLATE_PAD_LEFT
               COL_BOS == SPL_COLLATE_BOS && COL_EOS == SPL_COLLATE_EOS, "spl_k_collate.h and splintr_hip.h must agree on the flags");
 
 inline bool col_misaligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
+// What every options struct and flag word is refused for (SPL_OK: not refused).  A caller's struct may be longer than this library's (only
+// the fields known here are read), not shorter than `least`: `shorter` names that in the message, null for no such tail.
+int refuse_struct_size(const std::string& who, const char* name, uint32_t have, size_t least, const char* shorter) {
+    if (have >= least && have <= 4096) return SPL_OK;
+    const std::string m = who + ": " + name + ".struct_size is not set";
+    return fail(SPL_EINVAL, shorter ? m + ": it is shorter than " + shorter + " or above 4096" : m);
+}
+int refuse_unknown_bits(const std::string& who, const char* word, uint32_t bits, uint32_t known) {
+    if (!(bits & ~known)) return SPL_OK;
+    char b[64];
+    snprintf(b, sizeof b, ": unknown %s bit 0x%x", word, bits & ~known);
+    return fail(SPL_EINVAL, who + b);
+}
 
 // What both calls refuse alike; `o` receives the options the kernels take.
 int collate_check(const std::string& who, bool pack, const spl_tokenizer* t, const uint64_t* d_out_off, uint64_t n_docs,
@@ -14,15 +27,8 @@ int collate_check(const std::string& who, bool pack, const spl_tokenizer* t, con
     if (!t) return fail(SPL_EINVAL, who + ": null handle");
     if (!d_out_off) return fail(SPL_EINVAL, who + ": d_out_off is null");
     if (!o_in) return fail(SPL_EINVAL, who + ": the options are null");
-    const uint32_t have = o_in->struct_size;      // the caller's struct may be longer than this library's: only the fields known here are read
-    if (have < sizeof(spl_collate_opts) || have > 4096)
-        return fail(SPL_EINVAL, who + ": spl_collate_opts.struct_size is not set: it is shorter than the struct's six fields (24 bytes) or above 4096");
-    const uint32_t known = SPL_COLLATE_I64 | SPL_COLLATE_PAD_LEFT | SPL_COLLATE_KEEP_TAIL | SPL_COLLATE_BOS | SPL_COLLATE_EOS;
-    if (o_in->flags & ~known) {
-        char b[64];
-        snprintf(b, sizeof b, ": unknown flag bit 0x%x", o_in->flags & ~known);
-        return fail(SPL_EINVAL, who + b);
-    }
+    SPL_TRY(refuse_struct_size(who, "spl_collate_opts", o_in->struct_size, sizeof(spl_collate_opts), "the struct's six fields (24 bytes)"));
+    SPL_TRY(refuse_unknown_bits(who, "flag", o_in->flags, SPL_COLLATE_I64 | SPL_COLLATE_PAD_LEFT | SPL_COLLATE_KEEP_TAIL | SPL_COLLATE_BOS | SPL_COLLATE_EOS));
     if (pack && (o_in->flags & (SPL_COLLATE_PAD_LEFT | SPL_COLLATE_KEEP_TAIL)))
         return fail(SPL_EINVAL, who + ": SPL_COLLATE_PAD_LEFT and SPL_COLLATE_KEEP_TAIL are pad-mode flags (pack mode neither pads a document nor truncates)");
     if (o_in->row_len == 0) return fail(SPL_EINVAL, who + ": row_len is 0");

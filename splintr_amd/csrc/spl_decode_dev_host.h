@@ -49,15 +49,8 @@ int decode_dev_check_in(const std::string& who, const spl_tokenizer* t, const vo
                         const int32_t* d_len, uint64_t n_docs, const spl_decode_opts* o, uint64_t* slots_out) {
     if (!t) return fail(SPL_EINVAL, who + ": null handle");
     if (!o) return fail(SPL_EINVAL, who + ": the options are null");
-    const uint32_t have = o->struct_size;         // the caller's struct may be longer than this library's: only the fields known here are read
-    if (have < sizeof(spl_decode_opts) || have > 4096)
-        return fail(SPL_EINVAL, who + ": spl_decode_opts.struct_size is not set: it is shorter than the struct's three fields (12 bytes) or above 4096");
-    const uint32_t known = SPL_DECODE_I64 | SPL_DECODE_PAD_LEFT | SPL_DECODE_SKIP_SPECIAL;
-    if (o->flags & ~known) {
-        char b[64];
-        snprintf(b, sizeof b, ": unknown flag bit 0x%x", o->flags & ~known);
-        return fail(SPL_EINVAL, who + b);
-    }
+    SPL_TRY(refuse_struct_size(who, "spl_decode_opts", o->struct_size, sizeof(spl_decode_opts), "the struct's three fields (12 bytes)"));
+    SPL_TRY(refuse_unknown_bits(who, "flag", o->flags, SPL_DECODE_I64 | SPL_DECODE_PAD_LEFT | SPL_DECODE_SKIP_SPECIAL));
     const bool rows = o->row_len != 0;
     if (n_docs >= (1ull << 31)) return fail(SPL_EINVAL, who + ": n_docs >= 2^31");
     if (!rows) {

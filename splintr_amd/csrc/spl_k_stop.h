@@ -24,18 +24,16 @@
 // at the first chunk with a hit.  Without a hit lane k (1 .. 63) asks whether the last k bytes of W begin a live stop longer than k: the
 // highest set bit of that ballot is h.  The table (4 160 bytes) is copied into LDS once per workgroup.
 //
-// Two shapes, as spl_k_stream.h.  n_seqs <= the handle's "stop_one_max" (SP_ONE_DEFAULT, at most SP_ONE_MAX): ONE launch of one workgroup
-// (k_stop_one: find every sequence's cut, keep cut and hit in LDS, scan the counts there, write).  Beyond: k_stop_len (cut, hit and count per
-// sequence into the scratch, sums per ST_SEQ_BLK sequences), k_decode_scan (spl_k_decode.h), k_stop_write (which only copies).  No atomics,
-// no polling, no workgroup waits for another; every output byte below min(need, capacity), every offset, every hit and every state word is
-// written exactly once; the write pass alone writes state_out and hit, by the wavefront that has read state_in[b] before: the two may be
-// one array.
+// The driver around a sequence is spl_k_seqscan.h's: one launch (k_stop_one) up to the handle's "stop_one_max" sequences (SP_ONE_DEFAULT), three
+// beyond (k_stop_len, k_decode_scan, k_stop_write).  The count pass finds cut and hit and hands them to the write pass, which only copies:
+// through LDS (a u64 and a u32 per sequence) or through the scratch (two u64).  The write pass alone writes state_out and hit, by a
+// wavefront that has read state_in[b] before: the two may be one array.
 //
 // The first half is plain C++ (values and pointers only): tests/hostsim/stop_sim.cpp includes it in a g++ build and evaluates it sequence by
 // sequence and lane by lane with a run-time lane count and chunk size; the kernels call exactly these functions.
 #pragma once
 #include "spl_common.h"
-#include "spl_k_stream.h"
+#include "spl_k_seqscan.h"
 
 #ifndef SPL_STOP_HALO
 #define SPL_STOP_HALO 63               /* bytes staged in front of a chunk: the longest stop less one (tests/hostsim builds a mutant with 62) */
@@ -52,9 +50,8 @@ constexpr uint32_t SP_SLOTS = 64, SP_MAX_LEN = 64, SP_TABLE_BYTES = 64 * 64 + 64
 constexpr uint32_t SP_TAIL_MAX = SP_MAX_LEN - 1;     // bytes of T a sequence keeps: what a stop that ends in a later step can reach back
 constexpr uint32_t SP_H = SPL_STOP_HALO;
 constexpr uint32_t SP_WAVE = 64;                     // lanes of a wavefront: end positions of a chunk
-constexpr uint32_t SP_NT = 256;                      // lanes per workgroup of the three-launch form (ST_SEQ_BLK sequences per workgroup)
-constexpr uint32_t SP_ONE_NT = 1024;                 // lanes of the one workgroup of the one-launch form
-constexpr uint32_t SP_ONE_MAX = 1024;                // most sequences the one-launch form can take (cut, hit and count are in LDS); option "stop_one_max"
+constexpr uint32_t SP_NT = SEQ_NT, SP_ONE_NT = SEQ_ONE_NT;     // the driver's workgroups (spl_k_seqscan.h)
+constexpr uint32_t SP_ONE_MAX = SEQ_ONE_MAX;         // most sequences the one-launch form can take (cut and hit are in LDS too); option "stop_one_max"
 constexpr uint32_t SP_ONE_DEFAULT = SPL_STOP_ONE_DEFAULT;
 static_assert(SP_ONE_DEFAULT <= SP_ONE_MAX, "the default threshold is one the kernel can take");
 static_assert(SP_H <= SP_TAIL_MAX && SP_TAIL_MAX < SP_WAVE, "lane k holds the suffix of k bytes; the tail fits eight words");
@@ -263,7 +260,7 @@ __device__ __forceinline__ void sp_emit(const SpIn& a, uint64_t b, SpWave& L, ui
     }
     const uint8_t* tail = reinterpret_cast<const uint8_t*>(&L.row[2]);
     const uint64_t count = sp_count(q, cut), r0 = q.L0 - q.h0;
-    for (uint64_t i = lane; i < count; i += SP_WAVE) st_put(out, cap, o0 + i, sp_w(tail, q.L0, a.in, q.lo, r0 + i));
+    for (uint64_t i = lane; i < count; i += SP_WAVE) seq_put(out, cap, o0 + i, sp_w(tail, q.L0, a.in, q.lo, r0 + i));
     const bool hit = sp_info_hit(info);
     const uint64_t end = hit ? sp_end_hit(a.flags, cut, sp_info_len(info)) : q.n;
     const uint32_t tl = sp_new_tail_len(hit, q.fin, end);
@@ -276,59 +273,39 @@ __device__ __forceinline__ void sp_emit(const SpIn& a, uint64_t b, SpWave& L, ui
     wave_lds_sync();
 }
 
-// ------------------------------------------------------------------------------------------ three launches
-// cnt[b], cut[b], inf[b]: what sequence b emits and where it is cut; blk[g]: the counts' sum over block g's ST_SEQ_BLK sequences
+// ------------------------------------------------------------------------------------------ the op and its kernels (spl_k_seqscan.h)
+struct SpCarry { uint64_t cut; uint32_t info; };
+template <class C, class I>
+struct SpKeep {
+    C* cut; I* inf;
+    __device__ __forceinline__ void put(uint64_t b, const SpCarry& k) const { cut[b] = k.cut; inf[b] = k.info; }
+    __device__ __forceinline__ SpCarry get(uint64_t b) const { return {cut[b], (uint32_t)inf[b]}; }
+};
+struct SpOp {
+    using Wave = SpWave;
+    using Carry = SpCarry;
+    const SpIn& a; const uint8_t* tab; uint8_t* out; uint64_t cap; uint64_t* state_out; int32_t* hit_out;
+    __device__ __forceinline__ uint64_t count(uint64_t b, SpWave& L, SpCarry& k) const { return sp_find(a, tab, b, L, k.cut, k.info); }
+    __device__ __forceinline__ void write(uint64_t b, SpWave& L, const SpCarry& k, uint64_t o0) const { sp_emit(a, b, L, k.cut, k.info, out, cap, o0, state_out, hit_out); }
+};
+
+// cut[b], inf[b]: where sequence b is cut, behind the driver's cnt[b]
 __global__ __launch_bounds__(SP_NT) void k_stop_len(SpIn a, uint64_t n_blk, uint64_t* __restrict__ cnt, uint64_t* __restrict__ cut,
                                                     uint64_t* __restrict__ inf, uint64_t* __restrict__ blk) {
     __shared__ __attribute__((aligned(16))) uint8_t s_tab[SP_TABLE_BYTES];
     __shared__ SpWave s_wave[SP_NT / 64];
     __shared__ uint64_t s_sum[SP_NT / 64];
-    const uint32_t wv = threadIdx.x >> 6;
     sp_load_table(a.table, s_tab);
     __syncthreads();
-    for (uint64_t g = blockIdx.x; g < n_blk; g += gridDim.x) {
-        uint64_t sum = 0;
-        for (uint32_t i = wv; i < ST_SEQ_BLK; i += SP_NT / 64) {
-            const uint64_t b = g * ST_SEQ_BLK + i;
-            if (b >= a.n_seqs) break;
-            uint64_t c_cut; uint32_t c_inf;
-            const uint64_t c = sp_find(a, s_tab, b, s_wave[wv], c_cut, c_inf);
-            if ((threadIdx.x & 63) == 0) { cnt[b] = c; cut[b] = c_cut; inf[b] = c_inf; }
-            sum += c;
-        }
-        if ((threadIdx.x & 63) == 0) s_sum[wv] = sum;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint64_t s = 0;
-            for (uint32_t w = 0; w < SP_NT / 64; w++) s += s_sum[w];
-            blk[g] = s;
-        }
-        __syncthreads();
-    }
+    seq_len_body(SpOp{a, s_tab, nullptr, 0, nullptr, nullptr}, SpKeep<uint64_t, uint64_t>{cut, inf}, a.n_seqs, n_blk, s_wave, s_sum, cnt, blk);
 }
-// blk: the exclusive scan of k_stop_len's sums, the total behind them
 __global__ __launch_bounds__(SP_NT) void k_stop_write(SpIn a, uint64_t n_blk, const uint64_t* __restrict__ cnt, const uint64_t* __restrict__ cut,
                                                       const uint64_t* __restrict__ inf, const uint64_t* __restrict__ blk,
                                                       uint8_t* __restrict__ out, uint64_t cap, uint64_t* __restrict__ out_off,
                                                       uint64_t* __restrict__ state_out, int32_t* __restrict__ hit_out) {
     __shared__ SpWave s_wave[SP_NT / 64];
-    const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (uint64_t g = blockIdx.x; g < n_blk; g += gridDim.x) {
-        const uint64_t b_lane = g * ST_SEQ_BLK + lane;
-        const uint64_t mine = lane < ST_SEQ_BLK && b_lane < a.n_seqs ? cnt[b_lane] : 0ull;
-        const uint64_t excl = st_wave_scan64(mine) - mine + blk[g];
-        for (uint32_t i = wv; i < ST_SEQ_BLK; i += SP_NT / 64) {
-            const uint64_t b = g * ST_SEQ_BLK + i;
-            if (b >= a.n_seqs) break;
-            const uint64_t o0 = (uint64_t)__shfl((unsigned long long)excl, (int)i);
-            sp_emit(a, b, s_wave[wv], cut[b], (uint32_t)inf[b], out, cap, o0, state_out, hit_out);
-            if (lane == 0) out_off[b] = o0;
-        }
-        if (g == 0 && threadIdx.x == 0) out_off[a.n_seqs] = blk[n_blk];
-    }
+    seq_write_body(SpOp{a, nullptr, out, cap, state_out, hit_out}, SpKeep<const uint64_t, const uint64_t>{cut, inf}, a.n_seqs, n_blk, s_wave, cnt, blk, out_off);
 }
-
-// ------------------------------------------------------------------------------------------ one launch (n_seqs <= SP_ONE_MAX)
 __global__ __launch_bounds__(SP_ONE_NT) void k_stop_one(SpIn a, uint8_t* __restrict__ out, uint64_t cap, uint64_t* __restrict__ out_off,
                                                         uint64_t* __restrict__ state_out, int32_t* __restrict__ hit_out) {
     __shared__ __attribute__((aligned(16))) uint8_t s_tab[SP_TABLE_BYTES];
@@ -336,32 +313,9 @@ __global__ __launch_bounds__(SP_ONE_NT) void k_stop_one(SpIn a, uint8_t* __restr
     __shared__ uint64_t s_cnt[SP_ONE_MAX + 1];
     __shared__ uint64_t s_cut[SP_ONE_MAX];
     __shared__ uint32_t s_inf[SP_ONE_MAX];
-    const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const uint32_t n = (uint32_t)a.n_seqs;
     sp_load_table(a.table, s_tab);
     __syncthreads();
-    for (uint32_t b = wv; b < n; b += SP_ONE_NT / 64) {
-        uint64_t c_cut; uint32_t c_inf;
-        const uint64_t c = sp_find(a, s_tab, b, s_wave[wv], c_cut, c_inf);
-        if (lane == 0) { s_cnt[b] = c; s_cut[b] = c_cut; s_inf[b] = c_inf; }
-    }
-    __syncthreads();
-    if (wv == 0) {
-        uint64_t carry = 0;
-        for (uint32_t base = 0; base < n; base += 64) {
-            const uint64_t v = base + lane < n ? s_cnt[base + lane] : 0ull;
-            const uint64_t x = st_wave_scan64(v);
-            if (base + lane < n) s_cnt[base + lane] = carry + x - v;
-            carry += (uint64_t)__shfl((unsigned long long)x, 63);
-        }
-        if (lane == 0) { s_cnt[n] = carry; out_off[n] = carry; }
-    }
-    __syncthreads();
-    for (uint32_t b = wv; b < n; b += SP_ONE_NT / 64) {
-        const uint64_t o0 = s_cnt[b];
-        sp_emit(a, b, s_wave[wv], s_cut[b], s_inf[b], out, cap, o0, state_out, hit_out);
-        if (lane == 0) out_off[b] = o0;
-    }
+    seq_one_body(SpOp{a, s_tab, out, cap, state_out, hit_out}, SpKeep<uint64_t, uint32_t>{s_cut, s_inf}, (uint32_t)a.n_seqs, s_wave, s_cnt, out_off);
 }
 #endif  // __HIPCC__
 

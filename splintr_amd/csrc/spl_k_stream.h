@@ -26,16 +26,16 @@
 // A ballot gives the roles; hold mode takes the first non-copy position (count of trailing zeros), replace mode scans the per-byte output
 // lengths {0, 1, 3}.  Between windows the carry is the state word itself: feeding a decoder window by window is feeding it step by step.
 //
-// Two shapes.  n_seqs <= the handle's "stream_one_max" (ST_ONE_DEFAULT, at most ST_ONE_MAX): ONE launch of one workgroup (k_stream_one: count every sequence, scan the counts in LDS, write).
-// Beyond: k_stream_len (per-sequence counts, sums per ST_SEQ_BLK sequences), k_decode_scan (spl_k_decode.h), k_stream_write.  No atomics,
-// no polling, no workgroup waits for another; every output byte below min(need, capacity), every offset and every state word is written
-// exactly once; the write pass alone writes state_out, by the wavefront that has read state_in[b] before: the two may be one array.
+// The driver around a sequence is spl_k_seqscan.h's: one launch (k_stream_one) up to the handle's "stream_one_max" sequences (ST_ONE_DEFAULT),
+// three beyond (k_stream_len, k_decode_scan, k_stream_write); the count hands the write nothing.  The write pass alone writes state_out, by
+// a wavefront that has read state_in[b] before: the two may be one array.
 //
 // The first half is plain C++ (values and pointers only): tests/hostsim/stream_sim.cpp includes it in a g++ build and evaluates it sequence
 // by sequence and lane by lane with a run-time window and chunk size; the kernels call exactly these functions.
 #pragma once
 #include "spl_common.h"
 #include "spl_k_decode_dev.h"
+#include "spl_k_seqscan.h"
 
 #ifndef SPL_STREAM_HALO
 #define SPL_STREAM_HALO 3              /* bytes either side of a byte that decide its role (tests/hostsim builds a mutant with 2) */
@@ -50,14 +50,11 @@ namespace spl {
 constexpr uint32_t ST_REPLACE = 1u, ST_FINAL_ALL = 2u;
 constexpr uint32_t ST_H = SPL_STREAM_HALO;
 constexpr uint32_t ST_WAVE = 64;                    // lanes of a wavefront: slots of a window, bytes of a chunk
-constexpr uint32_t ST_NT = 256;                     // lanes per workgroup of the three-launch form
-constexpr uint32_t ST_SEQ_BLK = 16;                 // sequences per workgroup there (four per wavefront)
-constexpr uint32_t ST_ONE_NT = 1024;                // lanes of the one workgroup of the one-launch form
-constexpr uint32_t ST_ONE_MAX = 1024;                // most sequences the one-launch form can take (its counts are in LDS); option "stream_one_max"
+constexpr uint32_t ST_NT = SEQ_NT, ST_ONE_NT = SEQ_ONE_NT;     // the driver's workgroups (spl_k_seqscan.h)
+constexpr uint32_t ST_ONE_MAX = SEQ_ONE_MAX;        // most sequences the one-launch form can take; option "stream_one_max"
 constexpr uint32_t ST_ONE_DEFAULT = SPL_STREAM_ONE_DEFAULT;
 static_assert(ST_ONE_DEFAULT <= ST_ONE_MAX, "the default threshold is one the kernel can take");
 static_assert(ST_H >= 1 && ST_H <= 3, "a role looks at most three bytes either way");
-static_assert(ST_SEQ_BLK <= ST_WAVE, "one wave scan gives a block's starts");
 
 struct StIn {
     const void* ids; const int32_t* len; const uint8_t* fin; const uint64_t* state_in;
@@ -181,8 +178,6 @@ SPL_HD uint32_t st_nbr(const uint8_t* stage, uint32_t lane, uint32_t p0, uint32_
     return have;
 }
 SPL_HD bool st_final(const StIn& a, uint64_t b) { return (a.sflags & ST_FINAL_ALL) || (a.fin && a.fin[b]); }
-// blocks of the three-launch form: block 0 exists even for no sequence (it writes the closing offset)
-SPL_HD uint64_t st_n_blocks(uint64_t n_seqs) { const uint64_t n = (n_seqs + ST_SEQ_BLK - 1) / ST_SEQ_BLK; return n ? n : 1; }
 
 #if defined(__HIPCC__)
 // ------------------------------------------------------------------------------------------ one sequence, one wavefront
@@ -191,7 +186,6 @@ struct StWave {
     uint32_t src[ST_WAVE + 4];
     uint8_t byte[ST_WAVE + 16];        // a chunk and its two halos
 };
-__device__ __forceinline__ void st_put(uint8_t* __restrict__ out, uint64_t cap, uint64_t o, uint32_t x) { if (o < cap) out[o] = (uint8_t)x; }
 
 // The bytes sequence b emits, counted (WRITE false) or written from o0 on, with its state word.  Every lane of the wavefront calls it.
 template <bool I64, bool WRITE>
@@ -232,15 +226,15 @@ __device__ __forceinline__ uint64_t st_seq(const StIn& a, const DecTab& t, uint6
                 const uint64_t bad = __ballot(active && r >= ST_R_BAD);
                 const uint32_t first = bad ? (uint32_t)__builtin_ctzll(bad) : ST_WAVE;
                 const uint32_t n_copy = first < n - p0 ? first : n - p0;
-                if (WRITE && lane < n_copy) st_put(out, cap, o + lane, x);
+                if (WRITE && lane < n_copy) seq_put(out, cap, o + lane, x);
                 o += n_copy;
                 if (bad) { next = (uint64_t)__shfl((unsigned long long)mine, (int)first); stop = true; }
             } else {
                 const uint32_t l = r & 3u, li = wave_scan_incl(l);
                 if (WRITE) {
                     const uint64_t at = o + li - l;
-                    if (l == 1) st_put(out, cap, at, x);
-                    else if (l == 3) { st_put(out, cap, at, 0xEF); st_put(out, cap, at + 1, 0xBF); st_put(out, cap, at + 2, 0xBD); }
+                    if (l == 1) seq_put(out, cap, at, x);
+                    else if (l == 3) { seq_put(out, cap, at, 0xEF); seq_put(out, cap, at + 1, 0xBF); seq_put(out, cap, at + 2, 0xBD); }
                 }
                 o += (uint32_t)__shfl((int)li, 63);
                 const uint64_t pm = __ballot(active && r == ST_R_PEND);
@@ -252,7 +246,7 @@ __device__ __forceinline__ uint64_t st_seq(const StIn& a, const DecTab& t, uint6
         state = next;
     }
     if (st_final(a, b) && !st_stalled(state) && st_count(state)) {
-        if (WRITE && lane < 3) st_put(out, cap, o + lane, lane == 0 ? 0xEFu : lane == 1 ? 0xBFu : 0xBDu);
+        if (WRITE && lane < 3) seq_put(out, cap, o + lane, lane == 0 ? 0xEFu : lane == 1 ? 0xBFu : 0xBDu);
         o += 3;
         state = 0;
     }
@@ -260,89 +254,35 @@ __device__ __forceinline__ uint64_t st_seq(const StIn& a, const DecTab& t, uint6
     return o - o0;
 }
 
-// ------------------------------------------------------------------------------------------ three launches
-// cnt[b]: the bytes sequence b emits; blk[g]: their sum over block g's ST_SEQ_BLK sequences (k_decode_scan scans those)
+// ------------------------------------------------------------------------------------------ the op and its kernels (spl_k_seqscan.h)
+template <bool I64>
+struct StOp {
+    using Wave = StWave;
+    using Carry = SeqNoCarry;
+    const StIn& a; const DecTab& t; uint8_t* out; uint64_t cap; uint64_t* state_out;
+    __device__ __forceinline__ uint64_t count(uint64_t b, StWave& L, SeqNoCarry&) const { return st_seq<I64, false>(a, t, b, L, nullptr, 0, 0, nullptr); }
+    __device__ __forceinline__ void write(uint64_t b, StWave& L, const SeqNoCarry&, uint64_t o0) const { st_seq<I64, true>(a, t, b, L, out, cap, o0, state_out); }
+};
+
 template <bool I64>
 __global__ __launch_bounds__(ST_NT) void k_stream_len(StIn a, DecTab t, uint64_t n_blk, uint64_t* __restrict__ cnt, uint64_t* __restrict__ blk) {
     __shared__ StWave s_wave[ST_NT / 64];
     __shared__ uint64_t s_sum[ST_NT / 64];
-    const uint32_t wv = threadIdx.x >> 6;
-    for (uint64_t g = blockIdx.x; g < n_blk; g += gridDim.x) {
-        uint64_t sum = 0;
-        for (uint32_t i = wv; i < ST_SEQ_BLK; i += ST_NT / 64) {
-            const uint64_t b = g * ST_SEQ_BLK + i;
-            if (b >= a.n_seqs) break;
-            const uint64_t c = st_seq<I64, false>(a, t, b, s_wave[wv], nullptr, 0, 0, nullptr);
-            if ((threadIdx.x & 63) == 0) cnt[b] = c;
-            sum += c;
-        }
-        if ((threadIdx.x & 63) == 0) s_sum[wv] = sum;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint64_t s = 0;
-            for (uint32_t w = 0; w < ST_NT / 64; w++) s += s_sum[w];
-            blk[g] = s;
-        }
-        __syncthreads();
-    }
+    seq_len_body(StOp<I64>{a, t, nullptr, 0, nullptr}, SeqNoKeep{}, a.n_seqs, n_blk, s_wave, s_sum, cnt, blk);
 }
-__device__ __forceinline__ uint64_t st_wave_scan64(uint64_t v) {
-    uint64_t x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint64_t y = (uint64_t)__shfl_up((unsigned long long)x, d); if ((int)(threadIdx.x & 63) >= d) x += y; }
-    return x;
-}
-// blk: the exclusive scan of k_stream_len's sums, the total behind them
 template <bool I64>
 __global__ __launch_bounds__(ST_NT) void k_stream_write(StIn a, DecTab t, uint64_t n_blk, const uint64_t* __restrict__ cnt,
                                                         const uint64_t* __restrict__ blk, uint8_t* __restrict__ out, uint64_t cap,
                                                         uint64_t* __restrict__ out_off, uint64_t* __restrict__ state_out) {
     __shared__ StWave s_wave[ST_NT / 64];
-    const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (uint64_t g = blockIdx.x; g < n_blk; g += gridDim.x) {
-        const uint64_t b_lane = g * ST_SEQ_BLK + lane;
-        const uint64_t mine = lane < ST_SEQ_BLK && b_lane < a.n_seqs ? cnt[b_lane] : 0ull;
-        const uint64_t excl = st_wave_scan64(mine) - mine + blk[g];
-        for (uint32_t i = wv; i < ST_SEQ_BLK; i += ST_NT / 64) {
-            const uint64_t b = g * ST_SEQ_BLK + i;
-            if (b >= a.n_seqs) break;
-            const uint64_t o0 = (uint64_t)__shfl((unsigned long long)excl, (int)i);
-            st_seq<I64, true>(a, t, b, s_wave[wv], out, cap, o0, state_out);
-            if (lane == 0) out_off[b] = o0;
-        }
-        if (g == 0 && threadIdx.x == 0) out_off[a.n_seqs] = blk[n_blk];
-    }
+    seq_write_body(StOp<I64>{a, t, out, cap, state_out}, SeqNoKeep{}, a.n_seqs, n_blk, s_wave, cnt, blk, out_off);
 }
-
-// ------------------------------------------------------------------------------------------ one launch (n_seqs <= ST_ONE_MAX)
 template <bool I64>
 __global__ __launch_bounds__(ST_ONE_NT) void k_stream_one(StIn a, DecTab t, uint8_t* __restrict__ out, uint64_t cap, uint64_t* __restrict__ out_off,
                                                           uint64_t* __restrict__ state_out) {
     __shared__ StWave s_wave[ST_ONE_NT / 64];
     __shared__ uint64_t s_cnt[ST_ONE_MAX + 1];
-    const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const uint32_t n = (uint32_t)a.n_seqs;
-    for (uint32_t b = wv; b < n; b += ST_ONE_NT / 64) {
-        const uint64_t c = st_seq<I64, false>(a, t, b, s_wave[wv], nullptr, 0, 0, nullptr);
-        if (lane == 0) s_cnt[b] = c;
-    }
-    __syncthreads();
-    if (wv == 0) {
-        uint64_t carry = 0;
-        for (uint32_t base = 0; base < n; base += 64) {
-            const uint64_t v = base + lane < n ? s_cnt[base + lane] : 0ull;
-            const uint64_t x = st_wave_scan64(v);
-            if (base + lane < n) s_cnt[base + lane] = carry + x - v;
-            carry += (uint64_t)__shfl((unsigned long long)x, 63);
-        }
-        if (lane == 0) { s_cnt[n] = carry; out_off[n] = carry; }
-    }
-    __syncthreads();
-    for (uint32_t b = wv; b < n; b += ST_ONE_NT / 64) {
-        const uint64_t o0 = s_cnt[b];
-        st_seq<I64, true>(a, t, b, s_wave[wv], out, cap, o0, state_out);
-        if (lane == 0) out_off[b] = o0;
-    }
+    seq_one_body(StOp<I64>{a, t, out, cap, state_out}, SeqNoKeep{}, (uint32_t)a.n_seqs, s_wave, s_cnt, out_off);
 }
 #endif  // __HIPCC__
 

@@ -22,6 +22,7 @@
 //   spl_k_window.h     k_window_scan / _totals / _add / _gather: the CSR as overlapping windows of every document (rows per document by a scan over launches)
 //   spl_k_decode_dev.h k_dec_len / k_dec_gather: ids in HBM (CSR or rows) to a bytes CSR in HBM (and their host-testable mapping)
 //   spl_k_spans.h      k_span_len / k_span_write: ids in HBM (CSR or rows) to per-id byte and character spans (and their host-testable mapping)
+//   spl_k_seqscan.h    seq_one_body / seq_len_body / seq_write_body: the count-scan-write driver of the per-sequence ops below, one launch or three
 //   spl_k_stream.h     k_stream_one / k_stream_len / k_stream_write: one step of B streaming decoders, per-sequence UTF-8 state (and their host-testable mapping)
 //   spl_k_stop.h       k_stop_one / k_stop_len / k_stop_write: stop strings over the streaming decode's bytes, per-sequence match state and hold-back (and their host-testable mapping)
 //   (spl_rx_split.h, included by spl_api.hip: the device splitter for custom split patterns; its host half is in spl_launch.h)

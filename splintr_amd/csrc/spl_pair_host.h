@@ -17,18 +17,11 @@ int pair_device(spl_tokenizer* t, const uint32_t* d_a_ids, const uint64_t* d_a_o
     if (!d_rows) return fail(SPL_EINVAL, who + ": d_rows is null");
     if (!d_a_off || !d_b_off) return fail(SPL_EINVAL, who + (d_a_off ? ": d_b_off is null" : ": d_a_off is null"));
     if (!d_status) return fail(SPL_EINVAL, who + ": d_status is null");
-    const uint32_t have = o_in->struct_size;      // the caller's struct may be longer than this library's: only the fields known here are read
-    if (have < sizeof(spl_pair_opts) || have > 4096)
-        return fail(SPL_EINVAL, who + ": spl_pair_opts.struct_size is not set: it is shorter than the struct (416 bytes) or above 4096");
+    SPL_TRY(refuse_struct_size(who, "spl_pair_opts", o_in->struct_size, sizeof(spl_pair_opts), "the struct (416 bytes)"));
     if (o_in->flags & (SPL_COLLATE_KEEP_TAIL | SPL_COLLATE_BOS | SPL_COLLATE_EOS))
         return fail(SPL_EINVAL, who + ": SPL_COLLATE_KEEP_TAIL, _BOS and _EOS are not flags of this call: the fixed segments (prefix, middle, "
                                       "suffix) take the place of BOS and EOS, SPL_PAIR_KEEP_TAIL_A / _B that of KEEP_TAIL");
-    const uint32_t known = SPL_COLLATE_I64 | SPL_COLLATE_PAD_LEFT | SPL_PAIR_KEEP_TAIL_A | SPL_PAIR_KEEP_TAIL_B;
-    if (o_in->flags & ~known) {
-        char b[64];
-        snprintf(b, sizeof b, ": unknown flag bit 0x%x", o_in->flags & ~known);
-        return fail(SPL_EINVAL, who + b);
-    }
+    SPL_TRY(refuse_unknown_bits(who, "flag", o_in->flags, SPL_COLLATE_I64 | SPL_COLLATE_PAD_LEFT | SPL_PAIR_KEEP_TAIL_A | SPL_PAIR_KEEP_TAIL_B));
     if (o_in->trunc > SPL_PAIR_ONLY_SECOND) return fail(SPL_EINVAL, who + ": trunc is none of SPL_PAIR_LONGEST_FIRST, _ONLY_FIRST, _ONLY_SECOND");
     if (o_in->n_prefix > SPL_PAIR_MAX_FIXED || o_in->n_middle > SPL_PAIR_MAX_FIXED || o_in->n_suffix > SPL_PAIR_MAX_FIXED)
         return fail(SPL_EINVAL, who + ": a fixed segment (n_prefix, n_middle, n_suffix) holds more than SPL_PAIR_MAX_FIXED ids");

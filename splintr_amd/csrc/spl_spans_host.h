@@ -14,11 +14,7 @@ int token_spans_device(spl_tokenizer* t, const void* d_ids, uint64_t n_ids_cap, 
     uint64_t slots = 0;
     SPL_TRY(decode_dev_check_in(who, t, d_ids, n_ids_cap, d_ids_off, d_len, n_docs, o, &slots));
     SPL_TRY(decode_dev_check_ids_aligned(who, d_ids, o));
-    if (span_flags & ~SPL_SPANS_I64) {
-        char b[64];
-        snprintf(b, sizeof b, ": unknown span_flags bit 0x%x", span_flags & ~SPL_SPANS_I64);
-        return fail(SPL_EINVAL, who + b);
-    }
+    SPL_TRY(refuse_unknown_bits(who, "span_flags", span_flags, SPL_SPANS_I64));
     if (!d_byte_off) return fail(SPL_EINVAL, who + ": d_byte_off is null");
     if (col_misaligned(d_byte_span, 16)) return fail(SPL_EINVAL, who + ": d_byte_span is not 16-byte aligned");
     if (col_misaligned(d_char_span, 16)) return fail(SPL_EINVAL, who + ": d_char_span is not 16-byte aligned");

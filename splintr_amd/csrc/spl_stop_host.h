@@ -1,6 +1,6 @@
 // spl_stop_host.h -- the host half of spl_stop_reserve_device / spl_stop_match_device: the refusals (all of them before the handle or the
 // device is touched), the scratch (Ctx::d_spblk: the block sums, the total behind them, and count, cut and hit per sequence -- 24 bytes per
-// sequence and 8 per 16 of them, grow-only, shared with nothing) and the launches (spl_k_stop.h; k_decode_scan of spl_k_decode.h).  The
+// sequence and 8 per 16 of them, grow-only, shared with nothing) and the launches (spl_k_stop.h through spl_seqscan_host.h).  The
 // handle gives its device and its scratch, nothing else: no table of the tokenizer is read.  A call within what was reserved neither
 // allocates nor synchronises.
 #pragma once
@@ -20,8 +20,7 @@ struct StopReq {
 
 int stop_prepare(Ctx* c, uint64_t max_seqs) {
     HIP_TRY(hipSetDevice(c->device));
-    const uint64_t need = st_n_blocks(max_seqs) + 1 + 3 * max_seqs;
-    return c->d_spblk.grow(&c->spblk_cap, need, need + need / 4 + 64);
+    return seq_scratch_grow(c->d_spblk, &c->spblk_cap, max_seqs, 3);
 }
 
 int stop_reserve_device(spl_tokenizer* t, uint64_t max_seqs) {
@@ -43,12 +42,7 @@ int stop_match_device(spl_tokenizer* t, const StopReq& q) {
     if (!q.in && q.in_cap) return fail(SPL_EINVAL, who + ": d_in_bytes is null with in_capacity > 0");
     if (!q.out && q.out_cap) return fail(SPL_EINVAL, who + ": d_out_bytes is null with out_capacity > 0");
     if (col_misaligned(q.out, 16)) return fail(SPL_EINVAL, who + ": d_out_bytes is not 16-byte aligned");
-    const uint32_t known = SPL_STOP_INCLUDE | SPL_STOP_FINAL_ALL;
-    if (q.flags & ~known) {
-        char b[64];
-        snprintf(b, sizeof b, ": unknown stop_flags bit 0x%x", q.flags & ~known);
-        return fail(SPL_EINVAL, who + b);
-    }
+    SPL_TRY(refuse_unknown_bits(who, "stop_flags", q.flags, SPL_STOP_INCLUDE | SPL_STOP_FINAL_ALL));
     if (q.n_seqs >= (1ull << 31)) return fail(SPL_EINVAL, who + ": n_seqs >= 2^31");
 
     Ctx* c = t->ctx[0].get();
@@ -56,20 +50,14 @@ int stop_match_device(spl_tokenizer* t, const StopReq& q) {
     SpIn a{};
     a.in = q.in; a.in_cap = q.in_cap; a.in_off = q.in_off; a.n_seqs = q.n_seqs; a.table = q.table; a.mask = q.mask; a.fin = q.fin;
     a.flags = q.flags; a.state_in = q.state_in;
-    if (q.n_seqs <= t->stop_one_max) {
-        hipLaunchKernelGGL(k_stop_one, dim3(1), dim3(SP_ONE_NT), 0, q.stream, a, q.out, q.out_cap, q.out_off, q.state_out, q.hit);
-    } else {
-        const uint64_t n_blk = st_n_blocks(q.n_seqs);
-        const dim3 grid((uint32_t)n_blk), wg(SP_NT);             // (n_seqs < 2^31: fewer than 2^27 blocks)
-        uint64_t* blk = c->d_spblk.get();
-        uint64_t* cnt = blk + n_blk + 1;
-        uint64_t* cut = cnt + q.n_seqs;
-        uint64_t* inf = cut + q.n_seqs;
-        hipLaunchKernelGGL(k_stop_len, grid, wg, 0, q.stream, a, n_blk, cnt, cut, inf, blk);
-        hipLaunchKernelGGL(k_decode_scan, dim3(1), dim3(1024), 0, q.stream, blk, n_blk);
-        hipLaunchKernelGGL(k_stop_write, grid, wg, 0, q.stream, a, n_blk, (const uint64_t*)cnt, (const uint64_t*)cut, (const uint64_t*)inf,
-                           (const uint64_t*)blk, q.out, q.out_cap, q.out_off, q.state_out, q.hit);
-    }
+    const SeqScratch s{q.n_seqs, c->d_spblk.get()};
+    const uint64_t n_blk = s.n_blk(), *cnt = s.per_seq(0), *cut = s.per_seq(1), *inf = s.per_seq(2), *blk = s.blk;
+    seq_launch(s, t->stop_one_max, q.stream,
+        [&] { hipLaunchKernelGGL(k_stop_one, dim3(1), dim3(SP_ONE_NT), 0, q.stream, a, q.out, q.out_cap, q.out_off, q.state_out, q.hit); },
+        [&](dim3 grid, dim3 wg) { hipLaunchKernelGGL(k_stop_len, grid, wg, 0, q.stream, a, n_blk, s.per_seq(0), s.per_seq(1), s.per_seq(2), s.blk); },
+        [&](dim3 grid, dim3 wg) {
+            hipLaunchKernelGGL(k_stop_write, grid, wg, 0, q.stream, a, n_blk, cnt, cut, inf, blk, q.out, q.out_cap, q.out_off, q.state_out, q.hit);
+        });
     HIP_TRY(hipGetLastError());
     return SPL_OK;
 }

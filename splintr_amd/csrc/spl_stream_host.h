@@ -1,7 +1,7 @@
 // spl_stream_host.h -- the host half of spl_stream_reserve_device / spl_stream_decode_device: the refusals (all of them before the handle or
 // the device is touched), the scratch (Ctx::d_stblk: the block sums, the total behind them and one count per sequence -- 8 bytes per
-// sequence and 8 per 16 of them, grow-only, shared with nothing) and the launches (spl_k_stream.h; k_decode_scan of spl_k_decode.h).  A call
-// within what was reserved neither allocates nor synchronises.
+// sequence and 8 per 16 of them, grow-only, shared with nothing) and the launches (spl_k_stream.h through spl_seqscan_host.h).  A call within
+// what was reserved neither allocates nor synchronises.
 #pragma once
 namespace {
 
@@ -18,8 +18,7 @@ struct StreamReq {
 int stream_prepare(spl_tokenizer* t, Ctx* c, uint64_t max_seqs) {
     HIP_TRY(hipSetDevice(c->device));
     SPL_TRY(upload_decode(t, c));
-    const uint64_t need = st_n_blocks(max_seqs) + 1 + max_seqs;
-    return c->d_stblk.grow(&c->stblk_cap, need, need + need / 4 + 64);
+    return seq_scratch_grow(c->d_stblk, &c->stblk_cap, max_seqs, 1);
 }
 
 int stream_reserve_device(spl_tokenizer* t, uint64_t max_seqs) {
@@ -36,19 +35,9 @@ int stream_decode_device(spl_tokenizer* t, const StreamReq& q) {
     if (!q.state_in) return fail(SPL_EINVAL, who + ": d_state_in is null");
     if (!q.state_out) return fail(SPL_EINVAL, who + ": d_state_out is null");
     if (!q.out_off) return fail(SPL_EINVAL, who + ": d_out_off is null");
-    const uint32_t have = q.o->struct_size;       // the caller's struct may be longer than this library's: only the fields known here are read
-    if (have < sizeof(spl_decode_opts) || have > 4096)
-        return fail(SPL_EINVAL, who + ": spl_decode_opts.struct_size is not set: it is shorter than the struct's three fields (12 bytes) or above 4096");
-    const uint32_t known = SPL_DECODE_I64 | SPL_DECODE_PAD_LEFT | SPL_DECODE_SKIP_SPECIAL, sknown = SPL_STREAM_REPLACE | SPL_STREAM_FINAL_ALL;
-    char b[64];
-    if (q.o->flags & ~known) {
-        snprintf(b, sizeof b, ": unknown flag bit 0x%x", q.o->flags & ~known);
-        return fail(SPL_EINVAL, who + b);
-    }
-    if (q.stream_flags & ~sknown) {
-        snprintf(b, sizeof b, ": unknown stream_flags bit 0x%x", q.stream_flags & ~sknown);
-        return fail(SPL_EINVAL, who + b);
-    }
+    SPL_TRY(refuse_struct_size(who, "spl_decode_opts", q.o->struct_size, sizeof(spl_decode_opts), "the struct's three fields (12 bytes)"));
+    SPL_TRY(refuse_unknown_bits(who, "flag", q.o->flags, SPL_DECODE_I64 | SPL_DECODE_PAD_LEFT | SPL_DECODE_SKIP_SPECIAL));
+    SPL_TRY(refuse_unknown_bits(who, "stream_flags", q.stream_flags, SPL_STREAM_REPLACE | SPL_STREAM_FINAL_ALL));
     if (q.o->row_len == 0) return fail(SPL_EINVAL, who + ": row_len is 0 (rows mode only: ids [n_seqs, row_len], row_len >= 1)");
     if (q.o->flags & SPL_DECODE_PAD_LEFT) return fail(SPL_EINVAL, who + ": SPL_DECODE_PAD_LEFT is refused (a step's ids are a row's first d_len[b])");
     if (q.n_seqs >= (1ull << 31)) return fail(SPL_EINVAL, who + ": n_seqs >= 2^31");
@@ -63,20 +52,21 @@ int stream_decode_device(spl_tokenizer* t, const StreamReq& q) {
     a.row_len = q.o->row_len; a.dflags = q.o->flags; a.sflags = q.stream_flags;
     const DecTab tab = decode_dev_tab(c);
     const bool i64 = (q.o->flags & SPL_DECODE_I64) != 0;
-    if (q.n_seqs <= t->stream_one_max) {
-        if (i64) hipLaunchKernelGGL(k_stream_one<true>, dim3(1), dim3(ST_ONE_NT), 0, q.stream, a, tab, q.bytes, q.bytes_cap, q.out_off, q.state_out);
-        else hipLaunchKernelGGL(k_stream_one<false>, dim3(1), dim3(ST_ONE_NT), 0, q.stream, a, tab, q.bytes, q.bytes_cap, q.out_off, q.state_out);
-    } else {
-        const uint64_t n_blk = st_n_blocks(q.n_seqs);
-        const dim3 grid((uint32_t)n_blk), wg(ST_NT);             // (n_seqs < 2^31: fewer than 2^27 blocks)
-        uint64_t* blk = c->d_stblk.get();
-        uint64_t* cnt = blk + n_blk + 1;
-        if (i64) hipLaunchKernelGGL(k_stream_len<true>, grid, wg, 0, q.stream, a, tab, n_blk, cnt, blk);
-        else hipLaunchKernelGGL(k_stream_len<false>, grid, wg, 0, q.stream, a, tab, n_blk, cnt, blk);
-        hipLaunchKernelGGL(k_decode_scan, dim3(1), dim3(1024), 0, q.stream, blk, n_blk);
-        if (i64) hipLaunchKernelGGL(k_stream_write<true>, grid, wg, 0, q.stream, a, tab, n_blk, (const uint64_t*)cnt, (const uint64_t*)blk, q.bytes, q.bytes_cap, q.out_off, q.state_out);
-        else hipLaunchKernelGGL(k_stream_write<false>, grid, wg, 0, q.stream, a, tab, n_blk, (const uint64_t*)cnt, (const uint64_t*)blk, q.bytes, q.bytes_cap, q.out_off, q.state_out);
-    }
+    const SeqScratch s{q.n_seqs, c->d_stblk.get()};
+    const uint64_t n_blk = s.n_blk(), *cnt = s.per_seq(0), *blk = s.blk;
+    seq_launch(s, t->stream_one_max, q.stream,
+        [&] {
+            if (i64) hipLaunchKernelGGL(k_stream_one<true>, dim3(1), dim3(ST_ONE_NT), 0, q.stream, a, tab, q.bytes, q.bytes_cap, q.out_off, q.state_out);
+            else hipLaunchKernelGGL(k_stream_one<false>, dim3(1), dim3(ST_ONE_NT), 0, q.stream, a, tab, q.bytes, q.bytes_cap, q.out_off, q.state_out);
+        },
+        [&](dim3 grid, dim3 wg) {
+            if (i64) hipLaunchKernelGGL(k_stream_len<true>, grid, wg, 0, q.stream, a, tab, n_blk, s.per_seq(0), s.blk);
+            else hipLaunchKernelGGL(k_stream_len<false>, grid, wg, 0, q.stream, a, tab, n_blk, s.per_seq(0), s.blk);
+        },
+        [&](dim3 grid, dim3 wg) {
+            if (i64) hipLaunchKernelGGL(k_stream_write<true>, grid, wg, 0, q.stream, a, tab, n_blk, cnt, blk, q.bytes, q.bytes_cap, q.out_off, q.state_out);
+            else hipLaunchKernelGGL(k_stream_write<false>, grid, wg, 0, q.stream, a, tab, n_blk, cnt, blk, q.bytes, q.bytes_cap, q.out_off, q.state_out);
+        });
     HIP_TRY(hipGetLastError());
     return SPL_OK;
 }

@@ -17,6 +17,20 @@ from . import _ffi
 from .tokenizer import Tokenizer, _pack
 
 
+def _raise_rc(rc: int, name: str):             # what the library refused (SPL_EINVAL) is a ValueError, anything else a RuntimeError
+    raise (ValueError if rc == -1 else RuntimeError)(f"{name} failed ({rc}): {_ffi.last_error()}")
+
+
+def _ptr(t):                                   # an optional tensor's address: null for None, True or an empty tensor
+    return t.data_ptr() if isinstance(t, torch.Tensor) and t.numel() else None
+
+
+def _vec(name: str, t, B: int, dtypes, what: str):            # (name, t) for a per-sequence argument of a batch of B
+    if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or t.dim() != 1 or t.shape[0] != B or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {what} tensor of shape [batch]")
+    return name, t
+
+
 class DeviceBatch:
     """A packed corpus resident on one GPU plus preallocated output buffers."""
 
@@ -103,7 +117,7 @@ def pad_device(tok: Tokenizer, batch: DeviceBatch, max_length: int, *, pad_id: i
     rc = _ffi.lib().spl_pad_device(tok.handle, batch.ids.data_ptr(), batch.out_off.data_ptr(), batch.n_docs, ctypes.byref(o),
                                    rows.data_ptr(), mask.data_ptr(), lens.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
-        raise (ValueError if rc == -1 else RuntimeError)(f"spl_pad_device failed ({rc}): {_ffi.last_error()}")
+        _raise_rc(rc, "spl_pad_device")
     return rows, mask, lens
 
 
@@ -128,7 +142,7 @@ def pack_device(tok: Tokenizer, batch: DeviceBatch, seq_len: int, *, pad_id: int
                                     rows.data_ptr(), int(max_rows), doc.data_ptr(), pos.data_ptr(), n.data_ptr(),
                                     torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
-        raise (ValueError if rc == -1 else RuntimeError)(f"spl_pack_device failed ({rc}): {_ffi.last_error()}")
+        _raise_rc(rc, "spl_pack_device")
     return rows, doc, pos, n
 
 
@@ -179,7 +193,7 @@ def window_device(tok: Tokenizer, batch: DeviceBatch, max_length: int, *, overla
                              row_start.data_ptr() if max_rows else None, row_off.data_ptr(), n.data_ptr(),
                              work.data_ptr() if work.numel() else None, torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
-        raise (ValueError if rc == -1 else RuntimeError)(f"spl_window_device failed ({rc}): {_ffi.last_error()}")
+        _raise_rc(rc, "spl_window_device")
     return rows, mask, lens, row_doc, row_start, row_off, n
 
 
@@ -270,14 +284,13 @@ def pair_csr_device(tok: Tokenizer, a_ids: torch.Tensor, a_off: torch.Tensor, n_
     mask, ttype, special = (new(n_pairs, o.row_len, dt=torch.uint8) for _ in range(3))
     lens, kept = new(n_pairs, dt=torch.int32), new(n_pairs, 2, dt=torch.int32)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
     # (d_rows may never be null; without a pair nothing is written, and an empty tensor has no address: any aligned one stands in)
     rc = _ffi.lib().spl_pair_device(tok.handle, a_ids.data_ptr(), a_off.data_ptr(), n_a, b_ids.data_ptr(), b_off.data_ptr(), n_b,
-                                    ptr(a_index), ptr(b_index), n_pairs, ctypes.byref(o), rows.data_ptr() if n_pairs else status.data_ptr(),
-                                    ptr(mask), ptr(ttype), ptr(special), ptr(lens), ptr(kept), status.data_ptr(),
+                                    _ptr(a_index), _ptr(b_index), n_pairs, ctypes.byref(o), rows.data_ptr() if n_pairs else status.data_ptr(),
+                                    _ptr(mask), _ptr(ttype), _ptr(special), _ptr(lens), _ptr(kept), status.data_ptr(),
                                     torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
-        raise (ValueError if rc == -1 else RuntimeError)(f"spl_pair_device failed ({rc}): {_ffi.last_error()}")
+        _raise_rc(rc, "spl_pair_device")
     return rows, mask, ttype, special, lens, kept, status
 
 
@@ -300,10 +313,6 @@ def pair_device(tok: Tokenizer, batch_a: DeviceBatch, batch_b: DeviceBatch, max_
 
 
 # ---------------------------------------------------------------------------------------------- device-resident decode
-def _decode_error(rc: int) -> Exception:
-    return (ValueError if rc == -1 else RuntimeError)(f"spl_decode_batch_device failed ({rc}): {_ffi.last_error()}")
-
-
 def _max_bytes(max_bytes) -> int:
     if isinstance(max_bytes, bool) or not isinstance(max_bytes, (int, np.integer)) or not 0 <= int(max_bytes) < (1 << 62):
         raise ValueError(f"max_bytes must be an integer in 0 .. 2**62 - 1, not {max_bytes!r}")
@@ -350,7 +359,7 @@ def decode_reserve(tok: Tokenizer, max_ids: int) -> None:
     decode_rows_device calls within that size then neither allocate nor synchronise."""
     rc = _ffi.lib().spl_decode_reserve_device(tok.handle, int(max_ids))
     if rc != 0:
-        raise (ValueError if rc == -1 else RuntimeError)(f"spl_decode_reserve_device failed ({rc}): {_ffi.last_error()}")
+        _raise_rc(rc, "spl_decode_reserve_device")
 
 
 def _decode_call(tok: Tokenizer, ids: torch.Tensor, n_ids_cap: int, offsets, lengths, n_docs: int, o, max_bytes: int):
@@ -363,7 +372,7 @@ def _decode_call(tok: Tokenizer, ids: torch.Tensor, n_ids_cap: int, offsets, len
                                             out.data_ptr() if out.numel() else None, out.numel(), out_off.data_ptr(),
                                             torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
-        raise _decode_error(rc)
+        _raise_rc(rc, "spl_decode_batch_device")
     return out, out_off
 
 
@@ -408,12 +417,11 @@ def _spans_call(tok: Tokenizer, ids: torch.Tensor, n_ids_cap: int, offsets, leng
     char_span = new(slots, 2, dt=dtype) if chars else None
     byte_off = new(n_docs + 1, dt=torch.int64)
     char_off = new(n_docs + 1, dt=torch.int64) if chars else None
-    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
-    rc = _ffi.lib().spl_token_spans_device(tok.handle, ptr(ids), n_ids_cap, ptr(offsets), ptr(lengths), n_docs, ctypes.byref(o),
-                                           _span_dtype(dtype), ptr(byte_span), ptr(char_span), byte_off.data_ptr(), ptr(char_off),
+    rc = _ffi.lib().spl_token_spans_device(tok.handle, _ptr(ids), n_ids_cap, _ptr(offsets), _ptr(lengths), n_docs, ctypes.byref(o),
+                                           _span_dtype(dtype), _ptr(byte_span), _ptr(char_span), byte_off.data_ptr(), _ptr(char_off),
                                            torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
-        raise (ValueError if rc == -1 else RuntimeError)(f"spl_token_spans_device failed ({rc}): {_ffi.last_error()}")
+        _raise_rc(rc, "spl_token_spans_device")
     return byte_span, char_span, byte_off, char_off
 
 
@@ -472,18 +480,13 @@ def check_stream_args(ids, lengths, state, *, errors: str = "hold", final=None, 
         raise ValueError("the sequences must be fewer than 2**31")
     others = []
 
-    def vec(name, t, dtypes, what):
-        if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or t.dim() != 1 or t.shape[0] != B or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous {what} tensor of shape [batch]")
-        others.append((name, t))
-
     if lengths is not None:
-        vec("lengths", lengths, (torch.int32,), "int32")
-    vec("state", state, (torch.int64,), "int64")
+        others.append(_vec("lengths", lengths, B, (torch.int32,), "int32"))
+    others.append(_vec("state", state, B, (torch.int64,), "int64"))
     if state_out is not None:
-        vec("state_out", state_out, (torch.int64,), "int64")
+        others.append(_vec("state_out", state_out, B, (torch.int64,), "int64"))
     if final is not None and not isinstance(final, bool):
-        vec("final", final, (torch.uint8, torch.bool), "uint8 or bool")
+        others.append(_vec("final", final, B, (torch.uint8, torch.bool), "uint8 or bool"))
     if not ids.is_cuda:
         raise ValueError("the ids must be on a GPU (the device-side streaming decode takes no host tensor)")
     for name, t in others:
@@ -496,7 +499,7 @@ def stream_reserve(tok: Tokenizer, max_seqs: int) -> None:
     size then neither allocate nor synchronise."""
     rc = _ffi.lib().spl_stream_reserve_device(tok.handle, int(max_seqs))
     if rc != 0:
-        raise (ValueError if rc == -1 else RuntimeError)(f"spl_stream_reserve_device failed ({rc}): {_ffi.last_error()}")
+        _raise_rc(rc, "spl_stream_reserve_device")
 
 
 def stream_decode_device(tok: Tokenizer, ids: torch.Tensor, lengths: Optional[torch.Tensor], state: torch.Tensor, *, errors: str = "hold",
@@ -520,14 +523,13 @@ def stream_decode_device(tok: Tokenizer, ids: torch.Tensor, lengths: Optional[to
     out_off = torch.empty(B + 1, dtype=torch.int64, device=dev)                # (every offset and every state word is written by the kernels)
     if state_out is None:
         state_out = torch.empty(B, dtype=torch.int64, device=dev)
-    ptr = lambda t: t.data_ptr() if isinstance(t, torch.Tensor) and t.numel() else None
     o = _ffi.SplDecodeOpts(flags, K)
     # (a null state pointer is refused by the library: an empty batch passes the offsets' address, which nothing dereferences)
-    rc = _ffi.lib().spl_stream_decode_device(tok.handle, ptr(ids), ptr(lengths), B, ctypes.byref(o), sflags, ptr(final),
-                                             ptr(state) or out_off.data_ptr(), ptr(state_out) or out_off.data_ptr(), ptr(out), out.numel(),
+    rc = _ffi.lib().spl_stream_decode_device(tok.handle, _ptr(ids), _ptr(lengths), B, ctypes.byref(o), sflags, _ptr(final),
+                                             _ptr(state) or out_off.data_ptr(), _ptr(state_out) or out_off.data_ptr(), _ptr(out), out.numel(),
                                              out_off.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
-        raise (ValueError if rc == -1 else RuntimeError)(f"spl_stream_decode_device failed ({rc}): {_ffi.last_error()}")
+        _raise_rc(rc, "spl_stream_decode_device")
     return out, out_off, state_out
 
 
@@ -579,18 +581,13 @@ def check_stop_args(in_bytes, in_off, state, table, *, mask=None, final=None, ma
             raise ValueError(f"{name} must be a contiguous int64 tensor of shape [batch, {_ffi.SPL_STOP_STATE_WORDS}]")
         others.append((name, t))
 
-    def vec(name, t, dtypes, what):
-        if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or t.dim() != 1 or t.shape[0] != B or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous {what} tensor of shape [batch]")
-        others.append((name, t))
-
     rows("state", state)
     if state_out is not None:
         rows("state_out", state_out)
     if mask is not None:
-        vec("mask", mask, (torch.int64,), "int64")
+        others.append(_vec("mask", mask, B, (torch.int64,), "int64"))
     if final is not None and not isinstance(final, bool):
-        vec("final", final, (torch.uint8, torch.bool), "uint8 or bool")
+        others.append(_vec("final", final, B, (torch.uint8, torch.bool), "uint8 or bool"))
     if not in_bytes.is_cuda:
         raise ValueError("in_bytes must be on a GPU (the device-side stop match takes no host tensor)")
     for name, t in others:
@@ -603,7 +600,7 @@ def stop_reserve(tok: Tokenizer, max_seqs: int) -> None:
     synchronise."""
     rc = _ffi.lib().spl_stop_reserve_device(tok.handle, int(max_seqs))
     if rc != 0:
-        raise (ValueError if rc == -1 else RuntimeError)(f"spl_stop_reserve_device failed ({rc}): {_ffi.last_error()}")
+        _raise_rc(rc, "spl_stop_reserve_device")
 
 
 def stop_match_device(tok: Tokenizer, in_bytes: torch.Tensor, in_off: torch.Tensor, state: torch.Tensor, table: torch.Tensor, *, mask=None,
@@ -625,14 +622,13 @@ def stop_match_device(tok: Tokenizer, in_bytes: torch.Tensor, in_off: torch.Tens
     hit = torch.empty(max(B, 1), dtype=torch.int32, device=dev)[:B]
     if state_out is None:
         state_out = torch.empty((B, _ffi.SPL_STOP_STATE_WORDS), dtype=torch.int64, device=dev)
-    ptr = lambda t: t.data_ptr() if isinstance(t, torch.Tensor) and t.numel() else None
     # (null state and hit pointers are refused by the library: an empty batch passes the offsets' address, which nothing dereferences)
-    rc = _ffi.lib().spl_stop_match_device(tok.handle, ptr(in_bytes), in_bytes.numel(), in_off.data_ptr(), B, table.data_ptr(), ptr(mask),
-                                          ptr(final), flags, ptr(state) or out_off.data_ptr(), ptr(state_out) or out_off.data_ptr(),
-                                          ptr(out), out.numel(), out_off.data_ptr(), ptr(hit) or out_off.data_ptr(),
+    rc = _ffi.lib().spl_stop_match_device(tok.handle, _ptr(in_bytes), in_bytes.numel(), in_off.data_ptr(), B, table.data_ptr(), _ptr(mask),
+                                          _ptr(final), flags, _ptr(state) or out_off.data_ptr(), _ptr(state_out) or out_off.data_ptr(),
+                                          _ptr(out), out.numel(), out_off.data_ptr(), _ptr(hit) or out_off.data_ptr(),
                                           torch.cuda.current_stream(dev).cuda_stream)
     if rc != 0:
-        raise (ValueError if rc == -1 else RuntimeError)(f"spl_stop_match_device failed ({rc}): {_ffi.last_error()}")
+        _raise_rc(rc, "spl_stop_match_device")
     return out, out_off, hit, state_out
 
 

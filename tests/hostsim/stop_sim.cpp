@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../splintr_amd/csrc/spl_k_stop.h"
+#include "seqscan_sim.h"
 
 using namespace spl;
 
@@ -129,43 +130,14 @@ void emit(const SpIn& a, uint64_t b, uint32_t lanes, Wave& L, uint64_t cut, uint
     for (uint32_t i = 2; i < SP_STATE_WORDS; i++) { memcpy(&row_out[i], L.nt() + 8 * (i - 2), 8); w_out[i]++; }
 }
 
+struct Carry { uint64_t cut = 0; uint32_t inf = 0; };
+
+// the driver (seqscan_sim.h) over find and emit
 int run(const SpIn& a, uint32_t lanes, uint32_t chunk, int three, Sink& k) {
-    const uint64_t n = a.n_seqs;
     Wave L(chunk);
-    std::vector<uint64_t> cnt(n + 1, 0), cut(n, 0);
-    std::vector<uint32_t> inf(n, 0);
-    if (!three) {                                   // k_stop_one: find, scan in place, write
-        for (uint64_t b = 0; b < n; b++) cnt[b] = find(a, b, lanes, L, cut[b], inf[b]);
-        uint64_t run = 0;
-        for (uint64_t b = 0; b < n; b++) { const uint64_t v = cnt[b]; cnt[b] = run; run += v; }
-        k.out_off[n] = run; k.off_writes[n]++;
-        for (uint64_t b = 0; b < n; b++) { emit(a, b, lanes, L, cut[b], inf[b], k, cnt[b]); k.out_off[b] = cnt[b]; k.off_writes[b]++; }
-        k.canary_damage += L.damage();
-        return 0;
-    }
-    const uint64_t n_blk = st_n_blocks(n);
-    std::vector<uint64_t> blk(n_blk + 1, 0);
-    for (uint64_t g = 0; g < n_blk; g++)            // k_stop_len
-        for (uint32_t i = 0; i < ST_SEQ_BLK; i++) {
-            const uint64_t b = g * ST_SEQ_BLK + i;
-            if (b >= n) break;
-            cnt[b] = find(a, b, lanes, L, cut[b], inf[b]);
-            blk[g] += cnt[b];
-        }
-    uint64_t run = 0;                               // k_decode_scan
-    for (uint64_t g = 0; g < n_blk; g++) { const uint64_t v = blk[g]; blk[g] = run; run += v; }
-    blk[n_blk] = run;
-    for (uint64_t g = 0; g < n_blk; g++) {          // k_stop_write
-        uint64_t o0 = blk[g];
-        for (uint32_t i = 0; i < ST_SEQ_BLK; i++) {
-            const uint64_t b = g * ST_SEQ_BLK + i;
-            if (b >= n) break;
-            emit(a, b, lanes, L, cut[b], inf[b], k, o0);
-            k.out_off[b] = o0; k.off_writes[b]++;
-            o0 += cnt[b];
-        }
-        if (g == 0) { k.out_off[n] = blk[n_blk]; k.off_writes[n]++; }
-    }
+    seqsim::run<Carry>(a.n_seqs, three, k.out_off, k.off_writes,
+                       [&](uint64_t b, Carry& c) { return find(a, b, lanes, L, c.cut, c.inf); },
+                       [&](uint64_t b, const Carry& c, uint64_t o0) { emit(a, b, lanes, L, c.cut, c.inf, k, o0); });
     k.canary_damage += L.damage();
     return 0;
 }
@@ -175,7 +147,7 @@ int run(const SpIn& a, uint32_t lanes, uint32_t chunk, int three, Sink& k) {
 extern "C" {
 
 void sp_geometry(uint32_t out[8]) {
-    out[0] = SP_WAVE; out[1] = SP_H; out[2] = ST_SEQ_BLK; out[3] = SP_ONE_DEFAULT; out[4] = SP_NT; out[5] = SP_ONE_NT; out[6] = SP_ONE_MAX;
+    out[0] = SP_WAVE; out[1] = SP_H; out[2] = SEQ_BLK; out[3] = SP_ONE_DEFAULT; out[4] = SP_NT; out[5] = SP_ONE_NT; out[6] = SP_ONE_MAX;
     out[7] = SP_TABLE_BYTES;
 }
 

@@ -18,7 +18,7 @@ MUTANTS = {"": [], "halo62": ["-DSPL_STOP_HALO=62"], "shortest": ["-DSPL_STOP_MU
 def build(mutant=""):
     src = os.path.join(_HERE, "stop_sim.cpp")
     out = os.path.join(_HERE, "libstop_sim%s.so" % ("_" + mutant if mutant else ""))
-    deps = [src] + [os.path.join(_CSRC, f) for f in ("spl_k_stop.h", "spl_k_stream.h", "spl_k_decode_dev.h", "spl_common.h")]
+    deps = [src, os.path.join(_HERE, "seqscan_sim.h")] + [os.path.join(_CSRC, f) for f in ("spl_k_stop.h", "spl_k_seqscan.h", "spl_common.h")]
     if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas"] + MUTANTS[mutant] + ["-o", out, src])
     return out

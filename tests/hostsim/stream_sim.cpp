@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../splintr_amd/csrc/spl_k_stream.h"
+#include "seqscan_sim.h"
 
 using namespace spl;
 
@@ -96,41 +97,14 @@ uint64_t seq(const StIn& a, const DecTab& t, uint64_t b, uint32_t lanes, uint32_
     return o - o0;
 }
 
+struct NoCarry {};
+
+// the driver (seqscan_sim.h) over seq
 template <bool I64>
 int run(const StIn& a, const DecTab& t, uint32_t lanes, uint32_t chunk, int three, Sink& k) {
-    const uint64_t n = a.n_seqs;
-    std::vector<uint64_t> cnt(n + 1, 0);
-    if (!three) {                                   // k_stream_one: count, scan in place, write
-        for (uint64_t b = 0; b < n; b++) cnt[b] = seq<I64>(a, t, b, lanes, chunk, false, k, 0);
-        uint64_t run = 0;
-        for (uint64_t b = 0; b < n; b++) { const uint64_t v = cnt[b]; cnt[b] = run; run += v; }
-        k.out_off[n] = run; k.off_writes[n]++;
-        for (uint64_t b = 0; b < n; b++) { seq<I64>(a, t, b, lanes, chunk, true, k, cnt[b]); k.out_off[b] = cnt[b]; k.off_writes[b]++; }
-        return 0;
-    }
-    const uint64_t n_blk = st_n_blocks(n);
-    std::vector<uint64_t> blk(n_blk + 1, 0);
-    for (uint64_t g = 0; g < n_blk; g++)            // k_stream_len
-        for (uint32_t i = 0; i < ST_SEQ_BLK; i++) {
-            const uint64_t b = g * ST_SEQ_BLK + i;
-            if (b >= n) break;
-            cnt[b] = seq<I64>(a, t, b, lanes, chunk, false, k, 0);
-            blk[g] += cnt[b];
-        }
-    uint64_t run = 0;                               // k_decode_scan
-    for (uint64_t g = 0; g < n_blk; g++) { const uint64_t v = blk[g]; blk[g] = run; run += v; }
-    blk[n_blk] = run;
-    for (uint64_t g = 0; g < n_blk; g++) {          // k_stream_write
-        uint64_t o0 = blk[g];
-        for (uint32_t i = 0; i < ST_SEQ_BLK; i++) {
-            const uint64_t b = g * ST_SEQ_BLK + i;
-            if (b >= n) break;
-            seq<I64>(a, t, b, lanes, chunk, true, k, o0);
-            k.out_off[b] = o0; k.off_writes[b]++;
-            o0 += cnt[b];
-        }
-        if (g == 0) { k.out_off[n] = blk[n_blk]; k.off_writes[n]++; }
-    }
+    seqsim::run<NoCarry>(a.n_seqs, three, k.out_off, k.off_writes,
+                         [&](uint64_t b, NoCarry&) { return seq<I64>(a, t, b, lanes, chunk, false, k, 0); },
+                         [&](uint64_t b, const NoCarry&, uint64_t o0) { seq<I64>(a, t, b, lanes, chunk, true, k, o0); });
     return 0;
 }
 
@@ -138,7 +112,7 @@ int run(const StIn& a, const DecTab& t, uint32_t lanes, uint32_t chunk, int thre
 
 extern "C" {
 
-void ss_geometry(uint32_t out[7]) { out[0] = ST_WAVE; out[1] = ST_H; out[2] = ST_SEQ_BLK; out[3] = ST_ONE_DEFAULT; out[4] = ST_NT; out[5] = ST_ONE_NT; out[6] = ST_ONE_MAX; }
+void ss_geometry(uint32_t out[7]) { out[0] = ST_WAVE; out[1] = ST_H; out[2] = SEQ_BLK; out[3] = ST_ONE_DEFAULT; out[4] = ST_NT; out[5] = ST_ONE_NT; out[6] = ST_ONE_MAX; }
 
 int ss_step(const void* ids, const int32_t* len, const uint8_t* fin, const uint64_t* state_in, uint64_t n_seqs, uint32_t row_len, uint32_t dflags,
             uint32_t sflags, const uint32_t* tok_off, const uint8_t* tok_bytes, uint32_t max_id, const uint32_t* sp_ids, const uint32_t* sp_off,

@@ -204,6 +204,29 @@ def test_one_size_through_both_forms():
     assert res[0] == res[1]
 
 
+def test_block_edges_and_the_top_of_the_one_launch_form():
+    """three launches ("stop_one_max" 0) at the driver's block of 16 sequences, one either side of it and at two blocks plus one; one launch
+    (1024) across the carry of its chunked LDS scan and at its last count slot: each against the oracle, and every size through the other
+    form too with identical results"""
+    import stop_sim
+    g = stop_sim.geometry()
+    assert g["seq_block"] == 16 and g["one_cap"] == 1024
+    one = _option(b"stop_one_max")
+    tab = ref.table([b"abca", b"bcab", b"cc"])
+    texts = _texts6()[-1024:]
+    sizes = {0: (1, 15, 16, 17, 32, 33), 1024: (65, 1023, 1024)}
+    res = {}
+    try:
+        for limit in sizes:
+            assert _option(b"stop_one_max", limit) == limit
+            for n in sizes[0] + sizes[1024]:
+                res[limit, n] = _drive(tab, [[(t[:2], False), (t[2:], i % 3 == 0)] for i, t in enumerate(texts[:n])])
+    finally:
+        _option(b"stop_one_max", one)
+    for n in sizes[0] + sizes[1024]:
+        assert res[0, n] == res[1024, n], n
+
+
 def test_200_bytes_a_step_with_a_64_byte_stop_across_the_edges():
     """200 new bytes a sequence in one step; the 64-byte stop straddles the chunk edges (64, 128, 192) and the step edge"""
     tab = ref.table([LONG, b"zz"])

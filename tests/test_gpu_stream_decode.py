@@ -114,6 +114,24 @@ def test_both_shapes_at_one_size():
     assert L.spl_set_option(tok.handle, b"stream_one_max", cap + 1) == -1 and L.spl_set_option(tok.handle, b"stream_one_max", -1) == -1
 
 
+@MODES
+def test_block_edges_and_the_top_of_the_one_launch_form(replace):
+    """three launches ("stream_one_max" 0) at the driver's block of 16 sequences, one either side of it and at two blocks plus one; one launch
+    (1024) across the carry of its chunked LDS scan and at its last count slot"""
+    import stream_sim
+    from splintr_amd import _ffi
+    g = stream_sim.geometry()
+    assert g["seq_block"] == 16 and g["one_cap"] == 1024
+    tok, L = _byte_tok(), _ffi.lib()
+    try:
+        for limit, sizes in ((0, (1, 15, 16, 17, 32, 33)), (1024, (65, 1023, 1024))):
+            assert L.spl_set_option(tok.handle, b"stream_one_max", limit) == 0
+            for n in sizes:
+                _run_steps(tok, n, replace)
+    finally:
+        assert L.spl_set_option(tok.handle, b"stream_one_max", _one_max()) == 0
+
+
 def _random_rows(rng, B, K):
     pool = list(range(256)) * 3 + list(ref.CH2 + ref.CH3 + ref.CH4) * 40 + [ref.KEY4, ref.KEY2, ref.LIT3, ref.SPECIAL, ref.FAR] * 8 + \
         list(ref.UNKNOWN) * 6
