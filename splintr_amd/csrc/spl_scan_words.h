@@ -5,8 +5,11 @@
 // with a dozen ballots per 64-byte row: a fifth of the kernel's vector instructions for the two steps
 // (profiles/r04_phase_instruction_mix.txt).  Here a lane turns its four bytes into the records AND into two words of
 // NIBBLES, one nibble per kind: bit k of nibble j = "byte k of this lane's word is of kind j".  For ASCII -- nearly every
-// word of English / code -- that is four reads of a 128-entry LDS table and a few shifts; only a word with a byte beyond
-// ASCII (or at a text edge) takes the general path below.  Eight neighbouring lanes then transpose their 8 x 8 nibbles
+// word of English / code -- that is four reads of a 128-entry LDS table and a few shifts.  A word with a byte beyond
+// ASCII, away from every text edge, goes through classify_word_text: first the two-byte form (classify_word_two: accented
+// Latin, Greek, Cyrillic, Hebrew, Arabic), then the three-character form for well-formed text of any length (a dash, CJK);
+// what both decline -- malformed text, a text edge within three bytes, a special-literal span -- takes the general path
+// classify_word.  Eight neighbouring lanes then transpose their 8 x 8 nibbles
 // with three DPP exchanges (k_pretok), after which lane 8w + j holds mask word w of kind j, position-ordered as before.
 // The split semantics are untouched (same records, same masks: tests/hostsim checks this header against the
 // record-based mask builder on adversarial and malformed text); what it restates is still RegexBackend::find_iter over
@@ -204,8 +207,100 @@ SPL_HD uint32_t flags4(uint32_t x) { return (((x >> 7) & 0x01010101u) * 0x002040
 // a 4-bit mask spread to the bytes of a word: bit k -> 0x01 in byte k
 SPL_HD uint32_t spread4(uint32_t m4) { return (m4 * 0x00204081u) & 0x01010101u; }
 
+#ifndef SPL_WORD_TWO
+#define SPL_WORD_TWO 1           /* 0: every word beyond ASCII through the three-character form below (A/B) */
+#endif
+#ifndef SPL_WORD_TWO_ONE
+#define SPL_WORD_TWO_ONE 1       /* 0: no sub-case of its own for "exactly one character touches the word" (A/B; profiles/two_byte_words.txt) */
+#endif
+
+// The word of Latin-1, Latin Extended, Greek, Cyrillic, Hebrew or Arabic text: every byte beyond ASCII belongs to a whole
+// TWO-BYTE character -- a lead 110xxxxx with its continuation byte 10xxxxxx right behind it (in tw, or byte 0 of wn for a
+// lead in byte 3), or that continuation byte (its lead in tw, or byte 3 of wp for byte 0).  One to three characters per
+// word; the test is word arithmetic on the two bit patterns, the code point (lead & 0x1F) << 6 | (cont & 0x3F), no length
+// to find, no coverage to check, no CJK range.  A word that exactly ONE such character touches -- all that accented
+// English, Spanish or German has -- leaves through a sub-case with one lookup; Greek or Cyrillic runs take the full form.
+// A longer lead, a stray continuation byte, a lead without its continuation: false, and the word goes the way of
+// classify_word_text.  (The overlong leads 0xC0 / 0xC1 are taken: the general path decodes them by the same formula and
+// looks the result up in the same table.)  profiles/two_byte_words.txt: the classify phase of the bench batch 2.6 -> 1.5 us.
+//   precondition (classify_word_text's guard): window indices i0 - 3 .. i0 + 6 are one text, all staged
+//   SPL_WORDS_SIM_BREAK: deliberately wrong variants for tests/hostsim/words_sim.cpp only -- never defined in the product
+template <class AENT, class KENT>
+SPL_HD bool classify_word_two(const DeviceTables& T, int pattern, uint32_t wp, uint32_t tw, uint32_t wn, const AENT& aent, const KENT& kent,
+                              WordKinds& o) {
+#if SPL_WORDS_SIM_BREAK == 1
+    constexpr uint32_t CS_LEAD = V1_CS * 3u;
+#else
+    constexpr uint32_t CS_LEAD = V1_CS;                         // CS on the lead byte alone
+#endif
+    const uint32_t t1 = tw << 1, hi = tw & 0x80808080u;
+    const uint32_t ld = hi & t1, C = hi & ~t1;                  // bit 7 of a byte: 11xxxxxx / 10xxxxxx
+    const uint32_t wp1 = wp << 1;
+    const uint32_t lp = ((wp & wp1 & ~(wp1 << 1)) >> 24) & 0x80u;   // byte 3 of wp is 110xxxxx: in front of byte 0
+    const uint32_t cn = (wn & ~(wn << 1) & 0x80u) << 24;        // byte 0 of wn is 10xxxxxx: behind byte 3
+#if SPL_WORDS_SIM_BREAK == 2
+    const uint32_t Lp = (ld << 8) | 0x80u | (lp & 0u);
+#else
+    const uint32_t Lp = (ld << 8) | lp;
+#endif
+    const uint32_t Cn = (C >> 8) | cn;
+    if ((ld & (t1 << 1)) | (ld & ~Cn) | (C & ~Lp)) return false;    // a lead 111xxxxx; a lead without a continuation behind it; a continuation without a lead in front
+    // the characters: A, whose continuation byte is byte 0, and the (at most two) that start in the word, B and C
+    const bool hasA = (C & 0x80u) != 0u, hasB = ld != 0u;
+    const uint32_t rest = ld & (ld - 1u);
+    const bool hasC = rest != 0u;
+    const uint32_t k1 = hasB ? (uint32_t)ctz32(ld) >> 3 : 0u, k2 = hasC ? (uint32_t)ctz32(rest) >> 3 : 0u;
+    const uint32_t wA = bytes_at(wp, tw, 3u), wB = bytes_at(tw, wn, k1);     // lead in byte 0, continuation in byte 1
+    const uint32_t sh = T.ucls_shift, lowm = (1u << sh) - 1u;
+    // the ASCII bytes from the table (the other bytes' entries masked out)
+    const KindEnt e0 = aent(tw & 0x7Fu), e1 = aent((tw >> 8) & 0x7Fu), e2 = aent((tw >> 16) & 0x7Fu), e3 = aent((tw >> 24) & 0x7Fu);
+    const uint32_t h1 = hi >> 7;                                // 0x01 in every byte beyond ASCII
+    const uint32_t ascn = (~flags4(hi) & 0xFu) * 0x11111111u, ascb = ~(h1 * 0xFFu);
+    o.v0 = (e0.x | (e1.x << 1) | (e2.x << 2) | (e3.x << 3)) & ascn;
+    o.v1 = (e0.y | (e1.y << 1) | (e2.y << 2) | (e3.y << 3)) & ascn & 0x00FFFFFFu;
+    // records: the table's for ASCII, C_CONT on every continuation byte, class and length on the leads
+    o.rec = (((e0.y >> 28) | ((e1.y >> 28) << 8) | ((e2.y >> 28) << 16) | ((e3.y >> 28) << 24)) & ascb) | ((C >> 7) * (uint32_t)C_CONT);
+#if SPL_WORD_TWO_ONE
+    if (!hasC && hasA != hasB) {                                // exactly one character touches the word: one lookup, one kind entry
+        const uint32_t w = hasA ? wA : wB, cp1 = ((w & 0x1Fu) << 6) | ((w >> 8) & 0x3Fu);
+        const uint32_t c = T.ucls_stage2[((uint32_t)T.ucls_stage1[cp1 >> sh] << sh) | (cp1 & lowm)];
+        const KindEnt e = kent(c);
+        const bool bad = !(SPL_BIT(c) & (M_L | M_OTHER)) || (pattern != PAT_CL100K && c == C_M);
+        const uint32_t m = hasA ? 1u : (3u << k1) & 0xFu;
+        o.v0 |= e.x * m;
+        o.v1 |= (e.y | (bad ? V1_BAD : 0u)) * m | (hasA ? 0u : CS_LEAD << k1);
+        o.rec |= hasA ? 0u : ((1u << CB_LEN_SHIFT) | c) << (8u * k1);
+        return true;
+    }
+#endif
+    const uint32_t wC = bytes_at(tw, wn, k2);
+    const uint32_t cp[3] = {((wA & 0x1Fu) << 6) | ((wA >> 8) & 0x3Fu), ((wB & 0x1Fu) << 6) | ((wB >> 8) & 0x3Fu), ((wC & 0x1Fu) << 6) | ((wC >> 8) & 0x3Fu)};
+    const bool has[3] = {hasA, hasB, hasC};
+    // their classes: the lookups of the word in flight together
+    uint32_t blk[3], cls[3];
+#pragma unroll
+    for (int j = 0; j < 3; j++) blk[j] = T.ucls_stage1[has[j] ? cp[j] >> sh : 0u];
+#pragma unroll
+    for (int j = 0; j < 3; j++) cls[j] = T.ucls_stage2[(blk[j] << sh) | (has[j] ? cp[j] & lowm : 0u)];
+    // the characters: both bytes the kinds of their character; BAD for a number / whitespace / (o200k family) mark; CS on the lead
+    const uint32_t mm[3] = {hasA ? 1u : 0u, hasB ? (3u << k1) & 0xFu : 0u, hasC ? (3u << k2) & 0xFu : 0u}, kk[3] = {0u, k1, k2};
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        const uint32_t c = cls[j];
+        const KindEnt e = kent(c);
+        const bool bad = !(SPL_BIT(c) & (M_L | M_OTHER)) || (pattern != PAT_CL100K && c == C_M);
+        o.v0 |= e.x * mm[j];
+        o.v1 |= (e.y | (bad ? V1_BAD : 0u)) * mm[j];
+        if (j > 0 && has[j]) {
+            o.v1 |= CS_LEAD << kk[j];
+            o.rec |= ((1u << CB_LEN_SHIFT) | c) << (8u * kk[j]);
+        }
+    }
+    return true;
+}
+
 // The COMMON word beyond ASCII: well-formed UTF-8, away from every edge -- an accented letter, a dash, a run of CJK.  The
-// general path above decides each of its five byte slots on its own (every one a lead byte? a continuation byte of what?),
+// general path (classify_word) decides each of its five byte slots on its own (every one a lead byte? a continuation byte of what?),
 // nine hundred instructions that every wavefront with ONE such word walks through; here the word is taken as what it
 // nearly always is: ASCII bytes from the table, plus at most three whole characters -- the one the word begins inside
 // (A) and up to two that start in it (B, C).  Anything else -- a text start or an edge within three bytes, a stray
@@ -217,6 +312,9 @@ template <class AENT, class KENT>
 SPL_HD bool classify_word_text(const DeviceTables& T, int pattern, uint32_t wp, uint32_t tw, uint32_t wn, uint32_t ts16, const AENT& aent,
                                const KENT& kent, int i0, int lo, int iT, WordKinds& o) {
     if (((ts16 >> 1) & 0x3FFu) != 0u || i0 - 3 < lo || i0 + 7 > iT) return false;    // window indices i0 - 3 .. i0 + 6: one text, all staged
+#if SPL_WORD_TWO
+    if (classify_word_two(T, pattern, wp, tw, wn, aent, kent, o)) return true;          // two-byte characters only: the short form
+#endif
     const uint32_t hi_t = tw & 0x80808080u, lead_t = tw & (tw << 1) & 0x80808080u;
     const uint32_t non4 = flags4(hi_t), lead4 = flags4(lead_t);
     const uint32_t lead_p = flags4(wp & (wp << 1) & 0x80808080u), cont_p = flags4(wp & ~(wp << 1) & 0x80808080u);

@@ -11,7 +11,11 @@ L = _ffi.lib(); L.spl_memo_stats.argtypes = [ctypes.c_void_p, ctypes.POINTER(cty
 memo = int(sys.argv[1])
 WARM, N = 30, 20
 tok = Tokenizer.from_pretrained("cl100k_base")
-batch = DeviceBatch(corpus.c2(1000), torch.device("cuda", 0))
+texts = corpus.c2(1000)
+if os.environ.get("SPL_ASCII_CONTROL") == "1":        # (the accented letters as their base letters: tools/dev/two_byte_ceiling.py)
+    from two_byte_ceiling import ascii_control
+    texts = ascii_control(texts)
+batch = DeviceBatch(texts, torch.device("cuda", 0))
 reserve(tok, batch.n_bytes, batch.n_docs)
 assert L.spl_set_option(tok.handle, b"memo", memo) == 0
 st = (ctypes.c_uint64 * 16)()

@@ -18,6 +18,9 @@ if gen == "purecjk":
     texts = [corpus.cjk(_r, 4000) for _ in range(ndocs)]
 else:
     texts = getattr(corpus, gen)(ndocs)
+if os.environ.get("SPL_ASCII_CONTROL") == "1":        # (the accented letters as their base letters: tools/dev/two_byte_ceiling.py)
+    from two_byte_ceiling import ascii_control
+    texts = ascii_control(texts)
 batch = DeviceBatch(texts, torch.device("cuda", 0))
 reserve(tok, batch.n_bytes, batch.n_docs)
 for k_, v_ in (("memo", "SPL_WALLS_MEMO"), ("fuse", "SPL_WALLS_FUSE")):
