@@ -122,7 +122,8 @@ def idle_cpus(sample_s: float = 0.25, busy_max: float = 0.05) -> List[int]:
 
 
 class COracle:
-    def __init__(self, name: str, memo: bool = False):
+    def __init__(self, name: str, memo: bool = False, unicode_table: str = None):
+        """`unicode_table`: the path of a class table in place of the shipped splintr_amd/data/unicode_classes.bin"""
         base = {"llama3.1": "llama3", "llama3.2": "llama3", "llama3.3": "llama3",
                 "deepseek-v3": "deepseek_v3"}.get(name, name)
         if base not in _REG:
@@ -131,7 +132,7 @@ class COracle:
         fn, pid, bl, skey = _REG[base]
         self.name = base
         self._h = lib().orc_create(os.path.join(_DATA, fn).encode(),
-                                   os.path.join(_DATA, "unicode_classes.bin").encode(), pid, bl)
+                                   os.fspath(unicode_table or os.path.join(_DATA, "unicode_classes.bin")).encode(), pid, bl)
         if not self._h:
             raise IOError("orc_create failed")
         with open(os.path.join(_DATA, "special_tokens.json"), encoding="utf-8") as f:
