@@ -395,6 +395,108 @@ int spl_pair_device(spl_tokenizer* t,
                     int32_t* d_len /* [n_pairs] */, int32_t* d_kept /* [n_pairs*2] */,
                     uint32_t* d_status /* one word, cleared by the caller */, void* hip_stream);
 
+/* CHAT: a CSR of MESSAGES joined into one row per multi-turn CONVERSATION, with a label mask -- what an instruction-tuned model reads and
+ * what Hugging Face calls apply_chat_template with tokenize=True and return_assistant_tokens_mask=True.  Every message is wrapped in its role's control tokens
+ * (ChatML's <|im_start|>role\n ... <|im_end|>\n, llama3's <|start_header_id|>role<|end_header_id|>\n\n ... <|eot_id|>), the turns are joined, and
+ * only the turns of the trained roles carry labels.  spl_pair_device is the special case of two segments; this call has N turns, wrappers
+ * per role, labels, and can drop the oldest turns.  The reference has no counterpart, as for pad, pack and pairs; the same conventions hold:
+ * fully asynchronous on `hip_stream`, nothing allocated, nothing synchronised, the handle used only for its device, ANY CSR in device
+ * memory, ids as bit patterns (SPL_COLLATE_I64 zero-extends).  The messages are encoded SEPARATELY and the control tokens come from the
+ * options, never from message text: a message that contains the literal of a control token cannot forge a turn, and a message that many
+ * conversations name -- a shared system prompt -- is encoded once and read by each.  Two launches: one wavefront per conversation scans
+ * its turns, then a gather writes every output element once.
+ *
+ * Messages  document i is ids[off[i] .. off[i + 1]), i < n_docs; the offsets are ABSOLUTE into d_ids and off[0] need not be 0.
+ * Turns     turn t (t < n_turns) has the role d_turn_role[t] (a byte, 0 .. n_roles - 1) and the content document
+ *           d_turn_doc ? d_turn_doc[t] : t; it is TRAINABLE if d_turn_train ? d_turn_train[t] != 0 : true.  Conversation c (c < n_convs) owns
+ *           the turns [d_conv_off[c], d_conv_off[c + 1]) -- a CSR over the turns.
+ * Template  HOST values in the options: for every role r its header[r][0 .. n_header[r]) and footer[r][0 .. n_footer[r]); bos[0 .. n_bos)
+ *           in front of every row; gen[0 .. n_gen), the generation prompt (an assistant header, for sampling), behind every row's body;
+ *           n_gen == 0: none.  train_content and train_footer are bit masks over the roles (bit r: role r).
+ * Body      the body of conversation c is the concatenation over its turns, in order, of header[r] + content + footer[r], r the turn's
+ *           role, content the turn's document.  Its budget is B = row_len - n_bos - n_gen.  Row c is bos + body' + gen, then pad_id --
+ *           padding on the right, or on the left with SPL_COLLATE_PAD_LEFT.  bos and gen are never cut away.
+ * Cut       default: body' = the first min(len(body), B) entries of the body; the cut may fall inside a header, a content or a footer.
+ *           SPL_CHAT_DROP_OLDEST: whole leading turns are removed instead.  t0 = the smallest turn index (within the conversation) for
+ *           which the kept body -- the turns from t0 on -- has at most B entries.  With SPL_CHAT_PIN_FIRST (valid only together with
+ *           DROP_OLDEST; it keeps a system prompt) the kept body is turn 0 followed by the turns from t0 on, t0 >= 1 the smallest such
+ *           index for which turn 0 plus these turns have at most B entries; a conversation of fewer than two turns has nothing to drop.
+ *           If no t0 fits, only the conversation's LAST turn is kept (after turn 0 when pinned), and that body is cut on the right at
+ *           B like the default.  With no turn dropped the result equals the default.
+ * Bad input is never read out of range and sets d_status[0] = 1 (a plain store of 1; the caller clears the word before the call and a
+ *           call without bad input leaves it alone): a role >= n_roles -- the turn contributes NOTHING (no header, content or footer);
+ *           a document index that is negative or >= n_docs -- the turn's content is empty (header and footer remain); a conversation
+ *           whose turn range is reversed (d_conv_off[c + 1] < d_conv_off[c]) or reaches beyond n_turns -- it has no turns.  Only turns
+ *           that a valid conversation contains are looked at: a bad turn outside every conversation is not reported.  Turn ranges that
+ *           OVERLAP (one of them is then reversed, and reported) leave the rows and d_turn_col of the conversations involved
+ *           unspecified; nothing is read or written out of range.
+ * Outputs   every output is optional (NULL: not wanted, not written) except d_rows, d_status and d_work; every element of every array
+ *           that is given is written -- d_turn_col with the exception below -- and nothing at or beyond n_convs rows.  An entry of a row
+ *           is TRAINED if it is content of a turn that is trainable and whose role is in train_content, or footer of such a turn
+ *           whose role is also in train_footer (the end-of-turn token the model must learn to emit).  Headers, bos, gen and padding are never trained.
+ *             d_rows[c, col]      the row.
+ *             d_labels[c, col]    same dtype as the rows: a trained entry holds its id (zero-extended in int64), every other entry
+ *                                 ignore_id -- in int64 SIGN-extended from 32 bits, because -100 (0xFFFFFF9C) is a number.  Labels
+ *                                 are not shifted; the model shifts.
+ *             d_loss[c, col]      bytes: 1 on trained entries, 0 elsewhere.
+ *             d_mask[c, col]      bytes: 1 where the entry is not padding.
+ *             d_role[c, col]      bytes: the turn's role over its header, content and footer; SPL_CHAT_NO_ROLE on bos, gen and padding.
+ *             d_special[c, col]   bytes: 1 on template entries (bos, headers, footers, gen) and on padding, 0 on ids from a document.
+ *             d_len[c]            n_bos + len(body') + n_gen, the entries that are not padding.
+ *             d_kept[2c]          the turns dropped (0 without DROP_OLDEST); d_kept[2c + 1] the entries of the kept body cut off on the
+ *                                 right (saturated at 2^31 - 1).  Either being nonzero means truncation.
+ *             d_turn_col[2t], d_turn_col[2t + 1]   the columns [c0, c1) of turn t's CONTENT in its conversation's row, clipped to the
+ *                                 row; t is the turn's index in the d_turn_role array, not within its conversation.
+ *                                 (-1, -1) for a dropped turn, for a turn wholly behind the cut -- one whose content begins
+ *                                 at or behind the cut --, and for a bad turn (role or document index).  A content that is empty and
+ *                                 begins before the cut gives c0 == c1.  d_rows[c, c0 .. c1) are the ids of the document that are in
+ *                                 the row: mask a tool output, read back one message.  A turn that NO valid conversation contains is
+ *                                 not written: fill the array before the call if such turns exist.
+ *           d_len and d_turn_col are int32 like d_len of the pairs: for rows of 2^31 entries or more they hold the low 32 bits.
+ *           n_convs == 0: nothing to do.
+ * Work      d_work: spl_chat_work_bytes(n_turns, n_convs) bytes of device memory, 16-byte aligned, for this call alone until it has run
+ *           (the template copy, one record per conversation, one start per turn).  The size is a pure function of its two arguments,
+ *           monotone in both and a multiple of 16.
+ *
+ * SPL_EINVAL, with the cause in spl_last_error() and before anything touches the handle or the device: a null handle, null options, a null
+ * d_rows, d_off, d_conv_off, d_status or d_work (always), null d_turn_role with n_turns > 0, null d_ids with n_docs > 0; a struct_size
+ * shorter than the struct or above 4096 (a longer struct up to that is accepted, its tail ignored); an unknown flag bit;
+ * SPL_COLLATE_KEEP_TAIL, _BOS or _EOS; SPL_CHAT_PIN_FIRST without SPL_CHAT_DROP_OLDEST; n_roles outside 1 .. 8; n_bos > 8, n_gen > 16,
+ * n_header[r] > 16 or n_footer[r] > 8 for a role r < n_roles; a bit of train_content or train_footer at or above n_roles; row_len == 0 or
+ * row_len < n_bos + n_gen; n_docs, n_turns or n_convs >= 2^31; a NULL d_turn_doc with n_turns > n_docs; n_convs * row_len beyond 2^63;
+ * d_rows, d_labels, d_len, d_kept, d_turn_col or d_work not 16-byte aligned; d_loss, d_mask, d_role, d_special or d_turn_doc not 4-byte
+ * aligned; d_conv_off not 8-byte aligned. */
+#define SPL_CHAT_DROP_OLDEST 32u    /* truncation removes whole leading turns (default: the body is cut on the right) */
+#define SPL_CHAT_PIN_FIRST   64u    /* with DROP_OLDEST: turn 0 of every conversation is kept */
+/* also accepted: SPL_COLLATE_I64, SPL_COLLATE_PAD_LEFT (same values, same meaning) */
+#define SPL_CHAT_NO_ROLE     255u   /* d_role on bos, gen and padding */
+#define SPL_CHAT_MAX_ROLES   8u
+#define SPL_CHAT_MAX_HEADER  16u    /* ids per role header */
+#define SPL_CHAT_MAX_FOOTER  8u     /* ids per role footer */
+#define SPL_CHAT_MAX_BOS     8u
+#define SPL_CHAT_MAX_GEN     16u
+
+typedef struct spl_chat_opts {
+    uint32_t struct_size;                 /* sizeof the struct as the CALLER was compiled: versioned exactly like spl_collate_opts */
+    uint32_t flags, row_len, pad_id, ignore_id;
+    uint32_t n_roles, train_content, train_footer;  /* 1 .. 8; bit masks over the roles */
+    uint32_t n_bos, n_gen;                          /* 0 .. 8, 0 .. 16 */
+    uint32_t n_header[8], n_footer[8];              /* each 0 .. 16, each 0 .. 8 */
+    uint32_t bos[8], gen[16];                       /* HOST values, passed to the kernel by value */
+    uint32_t header[8][16], footer[8][8];
+} spl_chat_opts;
+
+uint64_t spl_chat_work_bytes(uint64_t n_turns, uint64_t n_convs);
+int spl_chat_device(spl_tokenizer* t,
+                    const uint32_t* d_ids, const uint64_t* d_off, uint64_t n_docs,
+                    const int32_t* d_turn_doc /* [n_turns], NULL: identity */, const uint8_t* d_turn_role /* [n_turns] */,
+                    const uint8_t* d_turn_train /* [n_turns], NULL: all 1 */, uint64_t n_turns,
+                    const uint64_t* d_conv_off /* [n_convs + 1] */, uint64_t n_convs, const spl_chat_opts* o,
+                    void* d_rows /* [n_convs*row_len] */, void* d_labels /* same */, uint8_t* d_loss, uint8_t* d_mask, uint8_t* d_role,
+                    uint8_t* d_special, int32_t* d_len /* [n_convs] */, int32_t* d_kept /* [n_convs*2] */,
+                    int32_t* d_turn_col /* [n_turns*2] */, uint32_t* d_status /* one word, cleared by the caller */,
+                    void* d_work /* spl_chat_work_bytes */, void* hip_stream);
+
 /* SLIDING WINDOWS over the CSR: every document alone and complete, as rows of row_len that overlap by `overlap` ids -- the one
  * per-document layout that loses nothing (pad mode truncates, pack mode joins documents), and what Hugging Face tokenizers call
  * return_overflowing_tokens with stride = overlap.  The reference has no counterpart, as for pad and pack; the same conventions hold:

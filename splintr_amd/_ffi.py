@@ -29,7 +29,7 @@ SYMBOLS = [
     "spl_comm_unique_id", "spl_comm_create", "spl_comm_destroy", "spl_comm_rank", "spl_comm_world",
     "spl_allgather_slabs", "spl_allgather_slabs_p2p", "spl_gatherv_unpack_at", "spl_allgatherv_csr", "spl_split_host", "spl_encode_chunks_device",
     "spl_split_device", "spl_device_split_fallbacks", "spl_small_path_calls", "spl_pick_stream", "spl_memo_stats", "spl_memo_seed_stats", "spl_debug_memo_entry",
-    "spl_pad_device", "spl_pack_device", "spl_pair_device", "spl_window_work_bytes", "spl_window_device",
+    "spl_pad_device", "spl_pack_device", "spl_pair_device", "spl_chat_work_bytes", "spl_chat_device", "spl_window_work_bytes", "spl_window_device",
     "spl_decode_reserve_device", "spl_decode_batch_device", "spl_max_token_bytes", "spl_token_spans_device",
     "spl_stream_reserve_device", "spl_stream_decode_device",
     "spl_get_option", "spl_stop_reserve_device", "spl_stop_match_device",
@@ -39,6 +39,8 @@ SPL_OPT_BYTE_LEVEL = 1
 SPL_COLLATE_I64, SPL_COLLATE_PAD_LEFT, SPL_COLLATE_KEEP_TAIL, SPL_COLLATE_BOS, SPL_COLLATE_EOS = 1, 2, 4, 8, 16
 SPL_PAIR_MAX_FIXED, SPL_PAIR_KEEP_TAIL_A, SPL_PAIR_KEEP_TAIL_B = 32, 32, 64
 SPL_PAIR_LONGEST_FIRST, SPL_PAIR_ONLY_FIRST, SPL_PAIR_ONLY_SECOND = 0, 1, 2
+SPL_CHAT_DROP_OLDEST, SPL_CHAT_PIN_FIRST, SPL_CHAT_NO_ROLE = 32, 64, 255
+SPL_CHAT_MAX_ROLES, SPL_CHAT_MAX_HEADER, SPL_CHAT_MAX_FOOTER, SPL_CHAT_MAX_BOS, SPL_CHAT_MAX_GEN = 8, 16, 8, 8, 16
 SPL_DECODE_I64, SPL_DECODE_PAD_LEFT, SPL_DECODE_SKIP_SPECIAL = 1, 2, 4
 SPL_SPANS_I64 = 1
 SPL_STREAM_REPLACE, SPL_STREAM_FINAL_ALL = 1, 2
@@ -73,6 +75,31 @@ class SplPairOpts(ctypes.Structure):
         seg = ctypes.c_uint32 * 32
         super().__init__(ctypes.sizeof(SplPairOpts), flags, row_len, pad_id, trunc, len(prefix), len(middle), len(suffix),
                          seg(*prefix[:32]), seg(*middle[:32]), seg(*suffix[:32]))
+
+
+class SplChatOpts(ctypes.Structure):
+    """spl_chat_opts (include/splintr_hip.h): what spl_chat_device is told about a row and the template -- HOST values.  roles: one
+    (header ids, footer ids) per role number; train_content / train_footer: bit masks over the role numbers."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("row_len", ctypes.c_uint32), ("pad_id", ctypes.c_uint32),
+                ("ignore_id", ctypes.c_uint32), ("n_roles", ctypes.c_uint32), ("train_content", ctypes.c_uint32),
+                ("train_footer", ctypes.c_uint32), ("n_bos", ctypes.c_uint32), ("n_gen", ctypes.c_uint32),
+                ("n_header", ctypes.c_uint32 * 8), ("n_footer", ctypes.c_uint32 * 8), ("bos", ctypes.c_uint32 * 8), ("gen", ctypes.c_uint32 * 16),
+                ("header", ctypes.c_uint32 * 16 * 8), ("footer", ctypes.c_uint32 * 8 * 8)]
+
+    def __init__(self, flags=0, row_len=0, pad_id=0, ignore_id=0xFFFFFF9C, roles=(((), ()),), train_content=0, train_footer=0, bos=(), gen=()):
+        roles = [(tuple(h), tuple(f)) for h, f in roles]
+        super().__init__(ctypes.sizeof(SplChatOpts), flags, row_len, pad_id, ignore_id & 0xFFFFFFFF, len(roles), train_content, train_footer,
+                         len(bos), len(gen))
+        for r, (h, f) in enumerate(roles[:8]):
+            self.n_header[r], self.n_footer[r] = len(h), len(f)
+            for j, v in enumerate(h[:16]):
+                self.header[r][j] = v
+            for j, v in enumerate(f[:8]):
+                self.footer[r][j] = v
+        for j, v in enumerate(bos[:8]):
+            self.bos[j] = v
+        for j, v in enumerate(gen[:16]):
+            self.gen[j] = v
 
 
 class SplDecodeOpts(ctypes.Structure):
@@ -183,6 +210,10 @@ def lib() -> ctypes.CDLL:
     L.spl_pack_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.POINTER(SplCollateOpts), vp, ctypes.c_uint64, vp, vp, vp, vp]
     L.spl_pair_device.argtypes = [vp, vp, vp, ctypes.c_uint64, vp, vp, ctypes.c_uint64, vp, vp, ctypes.c_uint64, ctypes.POINTER(SplPairOpts),
                                   vp, vp, vp, vp, vp, vp, vp, vp]
+    L.spl_chat_work_bytes.restype = ctypes.c_uint64
+    L.spl_chat_work_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
+    L.spl_chat_device.argtypes = [vp, vp, vp, ctypes.c_uint64, vp, vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.POINTER(SplChatOpts)] + \
+        [vp] * 12
     L.spl_window_work_bytes.restype = ctypes.c_uint64
     L.spl_window_work_bytes.argtypes = [ctypes.c_uint64]
     L.spl_window_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.POINTER(SplCollateOpts), ctypes.c_uint32, vp, ctypes.c_uint64,

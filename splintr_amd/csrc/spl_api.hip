@@ -1,7 +1,7 @@
 // spl_api.hip -- the C ABI (include/splintr_hip.h): the root of the library's one HIP translation unit.  It includes the kernels
 // (spl_kernels.hip) and the host side, one file per concern and each building on the ones before it -- spl_host_res.h (resource owners,
 // pinned pool), spl_ctx.h (per-GPU context, handle, uploads), spl_streams.h (stream probe), spl_launch.h (memo, launch order, device
-// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_pair_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h, spl_seqscan_host.h, spl_stream_host.h, spl_stop_host.h -- and holds the entry points.
+// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_pair_host.h, spl_chat_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h, spl_seqscan_host.h, spl_stream_host.h, spl_stop_host.h -- and holds the entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -41,6 +41,7 @@ using namespace spl;
 #include "spl_collective.h"
 #include "spl_collate_host.h"
 #include "spl_pair_host.h"
+#include "spl_chat_host.h"
 #include "spl_window_host.h"
 #include "spl_decode_dev_host.h"
 #include "spl_spans_host.h"
@@ -486,6 +487,17 @@ int spl_pair_device(spl_tokenizer* t, const uint32_t* d_a_ids, const uint64_t* d
     return guarded("spl_pair_device", [&] {
         return pair_device(t, d_a_ids, d_a_off, n_a, d_b_ids, d_b_off, n_b, d_a_idx, d_b_idx, n_pairs, o, d_rows, d_mask, d_type, d_special,
                            d_len, d_kept, d_status, (hipStream_t)hip_stream); });
+}
+
+uint64_t spl_chat_work_bytes(uint64_t n_turns, uint64_t n_convs) { return chat_work_bytes(n_turns, n_convs); }
+
+int spl_chat_device(spl_tokenizer* t, const uint32_t* d_ids, const uint64_t* d_off, uint64_t n_docs, const int32_t* d_turn_doc,
+                    const uint8_t* d_turn_role, const uint8_t* d_turn_train, uint64_t n_turns, const uint64_t* d_conv_off, uint64_t n_convs,
+                    const spl_chat_opts* o, void* d_rows, void* d_labels, uint8_t* d_loss, uint8_t* d_mask, uint8_t* d_role, uint8_t* d_special,
+                    int32_t* d_len, int32_t* d_kept, int32_t* d_turn_col, uint32_t* d_status, void* d_work, void* hip_stream) {
+    return guarded("spl_chat_device", [&] {
+        return chat_device(t, d_ids, d_off, n_docs, d_turn_doc, d_turn_role, d_turn_train, n_turns, d_conv_off, n_convs, o, d_rows, d_labels,
+                           d_loss, d_mask, d_role, d_special, d_len, d_kept, d_turn_col, d_status, d_work, (hipStream_t)hip_stream); });
 }
 
 uint64_t spl_window_work_bytes(uint64_t n_docs) { return window_work_bytes(n_docs); }

@@ -8,6 +8,8 @@ PyTorch is plumbing here (device memory, streams, torch.distributed); the work i
 from __future__ import annotations
 
 import ctypes
+from collections import namedtuple
+from collections.abc import Mapping
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -310,6 +312,146 @@ def pair_device(tok: Tokenizer, batch_a: DeviceBatch, batch_b: DeviceBatch, max_
                            pad_id=pad_id, prefix=prefix, middle=middle, suffix=suffix, a_index=a_index, b_index=b_index,
                            truncation=truncation, truncation_side_a=truncation_side_a, truncation_side_b=truncation_side_b,
                            padding_side=padding_side, dtype=dtype)
+
+
+# ---------------------------------------------------------------------------------------------- chat: a CSR of messages, one row per conversation
+ChatRows = namedtuple("ChatRows", "input_ids labels attention_mask role_ids loss_mask special_tokens_mask lengths kept turn_cols status")
+
+
+def _chat_opts(row_len: int, pad_id: int, template, add_generation_prompt: bool, truncation: str, pin_system: bool, padding_side: str,
+               ignore_index: int, dtype):
+    """spl_chat_opts for one call; ValueError for what the Python surface can refuse by itself."""
+    from .chat import ChatTemplate
+    if not isinstance(template, ChatTemplate):
+        raise ValueError(f"template must be a splintr_amd.chat.ChatTemplate, not {type(template).__name__}")
+    if dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"dtype must be torch.int32 or torch.int64, not {dtype}")
+    if truncation not in ("right", "drop_oldest"):
+        raise ValueError(f"truncation must be 'right' or 'drop_oldest', not {truncation!r}")
+    if pin_system and truncation != "drop_oldest":
+        raise ValueError("pin_system keeps the first turn while older ones are dropped: it needs truncation='drop_oldest'")
+    flags = (_ffi.SPL_COLLATE_I64 if dtype == torch.int64 else 0) | \
+        (_ffi.SPL_COLLATE_PAD_LEFT if _side("padding_side", padding_side) else 0) | \
+        (_ffi.SPL_CHAT_DROP_OLDEST if truncation == "drop_oldest" else 0) | (_ffi.SPL_CHAT_PIN_FIRST if pin_system else 0)
+    if isinstance(pad_id, bool) or not isinstance(pad_id, (int, np.integer)) or not 0 <= int(pad_id) < (1 << 32):
+        raise ValueError("pad_id must fit 32 bits")
+    if isinstance(ignore_index, bool) or not isinstance(ignore_index, (int, np.integer)) or not -(1 << 31) <= int(ignore_index) < (1 << 32):
+        raise ValueError("ignore_index must fit 32 bits (a negative one is sign-extended in int64 labels)")
+    gen = template.generation if add_generation_prompt else ()
+    if isinstance(row_len, bool) or not isinstance(row_len, (int, np.integer)) or int(row_len) <= 0 or int(row_len) >= (1 << 32):
+        raise ValueError("the row length must be in 1 .. 2**32 - 1")
+    if int(row_len) < len(template.bos) + len(gen):
+        raise ValueError(f"the row length {int(row_len)} is smaller than the {len(template.bos) + len(gen)} ids of bos + generation prompt every row holds")
+    return _ffi.SplChatOpts(flags, int(row_len), int(pad_id), int(ignore_index) & 0xFFFFFFFF, list(template.roles.values()),
+                            template.train_content_mask, template.train_footer_mask, template.bos, gen)
+
+
+def check_chat_args(row_len: int, pad_id: int, template, add_generation_prompt: bool = False, truncation: str = "right",
+                    pin_system: bool = False, padding_side: str = "right", ignore_index: int = -100, dtype=torch.int32) -> None:
+    """ValueError for a template, dtype, truncation or side string, id or row length that chat_device would refuse -- for callers that
+    want to know before they put a batch on the device."""
+    _chat_opts(row_len, pad_id, template, add_generation_prompt, truncation, pin_system, padding_side, ignore_index, dtype)
+
+
+def chat_turns(conversations, template, train_turns=None):
+    """Conversations (sequences of {"role", "content"} dicts or (role, content) tuples) as host arrays: (texts, turn_doc int32, turn_role
+    uint8, turn_train uint8 or None, conv_off int64).  EQUAL content strings are one text: a system prompt that ten thousand conversations
+    share is encoded once.  train_turns: None, or per conversation a sequence of truth values, one per turn (False: the turn carries no
+    labels whatever its role).  ValueError for a malformed message or a role the template does not have."""
+    from .chat import message
+    if isinstance(conversations, (str, bytes, Mapping)) or not hasattr(conversations, "__len__"):
+        raise ValueError(f"conversations must be a sequence of conversations, not {type(conversations).__name__}")
+    if train_turns is not None and len(train_turns) != len(conversations):
+        raise ValueError("train_turns must hold one sequence per conversation")
+    texts, index, turn_doc, turn_role, turn_train, conv_off = [], {}, [], [], [], [0]
+    for c, conv in enumerate(conversations):
+        if isinstance(conv, (str, bytes, Mapping)) or not hasattr(conv, "__len__"):
+            raise ValueError(f"conversation {c} must be a sequence of messages, not {type(conv).__name__}")
+        if train_turns is not None and len(train_turns[c]) != len(conv):
+            raise ValueError(f"train_turns[{c}] must hold one value per turn of conversation {c}")
+        for i, m in enumerate(conv):
+            role, content = message(m)
+            turn_role.append(template.role_of(role))
+            if content not in index:
+                index[content] = len(texts)
+                texts.append(content)
+            turn_doc.append(index[content])
+            turn_train.append(1 if train_turns is None or train_turns[c][i] else 0)
+        conv_off.append(len(turn_doc))
+    if len(turn_doc) >= (1 << 31) or len(conv_off) > (1 << 31):
+        raise ValueError("fewer than 2**31 turns and conversations")
+    return (texts, np.array(turn_doc, dtype=np.int32), np.array(turn_role, dtype=np.uint8),
+            None if train_turns is None else np.array(turn_train, dtype=np.uint8), np.array(conv_off, dtype=np.int64))
+
+
+def chat_csr_device(tok: Tokenizer, ids: torch.Tensor, off: torch.Tensor, n_docs: int, turn_doc: Optional[torch.Tensor],
+                    turn_role: torch.Tensor, conv_off: torch.Tensor, max_length: int, *, template, pad_id: int,
+                    add_generation_prompt: bool = False, truncation: str = "right", pin_system: bool = False, padding_side: str = "right",
+                    ignore_index: int = -100, turn_train: Optional[torch.Tensor] = None, dtype: torch.dtype = torch.int32) -> ChatRows:
+    """chat_device's low-level form: the messages are (ids int32 [capacity], offsets int64 [at least n_docs + 1], ABSOLUTE into ids),
+    turn t has the role number turn_role[t] (uint8 [n_turns]; template.role_of) and the content document turn_doc[t] (int32; None: t),
+    conversation c owns the turns conv_off[c] .. conv_off[c + 1] - 1 (int64 [n_convs + 1]); turn_train (uint8, optional): 0 takes a
+    turn's labels away.  Same return as chat_device."""
+    o = _chat_opts(max_length, pad_id, template, add_generation_prompt, truncation, pin_system, padding_side, ignore_index, dtype)
+    n_docs = int(n_docs)
+    if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or ids.dim() != 1 or not ids.is_contiguous() or not ids.is_cuda:
+        raise ValueError("ids must be a contiguous int32 tensor of rank 1 on a GPU")
+    dev = ids.device
+    if not isinstance(off, torch.Tensor) or off.dtype != torch.int64 or off.dim() != 1 or not off.is_contiguous() or n_docs < 0 or \
+            off.shape[0] < n_docs + 1 or off.device != dev:
+        raise ValueError("off must be a contiguous int64 tensor of at least n_docs + 1 entries on the device of the ids")
+    if not isinstance(turn_role, torch.Tensor) or turn_role.dtype != torch.uint8 or turn_role.dim() != 1 or not turn_role.is_contiguous() or \
+            turn_role.device != dev:
+        raise ValueError("turn_role must be a contiguous uint8 tensor of rank 1 on the device of the ids")
+    n_turns = int(turn_role.shape[0])
+    for name, t, dt in (("turn_doc", turn_doc, torch.int32), ("turn_train", turn_train, torch.uint8)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dtype != dt or t.dim() != 1 or t.shape[0] != n_turns or
+                              not t.is_contiguous() or t.device != dev):
+            raise ValueError(f"{name} must be a contiguous {str(dt).split('.')[-1]} tensor of shape [n_turns] on the device of the ids")
+    if turn_doc is None and n_turns > n_docs:
+        raise ValueError(f"without turn_doc turn t reads document t: {n_turns} turns need as many documents, not {n_docs}")
+    if not isinstance(conv_off, torch.Tensor) or conv_off.dtype != torch.int64 or conv_off.dim() != 1 or conv_off.shape[0] < 1 or \
+            not conv_off.is_contiguous() or conv_off.device != dev:
+        raise ValueError("conv_off must be a contiguous int64 tensor of shape [n_convs + 1] on the device of the ids")
+    n_convs = int(conv_off.shape[0]) - 1
+    L = _ffi.lib()
+    new = lambda *shape, dt: torch.empty(*shape, dtype=dt, device=dev)          # (every element is written by the kernels)
+    rows, labels = new(n_convs, o.row_len, dt=dtype), new(n_convs, o.row_len, dt=dtype)
+    mask, role, loss, special = (new(n_convs, o.row_len, dt=torch.uint8) for _ in range(4))
+    lens, kept = new(n_convs, dt=torch.int32), new(n_convs, 2, dt=torch.int32)
+    turn_cols = torch.full((n_turns, 2), -1, dtype=torch.int32, device=dev)     # (a turn outside every conversation is not written)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    work = torch.empty(int(L.spl_chat_work_bytes(n_turns, n_convs)), dtype=torch.uint8, device=dev)
+    # (d_rows may never be null; without a conversation nothing is written, and an empty tensor has no address: any aligned one stands in)
+    rc = L.spl_chat_device(tok.handle, ids.data_ptr(), off.data_ptr(), n_docs, _ptr(turn_doc), turn_role.data_ptr() if n_turns else None,
+                           _ptr(turn_train), n_turns, conv_off.data_ptr(), n_convs, ctypes.byref(o),
+                           rows.data_ptr() if n_convs else work.data_ptr(), _ptr(labels), _ptr(loss), _ptr(mask), _ptr(role), _ptr(special),
+                           _ptr(lens), _ptr(kept), _ptr(turn_cols), status.data_ptr(), work.data_ptr(),
+                           torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        _raise_rc(rc, "spl_chat_device")
+    return ChatRows(rows, labels, mask, role, loss, special, lens, kept, turn_cols, status)
+
+
+def chat_device(tok: Tokenizer, batch: DeviceBatch, turn_doc: Optional[torch.Tensor], turn_role: torch.Tensor, conv_off: torch.Tensor,
+                max_length: int, *, template, pad_id: int, add_generation_prompt: bool = False, truncation: str = "right",
+                pin_system: bool = False, padding_side: str = "right", ignore_index: int = -100,
+                turn_train: Optional[torch.Tensor] = None, dtype: torch.dtype = torch.int32) -> ChatRows:
+    """batch's CSR (encode_device: one document per distinct MESSAGE) as ONE ROW PER CONVERSATION with labels, two launches on torch's
+    current stream (spl_chat_device): row c = bos + the turns of conversation c, each as its role's header + the message's ids + its
+    role's footer, + the generation prompt (add_generation_prompt), padded with pad_id.  A body longer than max_length - len(bos +
+    generation prompt) is cut on the right (truncation "right") or loses whole turns from the front until it fits ("drop_oldest";
+    pin_system keeps turn 0); bos and the generation prompt are never cut away.  The control tokens come from `template`
+    (splintr_amd.chat.ChatTemplate), never from message text.  Returns ChatRows: input_ids [n_convs, L]; labels (same dtype: the id on
+    content and footer of the turns whose role the template trains -- and whose turn_train is not 0 --, ignore_index elsewhere, not
+    shifted); attention_mask uint8; role_ids uint8 (the role number over a turn's header, content and footer, 255 elsewhere);
+    loss_mask uint8 (1 where labels hold an id); special_tokens_mask uint8 (1 on template ids and padding); lengths int32 [n_convs];
+    kept int32 [n_convs, 2] (turns dropped, body entries cut off on the right); turn_cols int32 [n_turns, 2] (the columns of turn t's
+    content in its row, (-1, -1) if it is not there); status int32 [1] (1: a role, document index or turn range was out of range).
+    All device tensors, nothing synchronises."""
+    return chat_csr_device(tok, batch.ids, batch.out_off, batch.n_docs, turn_doc, turn_role, conv_off, max_length, template=template,
+                           pad_id=pad_id, add_generation_prompt=add_generation_prompt, truncation=truncation, pin_system=pin_system,
+                           padding_side=padding_side, ignore_index=ignore_index, turn_train=turn_train, dtype=dtype)
 
 
 # ---------------------------------------------------------------------------------------------- device-resident decode

@@ -374,6 +374,36 @@ class Tokenizer:
             raise IndexError(f"encode_batch_pairs: an entry of a_index / b_index names no text (valid: 0 .. {n_a - 1} for a, 0 .. {n_b - 1} for b)")
         return out
 
+    def encode_batch_chat(self, conversations, max_length: int, *, template, pad_id: int, add_generation_prompt: bool = False,
+                          truncation: str = "right", pin_system: bool = False, padding_side: str = "right", ignore_index: int = -100,
+                          train_turns=None, with_special: bool = False, dtype=None, check: bool = False):
+        """Extension: multi-turn CONVERSATIONS as one row each ON THE GPU, with labels (Hugging Face's apply_chat_template with
+        tokenize=True and return_assistant_tokens_mask=True).  conversations: a sequence of sequences of {"role", "content"} dicts or
+        (role, content) tuples; template: a splintr_amd.chat.ChatTemplate (ChatTemplate.chatml(tok), ChatTemplate.llama3(tok)).  Row c
+        = bos + per turn (the role's header + the message's ids + the role's footer) + the generation prompt (add_generation_prompt),
+        padded to max_length.  Every message is encoded by itself and equal message strings ONCE (a shared system prompt is one
+        document of the device batch); the control tokens come from the template, so with with_special=False, the default, message
+        text that spells <|eot_id|> stays ordinary text and cannot forge a turn.  truncation "right" cuts the body at the row's end,
+        "drop_oldest" removes whole turns from the front (pin_system keeps turn 0).  train_turns: per conversation one truth value per
+        turn, False takes that turn's labels away.  Returns splintr_amd.device.ChatRows (input_ids, labels, attention_mask, role_ids,
+        loss_mask, special_tokens_mask, lengths, kept, turn_cols, status), torch tensors on this tokenizer's device; nothing
+        synchronises.  check=True reads status (ONE synchronisation) and raises IndexError if it is set."""
+        import torch
+        from . import device as dv
+        dtype = torch.int32 if dtype is None else dtype
+        dv.check_chat_args(max_length, pad_id, template, add_generation_prompt, truncation, pin_system, padding_side, ignore_index,
+                           dtype)                    # (before anything goes to the device)
+        texts, turn_doc, turn_role, turn_train, conv_off = dv.chat_turns(conversations, template, train_turns)
+        dv, batch = self._encode_on_device(texts, with_special)
+        dev = batch.ids.device
+        up = lambda a: None if a is None else torch.from_numpy(a).to(dev)
+        out = dv.chat_device(self, batch, up(turn_doc), up(turn_role), up(conv_off), max_length, template=template, pad_id=pad_id,
+                             add_generation_prompt=add_generation_prompt, truncation=truncation, pin_system=pin_system,
+                             padding_side=padding_side, ignore_index=ignore_index, turn_train=up(turn_train), dtype=dtype)
+        if check and int(out.status.item()):
+            raise IndexError("encode_batch_chat: a role, a document index or a turn range was out of range")
+        return out
+
     def encode_batch_with_offsets(self, texts: Sequence[str], *, unit: str = "char", with_special: bool = False):
         """Extension: encode_batch plus WHERE every token lies in its text -- (ids list[list[int]], spans list[list[(start, end)]]), a
         span in characters (unit="char": Python str indices, Hugging Face's offset_mapping; a token that begins inside a character
