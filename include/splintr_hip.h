@@ -497,6 +497,106 @@ int spl_chat_device(spl_tokenizer* t,
                     int32_t* d_turn_col /* [n_turns*2] */, uint32_t* d_status /* one word, cleared by the caller */,
                     void* d_work /* spl_chat_work_bytes */, void* hip_stream);
 
+/* WHOLE-SEQUENCE PACKING: n_seqs sequences binned into rows of row_len, several per row and NONE CUT IN TWO -- what a fine-tuning or
+ * reranker trainer does to a padded batch before the model sees it (torchtune's PackedDataset, TRL's packing / padding_free, NeMo's
+ * sequence packing).  Labels and up to four byte arrays travel with the ids, position ids restart at every sequence, and the boundaries
+ * come out in the form a variable-length attention kernel takes.  spl_pack_device is the pre-training form (one stream cut every row_len,
+ * documents cross rows, ids only); this call keeps every sequence whole.  The reference has no counterpart; the conventions of the
+ * collate family hold: fully asynchronous on `hip_stream`, nothing allocated, nothing synchronised, the handle used only for its device
+ * and its test options, ids as bit patterns.  Two launches: ONE workgroup plans, a gather writes every output element once.
+ *
+ * Input     exactly one of two forms, named by which of in->d_lengths and in->d_off is not NULL:
+ *             rows form  d_ids [n_seqs, in_len] of the ROWS' dtype (int32, or int64 with SPL_COLLATE_I64: the low 32 bits are the id),
+ *                        d_lengths int32 [n_seqs]; sequence i is d_ids[i, 0 .. len) -- or d_ids[i, in_len - len .. in_len) with
+ *                        SPL_COLLATE_PAD_LEFT (the INPUT is left padded) -- as spl_pad_device, spl_pair_device and spl_chat_device leave it.
+ *             CSR form   d_ids int32 [capacity], d_off [n_seqs + 1]: sequence i is d_ids[off[i] .. off[i + 1]), offsets ABSOLUTE, as
+ *                        spl_encode_batch_device leaves it.  The ids (and labels) of a CSR are int32 whatever dtype the rows have.
+ *           Companions in the layout AND element type of d_ids, each optional (NULL): d_labels; d_bytes[0 .. 3], uint8.
+ * Clipping  a sequence's length is min(len, row_len): a longer one is cut and keeps its head, or its tail with SPL_COLLATE_KEEP_TAIL.
+ *           A sequence of length 0 takes no place.
+ * Placement o->strategy:
+ *             SPL_SEQPACK_NEXT_FIT             order preserving.  Walk the sequences in index order with a current row fill f: a
+ *                        non-empty sequence of clipped length l opens a new row if there is no row yet or f + l > row_len; it lands at
+ *                        column f of the current row, then f += l.
+ *             SPL_SEQPACK_BEST_FIT_DECREASING  the non-empty sequences are taken by clipped length DESCENDING, ties by ascending index.
+ *                        Each goes into the open row whose residual capacity is the smallest one >= l; among rows of that same residual
+ *                        into the one that reached that residual most recently (LIFO); if no row has room it opens a new row.  Rows are
+ *                        numbered in opening order; within a row the sequences sit in placement order without gaps.
+ *                        row_len <= SPL_SEQPACK_BFD_MAX_ROW_LEN (a table over the residuals lives in the 160 KB of a workgroup's LDS),
+ *                        and ONE LANE places the sequences one after the other: measured at 0.9 us per sequence (1.2 us at row_len
+ *                        16 384) where NEXT_FIT's whole plan costs 0.01 us per sequence (profiles/seqpack.txt, 2 500 sequences).
+ *                        Beyond about 4 000 sequences -- where this walk outlasts the gather of a [2500, 16384] batch -- take
+ *                        NEXT_FIT unless the rows saved (1 to 2 % there) are worth milliseconds.
+ *           Worked by hand (the rows as lists of sequence indices):
+ *             row_len 10, lengths 6 5 5 4             NEXT_FIT [0] [1 2] [3];  BEST_FIT_DECREASING [0 3] [1 2]
+ *             row_len 10, lengths 3 0 7 1 12 10 5 5   NEXT_FIT [0 2] [3] [4] [5] [6 7] (sequence 1 unplaced, sequence 4 cut to 10);
+ *                                                     BEST_FIT_DECREASING [4] [5] [2 0] [6 7] [3]
+ *             row_len 7,  lengths 4 4 3 3 3 3         BEST_FIT_DECREASING [0 3] [1 2] [4 5] (the LIFO tie)
+ *           Both plans run in one workgroup, which for n_seqs beyond a few thousand keeps its arrays in d_work instead of LDS: correct
+ *           for every n_seqs < 2^31, but sized for batches (thousands of sequences), not corpora.  (For tests, spl_set_option
+ *           "seqpack_lds_max", 0 .. 4096, default 4096, lowers the n_seqs up to which the arrays are in LDS.)
+ * Outputs   out->d_rows, d_status and d_work are required, every other output is optional (NULL: not wanted, not written).  The
+ *           [max_rows, row_len] arrays are written in full -- rows from n[0] on hold only padding -- and nothing behind them.
+ *             d_rows       the ids; padding holds pad_id.
+ *             d_labels     the rows' dtype; padding holds ignore_id; with SPL_SEQPACK_MASK_FIRST the entry at every sequence's FIRST
+ *                          column holds ignore_id too (labels are not shifted: the model would otherwise learn a sequence's first
+ *                          token from its neighbour's last).  In int64 a word equal to ignore_id is SIGN-extended (it is a number),
+ *                          any other word ZERO-extended (an id).  Written only if in->d_labels is given as well.
+ *             d_bytes[k]   byte array k; padding holds o->fill[k].  Written only if in->d_bytes[k] is given as well.
+ *             d_mask       bytes: 1 where the entry is not padding.
+ *             d_pos        int32: position ids, 0 at every sequence's first column, 0 in padding.
+ *             d_seq        int32: the source sequence's index, -1 in padding.
+ *             d_place      int32 [n_seqs, 2]: (row, column) of every sequence, (-1, -1) for an empty one.  Rows at or beyond max_rows
+ *                          are reported here although they are not written.
+ *             d_fill       int32 [max_rows]: the entries of a row that are not padding (0 from the rows written on).
+ *             d_cu         int32 [n_seqs + max_rows + 1]: the ascending boundaries of the flattened view of the rows WRITTEN
+ *                          (W = min(n[0], max_rows)): every sequence start row * row_len + column, the start of every row's padding
+ *                          tail where it has one, and the closing W * row_len.  n[2] entries; the rest is not written.  (With max_rows
+ *                          >= n[0] the closing entry is n[0] * row_len and the array is what a varlen attention call takes as it is.)
+ *             d_n          int64 [4]: rows needed, ids placed (of all rows needed), entries of d_cu, sequences cut.
+ *             d_status     one word, cleared by the caller; a plain store of 1 for a length below 0 or above in_len, or offsets that
+ *                          decrease.  Such a sequence counts as empty.
+ * Capacity  max_rows = n_seqs always suffices.  With fewer rows than needed the rows beyond max_rows are not written and n[0] still
+ *           reports the need (spl_pack_device's contract).  NEXT_FIT never uses more than 2 * ceil(ids / row_len) rows.
+ * Work      d_work: spl_seqpack_work_bytes(n_seqs, max_rows, strategy) bytes of device memory, 16-byte aligned, for this call alone
+ *           until it has run.  A pure function of its arguments, monotone in the first two, a multiple of 16.
+ *
+ * SPL_EINVAL, with the cause in spl_last_error() and before anything touches the device: a null handle, in, o, out, d_rows, d_status or
+ * d_work; a struct_size shorter than a struct or above 4096; both input forms or neither; null d_ids with n_seqs > 0; an unknown flag
+ * bit (SPL_COLLATE_BOS, _EOS are not flags of this call; SPL_COLLATE_PAD_LEFT only in the rows form); an unknown strategy;
+ * row_len == 0; BEST_FIT_DECREASING with row_len > SPL_SEQPACK_BFD_MAX_ROW_LEN; n_seqs >= 2^31 or max_rows >= 2^31; max_rows * row_len
+ * >= 2^31 with d_cu given (it is int32); the rows form with in_len == 0 while n_seqs > 0; d_rows, d_labels, d_pos, d_seq, d_place,
+ * d_fill, d_cu, d_n or d_work not 16-byte aligned; a byte output or d_mask not 4-byte aligned; d_lengths not 4-byte, d_off not 8-byte
+ * aligned.  The element type of d_ids cannot be seen from a pointer: the Python layer refuses a tensor of the wrong dtype. */
+#define SPL_SEQPACK_NEXT_FIT            0u
+#define SPL_SEQPACK_BEST_FIT_DECREASING 1u
+#define SPL_SEQPACK_MASK_FIRST          32u   /* the label at every sequence's first column is ignore_id */
+/* also accepted: SPL_COLLATE_I64, SPL_COLLATE_PAD_LEFT (the input rows are left padded), SPL_COLLATE_KEEP_TAIL */
+#define SPL_SEQPACK_BFD_MAX_ROW_LEN     32768u
+
+typedef struct spl_seqpack_opts {
+    uint32_t struct_size;                 /* sizeof the struct as the CALLER was compiled */
+    uint32_t flags, strategy, row_len, pad_id, ignore_id;
+    uint8_t fill[4];                      /* what pads byte array k */
+} spl_seqpack_opts;
+typedef struct spl_seqpack_in {
+    uint32_t struct_size, in_len;         /* in_len: the columns of the input rows (rows form) */
+    uint64_t n_seqs;
+    const void* d_ids; const int32_t* d_lengths; const uint64_t* d_off;
+    const void* d_labels; const uint8_t* d_bytes[4];
+} spl_seqpack_in;
+typedef struct spl_seqpack_out {
+    uint32_t struct_size, reserved;
+    uint64_t max_rows;
+    void* d_rows; void* d_labels; uint8_t* d_bytes[4]; uint8_t* d_mask;
+    int32_t* d_pos; int32_t* d_seq; int32_t* d_place; int32_t* d_fill; int32_t* d_cu; int64_t* d_n;
+    uint32_t* d_status;
+} spl_seqpack_out;
+
+uint64_t spl_seqpack_work_bytes(uint64_t n_seqs, uint64_t max_rows, uint32_t strategy);
+int spl_seqpack_device(spl_tokenizer* t, const spl_seqpack_in* in, const spl_seqpack_opts* o, const spl_seqpack_out* out,
+                       void* d_work /* spl_seqpack_work_bytes */, void* hip_stream);
+
 /* SLIDING WINDOWS over the CSR: every document alone and complete, as rows of row_len that overlap by `overlap` ids -- the one
  * per-document layout that loses nothing (pad mode truncates, pack mode joins documents), and what Hugging Face tokenizers call
  * return_overflowing_tokens with stride = overlap.  The reference has no counterpart, as for pad and pack; the same conventions hold:

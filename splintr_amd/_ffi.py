@@ -29,7 +29,7 @@ SYMBOLS = [
     "spl_comm_unique_id", "spl_comm_create", "spl_comm_destroy", "spl_comm_rank", "spl_comm_world",
     "spl_allgather_slabs", "spl_allgather_slabs_p2p", "spl_gatherv_unpack_at", "spl_allgatherv_csr", "spl_split_host", "spl_encode_chunks_device",
     "spl_split_device", "spl_device_split_fallbacks", "spl_small_path_calls", "spl_pick_stream", "spl_memo_stats", "spl_memo_seed_stats", "spl_debug_memo_entry",
-    "spl_pad_device", "spl_pack_device", "spl_pair_device", "spl_chat_work_bytes", "spl_chat_device", "spl_window_work_bytes", "spl_window_device",
+    "spl_pad_device", "spl_pack_device", "spl_pair_device", "spl_chat_work_bytes", "spl_chat_device", "spl_seqpack_work_bytes", "spl_seqpack_device", "spl_window_work_bytes", "spl_window_device",
     "spl_decode_reserve_device", "spl_decode_batch_device", "spl_max_token_bytes", "spl_token_spans_device",
     "spl_stream_reserve_device", "spl_stream_decode_device",
     "spl_get_option", "spl_stop_reserve_device", "spl_stop_match_device",
@@ -41,6 +41,7 @@ SPL_PAIR_MAX_FIXED, SPL_PAIR_KEEP_TAIL_A, SPL_PAIR_KEEP_TAIL_B = 32, 32, 64
 SPL_PAIR_LONGEST_FIRST, SPL_PAIR_ONLY_FIRST, SPL_PAIR_ONLY_SECOND = 0, 1, 2
 SPL_CHAT_DROP_OLDEST, SPL_CHAT_PIN_FIRST, SPL_CHAT_NO_ROLE = 32, 64, 255
 SPL_CHAT_MAX_ROLES, SPL_CHAT_MAX_HEADER, SPL_CHAT_MAX_FOOTER, SPL_CHAT_MAX_BOS, SPL_CHAT_MAX_GEN = 8, 16, 8, 8, 16
+SPL_SEQPACK_NEXT_FIT, SPL_SEQPACK_BEST_FIT_DECREASING, SPL_SEQPACK_MASK_FIRST, SPL_SEQPACK_BFD_MAX_ROW_LEN = 0, 1, 32, 32768
 SPL_DECODE_I64, SPL_DECODE_PAD_LEFT, SPL_DECODE_SKIP_SPECIAL = 1, 2, 4
 SPL_SPANS_I64 = 1
 SPL_STREAM_REPLACE, SPL_STREAM_FINAL_ALL = 1, 2
@@ -100,6 +101,37 @@ class SplChatOpts(ctypes.Structure):
             self.bos[j] = v
         for j, v in enumerate(gen[:16]):
             self.gen[j] = v
+
+
+class SplSeqpackOpts(ctypes.Structure):
+    """spl_seqpack_opts (include/splintr_hip.h): the row, the strategy and what pads each output of spl_seqpack_device."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("strategy", ctypes.c_uint32), ("row_len", ctypes.c_uint32),
+                ("pad_id", ctypes.c_uint32), ("ignore_id", ctypes.c_uint32), ("fill", ctypes.c_uint8 * 4)]
+
+    def __init__(self, flags=0, strategy=0, row_len=0, pad_id=0, ignore_id=0xFFFFFF9C, fill=(0, 0, 0, 0)):
+        super().__init__(ctypes.sizeof(SplSeqpackOpts), flags, strategy, row_len, pad_id, ignore_id & 0xFFFFFFFF, (ctypes.c_uint8 * 4)(*fill))
+
+
+class SplSeqpackIn(ctypes.Structure):
+    """spl_seqpack_in: the sequences -- rows + lengths, or a CSR -- and their companions, device addresses (None: not given)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("in_len", ctypes.c_uint32), ("n_seqs", ctypes.c_uint64), ("d_ids", ctypes.c_void_p),
+                ("d_lengths", ctypes.c_void_p), ("d_off", ctypes.c_void_p), ("d_labels", ctypes.c_void_p), ("d_bytes", ctypes.c_void_p * 4)]
+
+    def __init__(self, n_seqs=0, in_len=0, ids=None, lengths=None, off=None, labels=None, byte_arrays=(None,) * 4):
+        super().__init__(ctypes.sizeof(SplSeqpackIn), in_len, n_seqs, ids, lengths, off, labels, (ctypes.c_void_p * 4)(*byte_arrays))
+
+
+class SplSeqpackOut(ctypes.Structure):
+    """spl_seqpack_out: where the outputs go, device addresses (None: not wanted)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("max_rows", ctypes.c_uint64), ("d_rows", ctypes.c_void_p),
+                ("d_labels", ctypes.c_void_p), ("d_bytes", ctypes.c_void_p * 4), ("d_mask", ctypes.c_void_p), ("d_pos", ctypes.c_void_p),
+                ("d_seq", ctypes.c_void_p), ("d_place", ctypes.c_void_p), ("d_fill", ctypes.c_void_p), ("d_cu", ctypes.c_void_p),
+                ("d_n", ctypes.c_void_p), ("d_status", ctypes.c_void_p)]
+
+    def __init__(self, max_rows=0, rows=None, labels=None, byte_arrays=(None,) * 4, mask=None, pos=None, seq=None, place=None, fill=None,
+                 cu=None, n=None, status=None):
+        super().__init__(ctypes.sizeof(SplSeqpackOut), 0, max_rows, rows, labels, (ctypes.c_void_p * 4)(*byte_arrays), mask, pos, seq, place,
+                         fill, cu, n, status)
 
 
 class SplDecodeOpts(ctypes.Structure):
@@ -214,6 +246,9 @@ def lib() -> ctypes.CDLL:
     L.spl_chat_work_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
     L.spl_chat_device.argtypes = [vp, vp, vp, ctypes.c_uint64, vp, vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.POINTER(SplChatOpts)] + \
         [vp] * 12
+    L.spl_seqpack_work_bytes.restype = ctypes.c_uint64
+    L.spl_seqpack_work_bytes.argtypes = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]
+    L.spl_seqpack_device.argtypes = [vp, ctypes.POINTER(SplSeqpackIn), ctypes.POINTER(SplSeqpackOpts), ctypes.POINTER(SplSeqpackOut), vp, vp]
     L.spl_window_work_bytes.restype = ctypes.c_uint64
     L.spl_window_work_bytes.argtypes = [ctypes.c_uint64]
     L.spl_window_device.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.POINTER(SplCollateOpts), ctypes.c_uint32, vp, ctypes.c_uint64,

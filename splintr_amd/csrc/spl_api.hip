@@ -1,7 +1,7 @@
 // spl_api.hip -- the C ABI (include/splintr_hip.h): the root of the library's one HIP translation unit.  It includes the kernels
 // (spl_kernels.hip) and the host side, one file per concern and each building on the ones before it -- spl_host_res.h (resource owners,
 // pinned pool), spl_ctx.h (per-GPU context, handle, uploads), spl_streams.h (stream probe), spl_launch.h (memo, launch order, device
-// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_pair_host.h, spl_chat_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h, spl_seqscan_host.h, spl_stream_host.h, spl_stop_host.h -- and holds the entry points.
+// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_pair_host.h, spl_chat_host.h, spl_seqpack_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h, spl_seqscan_host.h, spl_stream_host.h, spl_stop_host.h -- and holds the entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -42,6 +42,7 @@ using namespace spl;
 #include "spl_collate_host.h"
 #include "spl_pair_host.h"
 #include "spl_chat_host.h"
+#include "spl_seqpack_host.h"
 #include "spl_window_host.h"
 #include "spl_decode_dev_host.h"
 #include "spl_spans_host.h"
@@ -155,6 +156,7 @@ int spl_set_option(spl_tokenizer* t, const char* name, int64_t value) {
     else if (k == "decode_chunk_ids" && value >= 1024) t->dec_chunk_ids = (uint64_t)value;
     else if (k == "sdma_d2h") t->sdma_d2h = value != 0;        // (where the HSA runtime or the device's agent cannot be found: hipMemcpyAsync, silently)
     else if (k == "window_totals_chunk" && value >= 1 && value <= (int64_t)WIN_CHUNK) t->win_chunk = (uint32_t)value;
+    else if (k == "seqpack_lds_max" && value >= 0 && value <= (int64_t)SQP_LDS_MAX) t->seqpack_lds_max = (uint32_t)value;
     else if (k == "stream_one_max" && value >= 0 && value <= (int64_t)ST_ONE_MAX) t->stream_one_max = (uint32_t)value;
     else if (k == "stop_one_max" && value >= 0 && value <= (int64_t)SP_ONE_MAX) t->stop_one_max = (uint32_t)value;
     else if (k == "slab_pack24") {
@@ -177,6 +179,7 @@ int spl_get_option(const spl_tokenizer* t, const char* name, int64_t* value) {
         {"memo", t->memo}, {"memo_first", t->memo_first}, {"memo_bits", t->memo_bits}, {"memo_long_bits", t->memo_long_bits},
         {"memo_log_cap", t->memo_log_cap}, {"fuse_max_tiles", t->fuse_max_tiles}, {"copy_threads", t->copy_threads},
         {"decode_chunk_ids", (int64_t)t->dec_chunk_ids}, {"sdma_d2h", t->sdma_d2h}, {"window_totals_chunk", t->win_chunk},
+        {"seqpack_lds_max", t->seqpack_lds_max},
         {"stream_one_max", t->stream_one_max}, {"stop_one_max", t->stop_one_max}, {"slab_pack24", t->slab_pack24},
     };
     for (const auto& e : all)
@@ -498,6 +501,13 @@ int spl_chat_device(spl_tokenizer* t, const uint32_t* d_ids, const uint64_t* d_o
     return guarded("spl_chat_device", [&] {
         return chat_device(t, d_ids, d_off, n_docs, d_turn_doc, d_turn_role, d_turn_train, n_turns, d_conv_off, n_convs, o, d_rows, d_labels,
                            d_loss, d_mask, d_role, d_special, d_len, d_kept, d_turn_col, d_status, d_work, (hipStream_t)hip_stream); });
+}
+
+uint64_t spl_seqpack_work_bytes(uint64_t n_seqs, uint64_t max_rows, uint32_t strategy) { (void)strategy; return sqp_work_bytes(n_seqs, max_rows); }
+
+int spl_seqpack_device(spl_tokenizer* t, const spl_seqpack_in* in, const spl_seqpack_opts* o, const spl_seqpack_out* out, void* d_work,
+                       void* hip_stream) {
+    return guarded("spl_seqpack_device", [&] { return seqpack_device(t, in, o, out, d_work, (hipStream_t)hip_stream); });
 }
 
 uint64_t spl_window_work_bytes(uint64_t n_docs) { return window_work_bytes(n_docs); }

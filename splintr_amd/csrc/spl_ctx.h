@@ -213,6 +213,7 @@ struct spl_tokenizer {
     int slab_pack24 = 0;                      // the ids of the all-gather slabs travel three bytes each (spl_set_option "slab_pack24": every rank alike)
     uint32_t stream_one_max = ST_ONE_DEFAULT;    // "stream_one_max": most sequences spl_stream_decode_device takes in its one-launch form
     uint32_t stop_one_max = SP_ONE_DEFAULT;      // "stop_one_max": most sequences spl_stop_match_device takes in its one-launch form
+    uint32_t seqpack_lds_max = SQP_LDS_MAX;  // "seqpack_lds_max" (tests): most sequences whose plan arrays spl_seqpack_device keeps in LDS, so that a few hundred reach the work-buffer form
     uint32_t win_chunk = WIN_CHUNK;          // "window_totals_chunk" (tests): span totals k_window_totals scans per round, so that a few thousand documents reach its second round
     int sdma_d2h = 0;                         // (measured, +0.5..3 %: not the default) pipeline chunks: their ids leave through hsa_amd_memory_async_copy (an SDMA engine) instead of hipMemcpyAsync
     uint64_t dec_chunk_ids = 2ull << 20;      // decode pipeline: ids per chunk (batches of fewer than three such chunks are decoded in one piece; C3: 28.3 GB/s at 1 M, 30.5 at 2 M, 29.6 at 3 M)

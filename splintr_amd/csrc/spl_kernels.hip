@@ -20,6 +20,7 @@
 //   spl_k_collate.h    k_collate_pad / k_collate_pack: the CSR as padded rows, or as one stream cut into rows (and their host-testable mapping)
 //   spl_k_pair.h       k_collate_pair: two CSRs joined into one row per pair of documents -- prefix A' middle B' suffix, truncated by rule (and its host-testable mapping)
 //   spl_k_chat.h       k_chat_turns, k_collate_chat: a CSR of messages joined into one row per multi-turn conversation -- role headers and footers, labels, oldest turns dropped (and its host-testable mapping)
+//   spl_k_seqpack.h    k_seqpack_next_fit / _bfd, k_seqpack_gather: whole sequences binned into rows, none cut -- the plan in one workgroup, labels, position ids, cu_seqlens (and its host-testable decisions)
 //   spl_k_window.h     k_window_scan / _totals / _add / _gather: the CSR as overlapping windows of every document (rows per document by a scan over launches)
 //   spl_k_decode_dev.h k_dec_len / k_dec_gather: ids in HBM (CSR or rows) to a bytes CSR in HBM (and their host-testable mapping)
 //   spl_k_spans.h      k_span_len / k_span_write: ids in HBM (CSR or rows) to per-id byte and character spans (and their host-testable mapping)
@@ -189,6 +190,7 @@ __device__ __forceinline__ uint32_t tidx() {
 #include "spl_k_collate.h"
 #include "spl_k_pair.h"
 #include "spl_k_chat.h"
+#include "spl_k_seqpack.h"
 #include "spl_k_window.h"
 #include "spl_k_decode_dev.h"
 #include "spl_k_spans.h"

@@ -454,6 +454,146 @@ def chat_device(tok: Tokenizer, batch: DeviceBatch, turn_doc: Optional[torch.Ten
                            padding_side=padding_side, ignore_index=ignore_index, turn_train=turn_train, dtype=dtype)
 
 
+# ---------------------------------------------------------------------------------------------- whole-sequence packing
+PackedRows = namedtuple("PackedRows", "input_ids labels attention_mask position_ids seq_ids loss_mask role_ids special_tokens_mask extra "
+                                      "seq_place row_fill cu_seqlens n status")
+SEQPACK_STRATEGIES = {"next_fit": _ffi.SPL_SEQPACK_NEXT_FIT, "best_fit_decreasing": _ffi.SPL_SEQPACK_BEST_FIT_DECREASING}
+SEQPACK_FILLS = (0, _ffi.SPL_CHAT_NO_ROLE, 1, 0)     # what pads loss_mask, role_ids, special_tokens_mask, extra: chat_device's own padding
+
+
+def _seqpack_opts(row_len: int, pad_id: int, strategy: str, ignore_index: int, fills, truncation_side: str, padding_side: str,
+                  mask_first: bool, dtype, max_rows):
+    """spl_seqpack_opts for one call; ValueError for what the Python surface can refuse by itself."""
+    if strategy not in SEQPACK_STRATEGIES:
+        raise ValueError(f"strategy must be 'next_fit' or 'best_fit_decreasing', not {strategy!r}")
+    if dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"dtype must be torch.int32 or torch.int64, not {dtype}")
+    if isinstance(pad_id, bool) or not isinstance(pad_id, (int, np.integer)) or not 0 <= int(pad_id) < (1 << 32):
+        raise ValueError("pad_id must fit 32 bits")
+    if isinstance(ignore_index, bool) or not isinstance(ignore_index, (int, np.integer)) or not -(1 << 31) <= int(ignore_index) < (1 << 32):
+        raise ValueError("ignore_index must fit 32 bits (a negative one is sign-extended in int64 labels)")
+    if isinstance(row_len, bool) or not isinstance(row_len, (int, np.integer)) or int(row_len) <= 0 or int(row_len) >= (1 << 32):
+        raise ValueError("the row length must be in 1 .. 2**32 - 1")
+    if strategy == "best_fit_decreasing" and int(row_len) > _ffi.SPL_SEQPACK_BFD_MAX_ROW_LEN:
+        raise ValueError(f"best_fit_decreasing takes rows of up to {_ffi.SPL_SEQPACK_BFD_MAX_ROW_LEN} ids; next_fit has no such bound")
+    fills = tuple(fills)
+    if len(fills) != 4 or any(isinstance(f, bool) or not isinstance(f, (int, np.integer)) or not 0 <= int(f) < 256 for f in fills):
+        raise ValueError("fills must be four byte values: what pads loss_mask, role_ids, special_tokens_mask and extra")
+    if max_rows is not None and (isinstance(max_rows, bool) or not isinstance(max_rows, (int, np.integer)) or not 0 <= int(max_rows) < (1 << 31)):
+        raise ValueError("max_rows must be in 0 .. 2**31 - 1")
+    flags = (_ffi.SPL_COLLATE_I64 if dtype == torch.int64 else 0) | \
+        (_ffi.SPL_COLLATE_PAD_LEFT if _side("padding_side", padding_side) else 0) | \
+        (_ffi.SPL_COLLATE_KEEP_TAIL if _side("truncation_side", truncation_side) else 0) | (_ffi.SPL_SEQPACK_MASK_FIRST if mask_first else 0)
+    return _ffi.SplSeqpackOpts(flags, SEQPACK_STRATEGIES[strategy], int(row_len), int(pad_id), int(ignore_index) & 0xFFFFFFFF, fills)
+
+
+def check_seqpack_args(row_len: int, *, pad_id: int, strategy: str = "best_fit_decreasing", ignore_index: int = -100, fills=SEQPACK_FILLS,
+                       truncation_side: str = "right", padding_side: str = "right", mask_first: bool = True, dtype=torch.int32,
+                       max_rows: Optional[int] = None) -> None:
+    """ValueError for a strategy, dtype, side string, id, fill, row length or max_rows that seqpack_rows_device / seqpack_csr_device would
+    refuse -- for callers that want to know before they put a batch on the device."""
+    _seqpack_opts(row_len, pad_id, strategy, ignore_index, fills, truncation_side, padding_side, mask_first, dtype, max_rows)
+
+
+def _seqpack_call(tok: Tokenizer, o, si, dev, n_seqs: int, have_labels: bool, have_bytes, dtype, max_rows: Optional[int]) -> PackedRows:
+    R = n_seqs if max_rows is None else int(max_rows)
+    L, row_len = _ffi.lib(), o.row_len
+    if R * row_len >= (1 << 31):
+        raise ValueError(f"cu_seqlens is int32: max_rows * seq_len = {R * row_len} must be below 2**31")
+    new = lambda *shape, dt: torch.empty(*shape, dtype=dt, device=dev)          # (every element is written by the kernels)
+    rows = new(R, row_len, dt=dtype)
+    labels = new(R, row_len, dt=dtype) if have_labels else None
+    byts = [new(R, row_len, dt=torch.uint8) if h else None for h in have_bytes]
+    mask, pos, seq = new(R, row_len, dt=torch.uint8), new(R, row_len, dt=torch.int32), new(R, row_len, dt=torch.int32)
+    place, fill, n = new(n_seqs, 2, dt=torch.int32), new(R, dt=torch.int32), new(4, dt=torch.int64)
+    cu = torch.zeros(n_seqs + R + 1, dtype=torch.int32, device=dev)             # (entries behind n[2] are not written)
+    status = torch.zeros(1, dtype=torch.int32, device=dev)
+    work = torch.empty(int(L.spl_seqpack_work_bytes(n_seqs, R, o.strategy)), dtype=torch.uint8, device=dev)
+    so = _ffi.SplSeqpackOut(R, rows.data_ptr() if R else work.data_ptr(), _ptr(labels), [_ptr(b) for b in byts], _ptr(mask), _ptr(pos), _ptr(seq),
+                            _ptr(place), _ptr(fill), cu.data_ptr(), n.data_ptr(), status.data_ptr())
+    rc = L.spl_seqpack_device(tok.handle, ctypes.byref(si), ctypes.byref(o), ctypes.byref(so), work.data_ptr(),
+                              torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        _raise_rc(rc, "spl_seqpack_device")
+    return PackedRows(rows, labels, mask, pos, seq, byts[0], byts[1], byts[2], byts[3], place, fill, cu, n, status)
+
+
+def _seqpack_companions(ids: torch.Tensor, labels, byte_arrays):
+    names = ("loss_mask", "role_ids", "special_tokens_mask", "extra")
+    if labels is not None and (not isinstance(labels, torch.Tensor) or labels.dtype != ids.dtype or labels.shape != ids.shape or
+                               not labels.is_contiguous() or labels.device != ids.device):
+        raise ValueError("labels must be a contiguous tensor of the dtype, shape and device of the ids")
+    for name, b in zip(names, byte_arrays):
+        if b is not None and (not isinstance(b, torch.Tensor) or b.dtype != torch.uint8 or b.shape != ids.shape or not b.is_contiguous() or
+                              b.device != ids.device):
+            raise ValueError(f"{name} must be a contiguous uint8 tensor of the shape and device of the ids")
+
+
+def seqpack_rows_device(tok: Tokenizer, ids: torch.Tensor, lengths: torch.Tensor, seq_len: int, *, pad_id: int,
+                        strategy: str = "best_fit_decreasing", labels: Optional[torch.Tensor] = None, loss_mask: Optional[torch.Tensor] = None,
+                        role_ids: Optional[torch.Tensor] = None, special_tokens_mask: Optional[torch.Tensor] = None,
+                        extra: Optional[torch.Tensor] = None, padding_side: str = "right", truncation_side: str = "right",
+                        ignore_index: int = -100, mask_first: bool = True, fills=SEQPACK_FILLS, max_rows: Optional[int] = None) -> PackedRows:
+    """Padded rows -- what pad_device, pair_device and chat_device return: ids [n_seqs, L_in] int32 or int64, lengths int32 [n_seqs],
+    padded on `padding_side` -- PACKED: several whole sequences per row of seq_len, none cut in two, two launches on torch's current stream
+    (spl_seqpack_device).  A sequence longer than seq_len keeps its head (truncation_side "right") or its tail.  strategy "next_fit"
+    keeps the order (a sequence that does not fit the current row opens the next one); "best_fit_decreasing" takes the sequences longest
+    first and puts each into the fullest row that still has room (fewer rows; seq_len <= 32768; one GPU lane places the sequences one
+    by one, so for tens of thousands of sequences take next_fit).  labels (the ids' dtype) and the uint8 arrays loss_mask, role_ids,
+    special_tokens_mask, extra travel with the ids; padding holds pad_id, ignore_index and fills.  mask_first puts ignore_index at every
+    sequence's first label (labels are not shifted: the model would learn a sequence's first token from its neighbour's last).  Returns
+    PackedRows: input_ids [max_rows, seq_len], labels, attention_mask uint8, position_ids int32 (0 at every sequence start), seq_ids int32
+    (-1 in padding), the byte arrays, seq_place int32 [n_seqs, 2] ((row, column); (-1, -1): empty), row_fill int32 [max_rows], cu_seqlens
+    int32 (n[2] entries: every sequence start and every padding tail of the flattened rows, then the end -- what a varlen attention call
+    takes), n int64 [4] (rows needed, ids placed, entries of cu_seqlens, sequences cut), status int32 [1] (1: a length was out of
+    range).  max_rows defaults to n_seqs, which always suffices; with fewer, n[0] still reports the need.  All device tensors, nothing
+    synchronises."""
+    if not isinstance(ids, torch.Tensor) or ids.dtype not in (torch.int32, torch.int64) or ids.dim() != 2 or not ids.is_contiguous() or not ids.is_cuda:
+        raise ValueError("ids must be a contiguous int32 or int64 tensor of rank 2 on a GPU")
+    o = _seqpack_opts(seq_len, pad_id, strategy, ignore_index, fills, truncation_side, padding_side, mask_first, ids.dtype, max_rows)
+    n_seqs, in_len = int(ids.shape[0]), int(ids.shape[1])
+    if not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.int32 or lengths.shape != (n_seqs,) or not lengths.is_contiguous() or \
+            lengths.device != ids.device:
+        raise ValueError("lengths must be a contiguous int32 tensor of shape [n_seqs] on the device of the ids")
+    byts = (loss_mask, role_ids, special_tokens_mask, extra)
+    _seqpack_companions(ids, labels, byts)
+    if n_seqs and in_len == 0:
+        raise ValueError("the input rows have no columns")
+    anchor = lengths if n_seqs else torch.zeros(4, dtype=torch.int32, device=ids.device)         # (an empty tensor has no address)
+    si = _ffi.SplSeqpackIn(n_seqs, in_len, _ptr(ids), anchor.data_ptr(), None, _ptr(labels), [_ptr(b) for b in byts])
+    return _seqpack_call(tok, o, si, ids.device, n_seqs, labels is not None, [b is not None for b in byts], ids.dtype, max_rows)
+
+
+def seqpack_csr_device(tok: Tokenizer, ids: torch.Tensor, offsets: torch.Tensor, n_seqs: int, seq_len: int, *, pad_id: int,
+                       strategy: str = "best_fit_decreasing", labels: Optional[torch.Tensor] = None, loss_mask: Optional[torch.Tensor] = None,
+                       role_ids: Optional[torch.Tensor] = None, special_tokens_mask: Optional[torch.Tensor] = None,
+                       extra: Optional[torch.Tensor] = None, truncation_side: str = "right", ignore_index: int = -100, mask_first: bool = True,
+                       fills=SEQPACK_FILLS, dtype: torch.dtype = torch.int32, max_rows: Optional[int] = None) -> PackedRows:
+    """seqpack_rows_device for a CSR -- what encode_device leaves: ids int32 [capacity], offsets int64 [at least n_seqs + 1], ABSOLUTE into
+    ids; labels (int32) and the uint8 arrays in the layout of the ids.  dtype: that of the rows returned.  Same return."""
+    o = _seqpack_opts(seq_len, pad_id, strategy, ignore_index, fills, truncation_side, "right", mask_first, dtype, max_rows)
+    n_seqs = int(n_seqs)
+    if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or ids.dim() != 1 or not ids.is_contiguous() or not ids.is_cuda:
+        raise ValueError("ids must be a contiguous int32 tensor of rank 1 on a GPU")
+    if not isinstance(offsets, torch.Tensor) or offsets.dtype != torch.int64 or offsets.dim() != 1 or not offsets.is_contiguous() or n_seqs < 0 or \
+            offsets.shape[0] < n_seqs + 1 or offsets.device != ids.device:
+        raise ValueError("offsets must be a contiguous int64 tensor of at least n_seqs + 1 entries on the device of the ids")
+    byts = (loss_mask, role_ids, special_tokens_mask, extra)
+    _seqpack_companions(ids, labels, byts)
+    si = _ffi.SplSeqpackIn(n_seqs, 0, ids.data_ptr(), None, offsets.data_ptr(), _ptr(labels), [_ptr(b) for b in byts])
+    return _seqpack_call(tok, o, si, ids.device, n_seqs, labels is not None, [b is not None for b in byts], dtype, max_rows)
+
+
+def seqpack_trim(p: PackedRows) -> PackedRows:
+    """p cut to the rows that are used and the cu_seqlens entries that are written: ONE synchronisation (n goes to the host)."""
+    n = p.n.tolist()
+    r = min(int(n[0]), int(p.input_ids.shape[0]))
+    cut = lambda t: None if t is None else t[:r]
+    return PackedRows(cut(p.input_ids), cut(p.labels), cut(p.attention_mask), cut(p.position_ids), cut(p.seq_ids), cut(p.loss_mask),
+                      cut(p.role_ids), cut(p.special_tokens_mask), cut(p.extra), p.seq_place, cut(p.row_fill), p.cu_seqlens[:int(n[2])], p.n,
+                      p.status)
+
+
 # ---------------------------------------------------------------------------------------------- device-resident decode
 def _max_bytes(max_bytes) -> int:
     if isinstance(max_bytes, bool) or not isinstance(max_bytes, (int, np.integer)) or not 0 <= int(max_bytes) < (1 << 62):

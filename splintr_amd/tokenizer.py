@@ -404,6 +404,54 @@ class Tokenizer:
             raise IndexError("encode_batch_chat: a role, a document index or a turn range was out of range")
         return out
 
+    def encode_batch_chat_packed(self, conversations, seq_len: int, *, template, pad_id: int, strategy: str = "best_fit_decreasing",
+                                 add_generation_prompt: bool = False, truncation: str = "right", pin_system: bool = False,
+                                 ignore_index: int = -100, train_turns=None, with_special: bool = False, dtype=None, mask_first: bool = True,
+                                 max_rows: Optional[int] = None, trim: bool = True, check: bool = False):
+        """Extension: encode_batch_chat PACKED ON THE GPU for fine-tuning -- several whole conversations per row of seq_len, none cut in
+        two (torchtune's PackedDataset, TRL's packing): encode_batch_chat with max_length = seq_len, then
+        splintr_amd.device.seqpack_rows_device over its rows; labels, loss_mask, role_ids and special_tokens_mask travel along.  strategy
+        "best_fit_decreasing" (fewest rows; seq_len <= 32768) or "next_fit" (keeps the order).  mask_first: the label at every
+        conversation's first column is ignore_index.  Returns splintr_amd.device.PackedRows (input_ids, labels, attention_mask,
+        position_ids, seq_ids, loss_mask, role_ids, special_tokens_mask, extra (None), seq_place, row_fill, cu_seqlens, n, status).  trim
+        (default) cuts the tensors to the rows used and cu_seqlens to its entries: ONE synchronisation; trim=False returns [max_rows,
+        seq_len] tensors (max_rows defaults to the number of conversations) and synchronises nothing.  check=True raises IndexError if
+        encode_batch_chat's status is set."""
+        import torch
+        from . import device as dv
+        dtype = torch.int32 if dtype is None else dtype
+        dv.check_seqpack_args(seq_len, pad_id=pad_id, strategy=strategy, ignore_index=ignore_index, mask_first=mask_first, dtype=dtype,
+                              max_rows=max_rows)       # (before anything goes to the device)
+        rows = self.encode_batch_chat(conversations, seq_len, template=template, pad_id=pad_id, add_generation_prompt=add_generation_prompt,
+                                      truncation=truncation, pin_system=pin_system, ignore_index=ignore_index, train_turns=train_turns,
+                                      with_special=with_special, dtype=dtype, check=check)
+        out = dv.seqpack_rows_device(self, rows.input_ids, rows.lengths, seq_len, pad_id=pad_id, strategy=strategy, labels=rows.labels,
+                                     loss_mask=rows.loss_mask, role_ids=rows.role_ids, special_tokens_mask=rows.special_tokens_mask,
+                                     ignore_index=ignore_index, mask_first=mask_first, max_rows=max_rows)
+        return dv.seqpack_trim(out) if trim else out
+
+    def encode_batch_packed_whole(self, texts: Sequence[str], seq_len: int, *, pad_id: int, bos_id: Optional[int] = None,
+                                  eos_id: Optional[int] = None, strategy: str = "best_fit_decreasing", truncation_side: str = "right",
+                                  with_special: bool = False, dtype=None, max_rows: Optional[int] = None, trim: bool = True):
+        """Extension: encode_batch as packed rows ON THE GPU with every document WHOLE -- [bos_id] ids [eos_id] of several documents per
+        row of seq_len, none cut in two (encode_batch_packed cuts one stream every seq_len instead).  A document longer than seq_len
+        is truncated (BOS and EOS are never cut away).  Returns splintr_amd.device.PackedRows without labels and byte arrays; seq_ids
+        are document numbers, cu_seqlens what a varlen attention call takes.  trim as for encode_batch_chat_packed."""
+        import torch
+        from . import device as dv
+        dtype = torch.int32 if dtype is None else dtype
+        dv.check_collate_args(seq_len, pad_id, bos_id, eos_id, dtype, "right", truncation_side)
+        dv.check_seqpack_args(seq_len, pad_id=pad_id, strategy=strategy, truncation_side=truncation_side, dtype=dtype, max_rows=max_rows)
+        dv, batch = self._encode_on_device(texts, with_special)
+        if bos_id is None and eos_id is None:           # the CSR as it is
+            out = dv.seqpack_csr_device(self, batch.ids, batch.out_off, batch.n_docs, seq_len, pad_id=pad_id, strategy=strategy,
+                                        truncation_side=truncation_side, dtype=dtype, max_rows=max_rows)
+        else:                                           # BOS and EOS join a document in pad_device's rows
+            rows, _, lens = dv.pad_device(self, batch, seq_len, pad_id=pad_id, bos_id=bos_id, eos_id=eos_id, truncation_side=truncation_side,
+                                          dtype=dtype)
+            out = dv.seqpack_rows_device(self, rows, lens, seq_len, pad_id=pad_id, strategy=strategy, max_rows=max_rows)
+        return dv.seqpack_trim(out) if trim else out
+
     def encode_batch_with_offsets(self, texts: Sequence[str], *, unit: str = "char", with_special: bool = False):
         """Extension: encode_batch plus WHERE every token lies in its text -- (ids list[list[int]], spans list[list[(start, end)]]), a
         span in characters (unit="char": Python str indices, Hugging Face's offset_mapping; a token that begins inside a character
