@@ -147,6 +147,8 @@ uint32_t spl_n_devices(const spl_tokenizer* t);
  *                            form beyond (0: always three; profiles/stream_decode.txt has the measured crossing)
  *   "stop_one_max"           0..1024 (64): spl_stop_match_device takes its one-launch form up to this many sequences, the three-launch form
  *                            beyond (0: always three; profiles/stop_match.txt has the measured crossing)
+ *   "heal_phase"             0..2 (0): measuring only -- 1: spl_heal_begin_device / spl_heal_step_device launch their plan alone, 2: their fill
+ *                            alone, over the scratch the last plan left (profiles/token_mask.txt)
  *   "slab_pack24"            0/1 (0): the ids of the all-gather slabs travel three bytes each; every rank alike; refused (SPL_EINVAL) when an
  *                            id of the tokenizer -- vocabulary or special token -- does not fit 24 bits
  * Unknown names and values out of range: SPL_EINVAL. */
@@ -912,6 +914,98 @@ int spl_stop_match_device(spl_tokenizer* t,
                           uint8_t* d_out_bytes, uint64_t out_capacity,
                           uint64_t* d_out_off /* [n_seqs+1] */,
                           int32_t* d_hit /* [n_seqs] */, void* hip_stream);
+
+/* TOKEN HEALING for n_seqs sequences at once, everything in DEVICE memory: the input side of the sampler.  A prompt that
+ * ends inside a word ("http:", "def foo(", a trailing space) ends with a token the model has rarely seen in front of the intended
+ * continuation.  The remedy (guidance, llguidance): take the last token or tokens off the prompt and, until their bytes are spelled again,
+ * let the model sample only ids whose bytes agree with them.  The id -> bytes tables already lie in HBM, so the mask [n_seqs, n_words] is
+ * written where the sampler reads it; no trie on the host, no copy per step.  "The answer must begin with this text" is the same
+ * primitive: the caller writes the text into the state rows and calls the step with row_len 0.
+ *
+ * b(t) is what spl_decode_batch_device emits for id t.  t is ORDINARY if it is an id of the vocabulary proper and b(t) has at least one
+ * byte; ids that only the special-token map holds, ids the vocabulary lacks and ids above its largest id are not ordinary.
+ *
+ * Per sequence there is a pending prefix P of 0 .. SPL_HEAL_MAX_PREFIX bytes.
+ *   |P| = 0   the sequence is FREE: its mask row is all ones, in every bit of every one of its n_words words.
+ *   |P| >= 1  it is CONSTRAINED: bit t is set iff t is ordinary and either b(t) starts with P (t COVERS; it may be longer than 64 bytes) or
+ *             P starts with b(t) and b(t) is shorter than P (t is PARTIAL).  Every other bit of the row is 0, bits beyond the largest id
+ *             included.
+ * The mask: int32 [n_seqs, n_words], n_words >= ceil((largest vocabulary id + 1) / 32) the caller's choice (a model's logits are often
+ * wider than the vocabulary); bit t & 31 of word t >> 5 stands for id t, 1 = allowed -- the layout xgrammar's and vLLM's
+ * apply_token_bitmask kernels read.
+ *
+ * STEP: per sequence the first clamp(d_len[b], 0, row_len) ids of row b of d_ids [n_seqs, row_len] (d_len NULL: all; row_len may be 0)
+ * are applied in order.  Free: stays free, whatever the id.  t covers: P becomes empty, `healed` is set.  t is partial: its bytes leave the
+ * front of P.  Anything else -- a special, an id of neither map, an int64 value outside 0 .. 2^32 - 1, an ordinary id that disagrees with
+ * P -- BREAKS the sequence: P becomes empty, the sticky `broken` is set, and it runs free from then on.  The call then writes the mask of
+ * the state it arrived at; row_len 0 only writes masks.
+ *
+ * BEGIN: prompts as rows d_ids [n_seqs, row_len] with d_len (NULL: every entry valid; SPL_HEAL_PAD_LEFT: a row's valid entries are its
+ * LAST d_len[b], and d_len is required), o->max_back in 0 .. SPL_HEAL_MAX_BACK, o->min_keep.  Per sequence, with P empty, for j = 1, 2, ...
+ * and t_j the j-th token from the end, stop at the first of: j > max_back; fewer than min_keep tokens would remain (len - j < min_keep);
+ * t_j is not ordinary; |b(t_j)| + |P| > 64; under SPL_HEAL_AUTO only: no ordinary token's bytes start with b(t_j) + P and are strictly
+ * longer than it.  Otherwise P := b(t_j) + P.  d_n_back[b] is the number of tokens taken: the caller feeds the model the first
+ * len - n_back tokens; the rows are not written.  Without SPL_HEAL_AUTO exactly as many tokens are taken as the other limits allow; with
+ * it "http" ":" is rolled back over ":" because "://" exists, and over "http" too only if some token extends "http:".
+ *
+ * The state row (SPL_HEAL_STATE_WORDS uint64 per sequence; all zero is free and fresh, so a reset is the caller zeroing rows; every bit not
+ * named is 0 and P's bytes from |P| on are 0, so rows compare bit for bit):
+ *     word 0      bits 0..6 |P|     bit 8 broken     bit 9 healed (it was constrained once and a covering token ended it)
+ *     words 1..8  P, the first byte lowest
+ * d_state_out may be d_state_in.  No other output may coincide with an input or with another output.
+ *
+ * Further outputs, each optional (NULL): d_live [n_seqs] uint8, 1 where the sequence is constrained after the call; d_n int32 [2], the
+ * number of constrained sequences and the number that broke in this call (device memory, like everything else).
+ * SPL_HEAL_KEEP_FREE: the rows of sequences that are free after the call are not written at all -- the caller filled them with ones
+ * once; long after every prompt has healed the call then writes nothing.
+ *
+ * What the rule is NOT: the allowed set ignores the split pattern, as every implementation of healing does, so the healed ids need not be
+ * the canonical encoding of the text; and UTF-8 validity of the continuation is not part of it.
+ *
+ * Two launches on hip_stream: a plan (a wavefront per sequence: the transition, then the covering ids as ONE range of the ordinary ids
+ * sorted by their bytes, found with one pivot per lane, then the partial ids from the prefix order) and a fill (whole words, each written
+ * once).  No atomics on global memory, no wait between workgroups.  spl_heal_reserve_device uploads the decode tables and builds the
+ * sorted order, id -> rank and the prefix order (synchronises once; again after spl_add_special) and sizes the scratch -- 264 bytes per
+ * sequence, grow-only, shared with nothing; after it a call within that size neither allocates nor synchronises.  Healing calls of ONE
+ * handle share the scratch: they need stream order among themselves.
+ *
+ * SPL_EINVAL, with the cause in spl_last_error() and before anything touches the device: a null t, in, o, out, d_state_out or d_mask; a
+ * null d_state_in (step) or d_n_back (begin); a null d_ids where there is an id to read; SPL_HEAL_PAD_LEFT without d_len; a struct_size
+ * shorter than a struct or above 4096; an unknown flag bit (SPL_HEAL_AUTO and _PAD_LEFT are flags of begin alone); n_words * 32 below the
+ * largest vocabulary id + 1, or n_words above 2^26; max_back above SPL_HEAL_MAX_BACK; n_seqs >= 2^31; an array not aligned to its element
+ * type; an output that coincides with an input (other than state out with state in) or with another output.  Arguments are refused,
+ * never clamped.  The element type of d_ids cannot be seen from a pointer: SPL_HEAL_I64 names it, the Python layer refuses other dtypes.
+ * A vocabulary in which more than 63 ids spell prefixes of one 64-byte string (many ids with equal bytes) is refused by the reserve. */
+#define SPL_HEAL_AUTO        1u  /* begin: take a token only if some ordinary token extends what has been taken */
+#define SPL_HEAL_KEEP_FREE   2u  /* rows of sequences that are free after the call are not written */
+#define SPL_HEAL_I64         4u  /* d_ids are int64 (torch.long); default int32 / uint32 bit patterns */
+#define SPL_HEAL_PAD_LEFT    8u  /* begin: a row's valid entries are its LAST d_len[b] */
+#define SPL_HEAL_STATE_WORDS 9
+#define SPL_HEAL_MAX_PREFIX  64
+#define SPL_HEAL_MAX_BACK    8
+
+typedef struct spl_heal_opts {
+    uint32_t struct_size;                 /* sizeof the struct as the CALLER was compiled */
+    uint32_t flags, n_words;
+    uint32_t max_back, min_keep;          /* begin only */
+} spl_heal_opts;
+typedef struct spl_heal_in {
+    uint32_t struct_size, row_len;        /* row_len: the columns of d_ids (step: may be 0) */
+    uint64_t n_seqs;
+    const void* d_ids; const int32_t* d_len;
+    const uint64_t* d_state_in;           /* step only: [n_seqs, SPL_HEAL_STATE_WORDS] */
+} spl_heal_in;
+typedef struct spl_heal_out {
+    uint32_t struct_size, reserved;
+    uint64_t* d_state_out;                /* [n_seqs, SPL_HEAL_STATE_WORDS] */
+    int32_t* d_mask;                      /* [n_seqs, n_words] */
+    uint8_t* d_live; int32_t* d_n;        /* NULL ok */
+    int32_t* d_n_back;                    /* begin only: [n_seqs] */
+} spl_heal_out;
+
+int spl_heal_reserve_device(spl_tokenizer* t, uint64_t max_seqs);
+int spl_heal_begin_device(spl_tokenizer* t, const spl_heal_in* in, const spl_heal_opts* o, const spl_heal_out* out, void* hip_stream);
+int spl_heal_step_device(spl_tokenizer* t, const spl_heal_in* in, const spl_heal_opts* o, const spl_heal_out* out, void* hip_stream);
 
 /* Host-side lookup of ONE id, for consumers that decode token by token on the CPU -- the streaming
  * decoders (src/core/streaming.rs, src/python/bindings.rs:465-834 take clones of Tokenizer::decoder

@@ -33,6 +33,7 @@ SYMBOLS = [
     "spl_decode_reserve_device", "spl_decode_batch_device", "spl_max_token_bytes", "spl_token_spans_device",
     "spl_stream_reserve_device", "spl_stream_decode_device",
     "spl_get_option", "spl_stop_reserve_device", "spl_stop_match_device",
+    "spl_heal_reserve_device", "spl_heal_begin_device", "spl_heal_step_device",
 ]
 SPL_PATTERN_CUSTOM = 3
 SPL_OPT_BYTE_LEVEL = 1
@@ -47,6 +48,8 @@ SPL_SPANS_I64 = 1
 SPL_STREAM_REPLACE, SPL_STREAM_FINAL_ALL = 1, 2
 SPL_STOP_SLOTS, SPL_STOP_MAX_LEN, SPL_STOP_TABLE_BYTES, SPL_STOP_STATE_WORDS = 64, 64, 64 * 64 + 64, 10
 SPL_STOP_INCLUDE, SPL_STOP_FINAL_ALL = 1, 2
+SPL_HEAL_AUTO, SPL_HEAL_KEEP_FREE, SPL_HEAL_I64, SPL_HEAL_PAD_LEFT = 1, 2, 4, 8
+SPL_HEAL_STATE_WORDS, SPL_HEAL_MAX_PREFIX, SPL_HEAL_MAX_BACK = 9, 64, 8
 
 
 class SplOpts(ctypes.Structure):
@@ -140,6 +143,33 @@ class SplDecodeOpts(ctypes.Structure):
 
     def __init__(self, flags=0, row_len=0):
         super().__init__(ctypes.sizeof(SplDecodeOpts), flags, row_len)
+
+
+class SplHealOpts(ctypes.Structure):
+    """spl_heal_opts (include/splintr_hip.h): flags, the words of a mask row, and what a begin may take off a prompt."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("n_words", ctypes.c_uint32), ("max_back", ctypes.c_uint32),
+                ("min_keep", ctypes.c_uint32)]
+
+    def __init__(self, flags=0, n_words=0, max_back=0, min_keep=0):
+        super().__init__(ctypes.sizeof(SplHealOpts), flags, n_words, max_back, min_keep)
+
+
+class SplHealIn(ctypes.Structure):
+    """spl_heal_in: the rows of ids, their lengths and (step) the state rows, device addresses (None: not given)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("row_len", ctypes.c_uint32), ("n_seqs", ctypes.c_uint64), ("d_ids", ctypes.c_void_p),
+                ("d_len", ctypes.c_void_p), ("d_state_in", ctypes.c_void_p)]
+
+    def __init__(self, n_seqs=0, row_len=0, ids=None, lengths=None, state=None):
+        super().__init__(ctypes.sizeof(SplHealIn), row_len, n_seqs, ids, lengths, state)
+
+
+class SplHealOut(ctypes.Structure):
+    """spl_heal_out: where the outputs go, device addresses (None: not wanted)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("d_state_out", ctypes.c_void_p), ("d_mask", ctypes.c_void_p),
+                ("d_live", ctypes.c_void_p), ("d_n", ctypes.c_void_p), ("d_n_back", ctypes.c_void_p)]
+
+    def __init__(self, state=None, mask=None, live=None, n=None, n_back=None):
+        super().__init__(ctypes.sizeof(SplHealOut), 0, state, mask, live, n, n_back)
 
 
 _lib = None
@@ -267,6 +297,9 @@ def lib() -> ctypes.CDLL:
     L.spl_stop_reserve_device.argtypes = [vp, ctypes.c_uint64]
     L.spl_stop_match_device.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, vp, vp, vp, ctypes.c_uint32, vp, vp, vp, ctypes.c_uint64,
                                         vp, vp, vp]
+    L.spl_heal_reserve_device.argtypes = [vp, ctypes.c_uint64]
+    L.spl_heal_begin_device.argtypes = [vp, ctypes.POINTER(SplHealIn), ctypes.POINTER(SplHealOpts), ctypes.POINTER(SplHealOut), vp]
+    L.spl_heal_step_device.argtypes = [vp, ctypes.POINTER(SplHealIn), ctypes.POINTER(SplHealOpts), ctypes.POINTER(SplHealOut), vp]
     _lib = L
     return L
 

@@ -1,7 +1,7 @@
 // spl_api.hip -- the C ABI (include/splintr_hip.h): the root of the library's one HIP translation unit.  It includes the kernels
 // (spl_kernels.hip) and the host side, one file per concern and each building on the ones before it -- spl_host_res.h (resource owners,
 // pinned pool), spl_ctx.h (per-GPU context, handle, uploads), spl_streams.h (stream probe), spl_launch.h (memo, launch order, device
-// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_pair_host.h, spl_chat_host.h, spl_seqpack_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h, spl_seqscan_host.h, spl_stream_host.h, spl_stop_host.h -- and holds the entry points.
+// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_pair_host.h, spl_chat_host.h, spl_seqpack_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h, spl_seqscan_host.h, spl_stream_host.h, spl_stop_host.h, spl_heal_host.h -- and holds the entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -49,6 +49,7 @@ using namespace spl;
 #include "spl_seqscan_host.h"
 #include "spl_stream_host.h"
 #include "spl_stop_host.h"
+#include "spl_heal_host.h"
 
 namespace {
 // No exception crosses the C ABI: every entry point that allocates (std::bad_alloc), starts threads or grows
@@ -159,6 +160,7 @@ int spl_set_option(spl_tokenizer* t, const char* name, int64_t value) {
     else if (k == "seqpack_lds_max" && value >= 0 && value <= (int64_t)SQP_LDS_MAX) t->seqpack_lds_max = (uint32_t)value;
     else if (k == "stream_one_max" && value >= 0 && value <= (int64_t)ST_ONE_MAX) t->stream_one_max = (uint32_t)value;
     else if (k == "stop_one_max" && value >= 0 && value <= (int64_t)SP_ONE_MAX) t->stop_one_max = (uint32_t)value;
+    else if (k == "heal_phase" && value >= 0 && value <= 2) t->heal_phase = (uint32_t)value;
     else if (k == "slab_pack24") {
         if (value && std::max(t->ht.max_id, t->max_special_id) >= (1u << 24))
             return fail(SPL_EINVAL, "slab_pack24: an id of this tokenizer does not fit three bytes (vocabulary or special-token ids >= 2^24)");
@@ -180,7 +182,8 @@ int spl_get_option(const spl_tokenizer* t, const char* name, int64_t* value) {
         {"memo_log_cap", t->memo_log_cap}, {"fuse_max_tiles", t->fuse_max_tiles}, {"copy_threads", t->copy_threads},
         {"decode_chunk_ids", (int64_t)t->dec_chunk_ids}, {"sdma_d2h", t->sdma_d2h}, {"window_totals_chunk", t->win_chunk},
         {"seqpack_lds_max", t->seqpack_lds_max},
-        {"stream_one_max", t->stream_one_max}, {"stop_one_max", t->stop_one_max}, {"slab_pack24", t->slab_pack24},
+        {"stream_one_max", t->stream_one_max}, {"stop_one_max", t->stop_one_max}, {"heal_phase", t->heal_phase},
+        {"slab_pack24", t->slab_pack24},
     };
     for (const auto& e : all)
         if (k == e.first) { *value = e.second; return SPL_OK; }
@@ -218,7 +221,7 @@ static int spl_add_special_impl(spl_tokenizer* t, const uint8_t* literal, size_t
         if (general) t->special_general = true;
         t->specials.push_back(Special{lit, id});
     }
-    for (auto& c : t->ctx) { c->sp_uploaded = false; c->dec_uploaded = false; if (c->twin) c->twin->sp_uploaded = false; }
+    for (auto& c : t->ctx) { c->sp_uploaded = false; c->dec_uploaded = false; c->heal_uploaded = false; if (c->twin) c->twin->sp_uploaded = false; }
     t->max_special_id = 0;
     t->max_tok_bytes = 0;
     for (const auto& sp : t->specials) t->max_special_id = std::max(t->max_special_id, sp.id);
@@ -475,6 +478,18 @@ int spl_stop_match_device(spl_tokenizer* t, const uint8_t* d_in_bytes, uint64_t 
                                      .mask = d_mask, .fin = d_final, .flags = stop_flags, .state_in = d_state_in, .state_out = d_state_out,
                                      .out = d_out_bytes, .out_cap = out_capacity, .out_off = d_out_off, .hit = d_hit,
                                      .stream = (hipStream_t)hip_stream}); });
+}
+
+int spl_heal_reserve_device(spl_tokenizer* t, uint64_t max_seqs) {
+    return guarded("spl_heal_reserve_device", [&] { return heal_reserve_device(t, max_seqs); });
+}
+
+int spl_heal_begin_device(spl_tokenizer* t, const spl_heal_in* in, const spl_heal_opts* o, const spl_heal_out* out, void* hip_stream) {
+    return guarded("spl_heal_begin_device", [&] { return heal_device(t, true, in, o, out, (hipStream_t)hip_stream); });
+}
+
+int spl_heal_step_device(spl_tokenizer* t, const spl_heal_in* in, const spl_heal_opts* o, const spl_heal_out* out, void* hip_stream) {
+    return guarded("spl_heal_step_device", [&] { return heal_device(t, false, in, o, out, (hipStream_t)hip_stream); });
 }
 
 int spl_pack_device(spl_tokenizer* t, const uint32_t* d_ids, const uint64_t* d_out_off, uint64_t n_docs, const spl_collate_opts* o,

@@ -69,6 +69,9 @@ struct Ctx {
     DevBuf<uint64_t> d_stblk; uint64_t stblk_cap = 0;   // spl_stream_decode_device: block sums and per-sequence counts, 8 bytes per sequence and 8 per 16 of them (grow-only; shared with nothing)
     DevBuf<uint64_t> d_spblk; uint64_t spblk_cap = 0;   // spl_stop_match_device: block sums and per-sequence count, cut and hit, 24 bytes per sequence and 8 per 16 of them (grow-only; shared with nothing)
     DevBuf<uint64_t> d_snblk; uint64_t snblk_cap = 0;   // spl_token_spans_device: block sums of bytes and of characters, 16 bytes per 1 024 ids (grow-only; shared with nothing)
+    DevBuf<uint32_t> d_heal_sorted, d_heal_rank, d_heal_parent; uint32_t heal_n = 0;   // spl_heal_*_device: the ordinary ids by their bytes, id -> rank, the prefix order (upload_heal; rebuilt after spl_add_special)
+    bool heal_uploaded = false;
+    DevBuf<uint32_t> d_heal_scr; uint64_t heal_cap = 0;   // ... lo, hi and up to 63 partial ids per sequence, 264 bytes each (grow-only; shared with nothing)
     DevBuf<uint8_t> d_sp_lits;                 // uploaded lazily; invalidated by spl_add_special
     bool sp_uploaded = false;
     // workspace
@@ -212,6 +215,7 @@ struct spl_tokenizer {
     int small_path = 1;                       // batches of up to 4 KB take the latency path (encode_small)
     int slab_pack24 = 0;                      // the ids of the all-gather slabs travel three bytes each (spl_set_option "slab_pack24": every rank alike)
     uint32_t stream_one_max = ST_ONE_DEFAULT;    // "stream_one_max": most sequences spl_stream_decode_device takes in its one-launch form
+    uint32_t heal_phase = 0;                     // "heal_phase": measuring only -- 1 the healing calls launch their plan alone, 2 their fill alone (over the scratch the last plan left)
     uint32_t stop_one_max = SP_ONE_DEFAULT;      // "stop_one_max": most sequences spl_stop_match_device takes in its one-launch form
     uint32_t seqpack_lds_max = SQP_LDS_MAX;  // "seqpack_lds_max" (tests): most sequences whose plan arrays spl_seqpack_device keeps in LDS, so that a few hundred reach the work-buffer form
     uint32_t win_chunk = WIN_CHUNK;          // "window_totals_chunk" (tests): span totals k_window_totals scans per round, so that a few thousand documents reach its second round

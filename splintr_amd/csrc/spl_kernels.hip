@@ -27,6 +27,7 @@
 //   spl_k_seqscan.h    seq_one_body / seq_len_body / seq_write_body: the count-scan-write driver of the per-sequence ops below, one launch or three
 //   spl_k_stream.h     k_stream_one / k_stream_len / k_stream_write: one step of B streaming decoders, per-sequence UTF-8 state (and their host-testable mapping)
 //   spl_k_stop.h       k_stop_one / k_stop_len / k_stop_write: stop strings over the streaming decode's bytes, per-sequence match state and hold-back (and their host-testable mapping)
+//   spl_k_heal.h       k_heal_plan / k_heal_fill: token healing -- per-sequence byte prefixes to allowed-token bitmasks [B, n_words] (and their host-testable first half)
 //   (spl_rx_split.h, included by spl_api.hip: the device splitter for custom split patterns; its host half is in spl_launch.h)
 // (The multi-pass pipeline of rounds 1-3 -- k_bpe_lanes64, k_count, k_scan, k_compact_docs and the k_pretok
 //  instantiations without tile records -- was removed in round 4: no BASELINE configuration reached it.)
@@ -196,3 +197,4 @@ __device__ __forceinline__ uint32_t tidx() {
 #include "spl_k_spans.h"
 #include "spl_k_stream.h"
 #include "spl_k_stop.h"
+#include "spl_k_heal.h"

@@ -1100,6 +1100,221 @@ class DeviceStreamingDecoder:
         return f"DeviceStreamingDecoder(batch_size={self.batch_size}, errors={self._errors!r})"
 
 
+# ---------------------------------------------------------------------------------------------- token healing (allowed-token bitmasks from byte prefixes)
+def heal_reserve(tok: Tokenizer, max_seqs: int) -> None:
+    """spl_heal_reserve_device: the decode tables, the sorted order of the ordinary ids and their prefix order on the device, and scratch
+    for max_seqs sequences; heal_begin_device / heal_step_device calls within that size then neither allocate nor synchronise."""
+    rc = _ffi.lib().spl_heal_reserve_device(tok.handle, int(max_seqs))
+    if rc != 0:
+        _raise_rc(rc, "spl_heal_reserve_device")
+
+
+def heal_n_words(tok: Tokenizer) -> int:
+    """The words of a mask row that cover every id the tokenizer knows (specials included)."""
+    return (tok.vocab_size + 31) // 32
+
+
+def heal_state_from_prefixes(prefixes, device=None) -> torch.Tensor:
+    """State rows int64 [len(prefixes), 9] for fresh sequences whose pending prefix is the given text (str: its UTF-8; empty: free), built
+    on the host -- "the answer must begin with this text": heal_step_device with ids None then writes the first masks.  ValueError for a
+    prefix over 64 bytes.  The tensor goes to `device` (default: the current GPU)."""
+    if isinstance(prefixes, (str, bytes, bytearray)) or not hasattr(prefixes, "__iter__"):
+        raise ValueError("prefixes must be a list of str or bytes")
+    prefixes = list(prefixes)
+    rows = np.zeros((len(prefixes), _ffi.SPL_HEAL_STATE_WORDS), dtype=np.uint64)
+    for b, x in enumerate(prefixes):
+        if isinstance(x, str):
+            x = x.encode("utf-8")
+        elif not isinstance(x, (bytes, bytearray)):
+            raise ValueError(f"prefix {b} must be str or bytes, not {type(x).__name__}")
+        if len(x) > _ffi.SPL_HEAL_MAX_PREFIX:
+            raise ValueError(f"prefix {b} must have at most {_ffi.SPL_HEAL_MAX_PREFIX} bytes, not {len(x)}")
+        rows[b, 0] = len(x)
+        rows[b, 1:] = np.frombuffer(bytes(x) + b"\0" * (_ffi.SPL_HEAL_MAX_PREFIX - len(x)), dtype="<u8")
+    return torch.from_numpy(rows.view(np.int64)).to(torch.device("cuda") if device is None else device)
+
+
+def check_heal_args(ids, lengths=None, state=None, *, begin: bool, n_words=None, max_back: int = 0, min_keep: int = 0,
+                    padding_side: str = "right", keep_free: bool = False, mask=None, state_out=None) -> None:
+    """ValueError for a dtype, rank, shape, layout, size or device that heal_begin_device / heal_step_device would refuse -- before anything
+    goes to the device."""
+    left = _side("padding_side", padding_side)
+    if not isinstance(ids, torch.Tensor) or ids.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"the ids must be a torch tensor of dtype int32 or int64, not {getattr(ids, 'dtype', type(ids))}")
+    if ids.dim() not in ((2,) if begin else (1, 2)):
+        raise ValueError("the prompts must have rank 2 ([batch, length])" if begin else "the ids must have rank 1 ([batch]) or 2 ([batch, steps])")
+    if not ids.is_contiguous():
+        raise ValueError("the ids must be contiguous")
+    B = int(ids.shape[0])
+    if B >= (1 << 31) or (ids.dim() == 2 and ids.shape[1] >= (1 << 32)):
+        raise ValueError("the sequences must be fewer than 2**31 and a row shorter than 2**32")
+    for name, v, top in (("max_back", max_back, _ffi.SPL_HEAL_MAX_BACK), ("min_keep", min_keep, (1 << 32) - 1)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= top:
+            raise ValueError(f"{name} must be an integer in 0 .. {top}, not {v!r}")
+    if n_words is not None and (isinstance(n_words, bool) or not isinstance(n_words, (int, np.integer)) or not 1 <= int(n_words) <= (1 << 26)):
+        raise ValueError(f"n_words must be an integer in 1 .. 2**26, not {n_words!r}")
+    others = []
+    if lengths is not None:
+        others.append(_vec("lengths", lengths, B, (torch.int32,), "int32"))
+    elif left:
+        raise ValueError("padding_side 'left' needs lengths")
+
+    def rows(name, t):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.shape != (B, _ffi.SPL_HEAL_STATE_WORDS) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous int64 tensor of shape [batch, {_ffi.SPL_HEAL_STATE_WORDS}]")
+        others.append((name, t))
+
+    if not begin:
+        rows("state", state)
+    if state_out is not None:
+        rows("state_out", state_out)
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.int32 or mask.dim() != 2 or mask.shape[0] != B or not mask.is_contiguous() or \
+                (n_words is not None and mask.shape[1] != int(n_words)):
+            raise ValueError("mask must be a contiguous int32 tensor of shape [batch, n_words]")
+        others.append(("mask", mask))
+    elif keep_free:
+        raise ValueError("keep_free needs the caller's mask (its free rows filled with ones once)")
+    if not ids.is_cuda:
+        raise ValueError("the ids must be on a GPU (device-side token healing takes no host tensor)")
+    for name, t in others:
+        if t.device != ids.device:
+            raise ValueError(f"{name} must be on the device of the ids")
+
+
+def _heal_call(tok: Tokenizer, begin: bool, ids, lengths, state, flags: int, n_words, max_back: int, min_keep: int, mask, state_out):
+    dev = ids.device
+    B = int(ids.shape[0])
+    K = int(ids.shape[1]) if ids.dim() == 2 else 1
+    n_words = int(mask.shape[1]) if mask is not None else (heal_n_words(tok) if n_words is None else int(n_words))
+    if mask is None:
+        mask = torch.empty((B, n_words), dtype=torch.int32, device=dev)          # (every word of every row is written by the kernels)
+    if state_out is None:
+        state_out = torch.empty((B, _ffi.SPL_HEAL_STATE_WORDS), dtype=torch.int64, device=dev)
+    live = torch.empty(max(B, 1), dtype=torch.uint8, device=dev)[:B]
+    n = torch.empty(2, dtype=torch.int32, device=dev)
+    n_back = torch.empty(max(B, 1), dtype=torch.int32, device=dev)[:B] if begin else None
+    flags |= _ffi.SPL_HEAL_I64 if ids.dtype == torch.int64 else 0
+    # (null state, mask and n_back pointers are refused by the library: an empty batch passes addresses of its own, which nothing dereferences)
+    spare = torch.empty(8, dtype=torch.int64, device=dev).data_ptr() if B == 0 or n_words == 0 else 0
+    si = _ffi.SplHealIn(B, K, _ptr(ids), _ptr(lengths), None if begin else (_ptr(state) or spare))
+    o = _ffi.SplHealOpts(flags, n_words, max_back, min_keep)
+    so = _ffi.SplHealOut(_ptr(state_out) or spare, _ptr(mask) or spare + 16, _ptr(live), n.data_ptr(), (_ptr(n_back) or spare + 32) if begin else None)
+    L = _ffi.lib()
+    fn, name = (L.spl_heal_begin_device, "spl_heal_begin_device") if begin else (L.spl_heal_step_device, "spl_heal_step_device")
+    rc = fn(tok.handle, ctypes.byref(si), ctypes.byref(o), ctypes.byref(so), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        _raise_rc(rc, name)
+    return n_back, state_out, mask, live, n
+
+
+def heal_begin_device(tok: Tokenizer, rows: torch.Tensor, lengths: Optional[torch.Tensor] = None, *, max_back: int = 1, min_keep: int = 0,
+                      auto: bool = True, padding_side: str = "right", n_words: Optional[int] = None, keep_free: bool = False,
+                      mask: Optional[torch.Tensor] = None, state_out: Optional[torch.Tensor] = None):
+    """Token healing, the start (spl_heal_begin_device), on torch's current stream; nothing synchronises.  rows int32 / int64 [B, L]: the
+    prompts, lengths int32 [B] (None: every entry), padding_side as decode_rows_device takes it.  Up to max_back (0 .. 8) tokens are taken
+    off every prompt's end -- while at least min_keep remain, the token is an ordinary one, the bytes taken fit 64, and with auto only
+    while some token extends what has been taken.  Returns (n_back int32 [B], state int64 [B, 9], mask int32 [B, n_words], live uint8 [B],
+    n int32 [2]): feed the model the first lengths - n_back tokens and let it sample where mask has a 1 (bit t & 31 of word t >> 5: id t,
+    the layout of xgrammar's apply_token_bitmask); n = (constrained sequences, 0).  n_words: default heal_n_words(tok), or mask's."""
+    check_heal_args(rows, lengths, begin=True, n_words=n_words, max_back=max_back, min_keep=min_keep, padding_side=padding_side,
+                    keep_free=keep_free, mask=mask, state_out=state_out)
+    flags = (_ffi.SPL_HEAL_AUTO if auto else 0) | (_ffi.SPL_HEAL_PAD_LEFT if padding_side == "left" else 0) | \
+        (_ffi.SPL_HEAL_KEEP_FREE if keep_free else 0)
+    return _heal_call(tok, True, rows, lengths, None, flags, n_words, int(max_back), int(min_keep), mask, state_out)
+
+
+def heal_step_device(tok: Tokenizer, ids: Optional[torch.Tensor], lengths: Optional[torch.Tensor], state: torch.Tensor, *,
+                     n_words: Optional[int] = None, keep_free: bool = False, mask: Optional[torch.Tensor] = None,
+                     state_out: Optional[torch.Tensor] = None):
+    """Token healing, one step (spl_heal_step_device), on torch's current stream; nothing synchronises.  ids [B] or [B, K] int32 / int64:
+    what the sampler drew (a sequence's first lengths[b] entries count, all with lengths None); None: no ids, the masks of the state rows
+    as they are -- the first call after heal_state_from_prefixes.  A covering id heals a sequence, a partial one shortens its prefix,
+    anything else breaks it (it runs free, `broken` set).  Returns (state_out int64 [B, 9], mask int32 [B, n_words], live uint8 [B],
+    n int32 [2]: constrained sequences, sequences that broke in this call).  state_out may be state.  keep_free: rows of sequences that are
+    free after the call are not written -- pass the mask whose free rows hold ones already."""
+    if ids is None:
+        if not isinstance(state, torch.Tensor) or state.dim() != 2:
+            raise ValueError(f"state must be a contiguous int64 tensor of shape [batch, {_ffi.SPL_HEAL_STATE_WORDS}]")
+        ids = torch.empty((state.shape[0], 0), dtype=torch.int32, device=state.device)
+    check_heal_args(ids, lengths, state, begin=False, n_words=n_words, keep_free=keep_free, mask=mask, state_out=state_out)
+    flags = _ffi.SPL_HEAL_KEEP_FREE if keep_free else 0
+    return _heal_call(tok, False, ids, lengths, state, flags, n_words, 0, 0, mask, state_out)[1:]
+
+
+class TokenHealer:
+    """`tokenizer.token_healer(batch_size)`: token healing for a batch whose state lives on the GPU.  begin(rows, lengths) takes the last
+    tokens off the prompts and returns how many; step(ids) follows the sampler; `mask` (int32 [B, n_words], the apply_token_bitmask layout)
+    always holds the ids the next step may draw -- all ones for a sequence that is free.  Nothing here synchronises."""
+
+    def __init__(self, tok: Tokenizer, batch_size: int, n_words: Optional[int] = None, max_back: int = 1, auto: bool = True):
+        if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)) or not 0 <= int(batch_size) < (1 << 31):
+            raise ValueError(f"batch_size must be an integer in 0 .. 2**31 - 1, not {batch_size!r}")
+        self._tok, self.batch_size, self.max_back, self.auto = tok, int(batch_size), max_back, bool(auto)
+        self.n_words = heal_n_words(tok) if n_words is None else int(n_words)
+        dev = torch.device("cuda", tok._device)
+        self.mask = torch.full((self.batch_size, self.n_words), -1, dtype=torch.int32, device=dev)
+        self._state = torch.zeros((self.batch_size, _ffi.SPL_HEAL_STATE_WORDS), dtype=torch.int64, device=dev)
+        self.live = torch.zeros(self.batch_size, dtype=torch.uint8, device=dev)
+        self.n = torch.zeros(2, dtype=torch.int32, device=dev)
+        check_heal_args(torch.empty((self.batch_size, 0), dtype=torch.int32, device=dev), None, self._state, begin=False, n_words=self.n_words,
+                        max_back=max_back)
+        heal_reserve(tok, self.batch_size)
+
+    def begin(self, rows: torch.Tensor, lengths: Optional[torch.Tensor] = None, *, padding_side: str = "right", min_keep: int = 0) -> torch.Tensor:
+        """The prompts [B, L] -> n_back int32 [B] on the device; state, mask and live are this batch's from here on."""
+        n_back, _, _, self.live, self.n = heal_begin_device(self._tok, rows, lengths, max_back=self.max_back, min_keep=min_keep, auto=self.auto,
+                                                            padding_side=padding_side, mask=self.mask, state_out=self._state)
+        return n_back
+
+    def step(self, ids: Optional[torch.Tensor], lengths: Optional[torch.Tensor] = None, *, keep_free: bool = False) -> torch.Tensor:
+        """What the sampler drew, [B] or [B, K] (None: only the masks, after the caller wrote prefixes into `state`) -> the mask.
+        keep_free: the rows of free sequences are not written again -- right once a step WITHOUT it has run after the last sequence
+        left its constraint (its row holds ones since then)."""
+        _, _, self.live, self.n = heal_step_device(self._tok, ids, lengths, self._state, keep_free=keep_free, mask=self.mask, state_out=self._state)
+        return self.mask
+
+    def reset(self, rows=None) -> None:
+        """All sequences (rows None) or the given ones (indices or a bool mask) free and fresh, their mask rows ones."""
+        if rows is None:
+            self._state.zero_(); self.mask.fill_(-1); self.live.zero_()
+        else:
+            self._state[rows] = 0
+            self.mask[rows] = -1
+            self.live[rows] = 0
+
+    def apply(self, logits: torch.Tensor) -> torch.Tensor:
+        """logits [B, V] with -inf wherever the mask forbids the id, IN PLACE (torch ops: a convenience, not a kernel of this library).
+        Columns beyond 32 * n_words are left as they are."""
+        if logits.dim() != 2 or logits.shape[0] != self.batch_size:
+            raise ValueError("logits must have shape [batch, vocabulary]")
+        V = min(int(logits.shape[1]), 32 * self.n_words)
+        bits = ((self.mask.unsqueeze(-1) >> torch.arange(32, device=self.mask.device, dtype=torch.int32)) & 1).reshape(self.batch_size, -1)
+        logits[:, :V].masked_fill_(bits[:, :V] == 0, float("-inf"))
+        return logits
+
+    @property
+    def state(self) -> torch.Tensor:
+        """int64 [B, 9] on the device, as include/splintr_hip.h lays it out (the healer's own tensor: a prefix written here counts)"""
+        return self._state
+
+    @property
+    def pending(self) -> torch.Tensor:
+        """int64 [B] on the device: the bytes of every sequence's pending prefix"""
+        return self._state[:, 0] & 0x7F
+
+    @property
+    def broken(self) -> torch.Tensor:
+        return ((self._state[:, 0] >> 8) & 1).bool()
+
+    @property
+    def healed(self) -> torch.Tensor:
+        return ((self._state[:, 0] >> 9) & 1).bool()
+
+    def __repr__(self) -> str:
+        return f"TokenHealer(batch_size={self.batch_size}, n_words={self.n_words}, max_back={self.max_back}, auto={self.auto})"
+
+
 class Comm:
     """One rank of the library's own RCCL communicator (include/splintr_hip.h: spl_comm_*).  The 128-byte id is
     made by rank 0 and handed to the others by whatever the caller has; `from_torch_group` uses an existing

@@ -596,6 +596,33 @@ class Tokenizer:
         return dv.DeviceStreamingDecoder(self, batch_size, errors=errors, skip_special_tokens=skip_special_tokens, stop=stop,
                                          include_stop_str_in_output=include_stop_str_in_output)
 
+    def token_healer(self, batch_size: int, n_words: Optional[int] = None, max_back: int = 1, auto: bool = True):
+        """Extension: token healing on the GPU (splintr_amd.device.TokenHealer): begin(rows, lengths) takes up to max_back tokens off
+        every prompt's end, step(ids) follows the sampler, and `mask` -- int32 [B, n_words], the apply_token_bitmask layout -- holds the
+        ids whose bytes agree with what was taken, until it is spelled again.  auto: a token is taken only if some token extends it."""
+        from . import device as dv
+        return dv.TokenHealer(self, batch_size, n_words=n_words, max_back=max_back, auto=auto)
+
+    def heal(self, texts_or_ids, *, max_back: int = 1, auto: bool = True, min_keep: int = 0, n_words: Optional[int] = None):
+        """The one-call convenience for a list of prompts (str: encoded here; or lists of ids): -> (the trimmed ids, list[list[int]] --
+        what to feed the model --, the TokenHealer whose mask constrains the first steps).  Synchronises once, for the trimmed lengths."""
+        import torch
+        from . import device as dv
+        prompts = list(texts_or_ids)
+        if prompts and all(isinstance(p, str) for p in prompts):
+            prompts = self.encode_batch(prompts)
+        prompts = [list(p) for p in prompts]
+        healer = dv.TokenHealer(self, len(prompts), n_words=n_words, max_back=max_back, auto=auto)
+        if not prompts:
+            return [], healer
+        L = max(1, max(len(p) for p in prompts))
+        rows = torch.zeros((len(prompts), L), dtype=torch.int64)
+        for i, p in enumerate(prompts):
+            rows[i, :len(p)] = torch.tensor(p, dtype=torch.int64)
+        dev = healer.mask.device
+        n_back = healer.begin(rows.to(dev), torch.tensor([len(p) for p in prompts], dtype=torch.int32, device=dev), min_keep=min_keep)
+        return [p[:len(p) - k] for p, k in zip(prompts, n_back.tolist())], healer
+
     # ------------------------------------------------------------------ cheap surface
     @property
     def vocab_size(self) -> int:
