@@ -248,7 +248,7 @@ __global__ __launch_bounds__(COL_NT) void k_chat_turns(ChatSrc s, ChatGeo g, Cha
             ext = chat_ext(u);
             if (u.bad) status[0] = 1u;
         }
-        const uint64_t x = seq_wave_scan64(ext), st = S + x - ext;
+        const uint64_t x = wave_scan_incl64(ext), st = S + x - ext;
         if (t < n) start[t] = st;
         if (base == 0) e0 = (uint64_t)__shfl((unsigned long long)x, 0);
         const uint32_t l = n - 1 - base < 63 ? n - 1 - base : 63;
@@ -328,6 +328,9 @@ __global__ __launch_bounds__(COL_NT) void k_collate_chat(ChatSrc s, ChatGeo g, v
     const uint32_t n = total - e0 < COL_VEC ? (uint32_t)(total - e0) : COL_VEC;
     uint32_t v[COL_VEC], bits, roles;
     chat_group(s, g, chat_work_tpl(work), chat_work_rec(work), chat_work_start(work, s.n_convs), e0, n, v, bits, roles);
+    // (The rows' tail is this kernel's own, NOT col_store_group: rows and labels share one test of n, and with the rows stored through
+    //  the shared helper the kernel measured 1 .. 2 % slower than before -- profiles/shared_prims_ab.txt.  As written here it compiles
+    //  to the code it had.  The byte arrays go through col_store_bytes.)
     if (n == COL_VEC) {
         col_store4<I64>(rows, e0, v);
         if (labels) chat_store_labels4<I64>(labels, e0, v, bits, g.ignore_id);
@@ -337,10 +340,10 @@ __global__ __launch_bounds__(COL_NT) void k_collate_chat(ChatSrc s, ChatGeo g, v
             if (labels) chat_store_label<I64>(labels, e0 + i, v[i], ((bits >> (8 * i)) & CHAT_LOSS) != 0, g.ignore_id);
         }
     }
-    cpair_store_bytes(mask, e0, n, bits & 0x01010101u);         // (an output that is not wanted: one uniform test each)
-    cpair_store_bytes(loss, e0, n, (bits >> 1) & 0x01010101u);
-    cpair_store_bytes(special, e0, n, (bits >> 2) & 0x01010101u);
-    cpair_store_bytes(role, e0, n, roles);
+    col_store_bytes(mask, e0, n, bits & 0x01010101u);           // (an output that is not wanted: one uniform test each)
+    col_store_bytes(loss, e0, n, (bits >> 1) & 0x01010101u);
+    col_store_bytes(special, e0, n, (bits >> 2) & 0x01010101u);
+    col_store_bytes(role, e0, n, roles);
 }
 #endif  // __HIPCC__
 

@@ -106,6 +106,31 @@ SPL_HD uint32_t col_span_hi_bound(uint32_t d_lo, uint64_t n_docs, uint32_t k) {
     return (uint32_t)((k && far < last) ? far : last);
 }
 SPL_HD bool col_use_window(uint32_t d_lo, uint32_t d_hi) { return d_hi - d_lo < COL_WIN; }
+// One search: lo becomes the LARGEST d of [lo, hi] with start_d <= p; returns its rounds.  count(pred) = how many of the workgroup's
+// COL_NT lanes hold pred(lane): one barrier in a kernel (WgCount of spl_k_merge.h), a loop over the lanes in a host simulation.
+template <class Count>
+SPL_HD uint32_t col_kary_search(const uint64_t* starts, uint32_t k, uint32_t& lo, uint32_t hi, uint64_t p, const Count& count) {
+    uint32_t rounds = 0;
+    for (; lo < hi; rounds++) {
+        const uint32_t step = col_kary_step(lo, hi);
+        const uint32_t cnt = count([&](uint32_t lane) { return col_kary_pred(starts, k, lo, hi, step, lane, p); });
+        col_kary_narrow(lo, hi, step, cnt);
+    }
+    return rounds;
+}
+// The documents d_lo, d_hi of a span's first and last position (p_first <= p_last, both in a document): the search over all documents
+// for the first, then from d_lo up to col_span_hi_bound for the last.  start_d = starts[d] + d * k; k_bound is the k of the bound
+// (pack mode: k; windows search row_off with k = 0, and every document has a row of its own: 1).  Uniform over the workgroup: every
+// lane takes part in every round.  Returns the most rounds one of the two searches took (the simulations report it, a kernel drops it).
+template <class Count>
+SPL_HD uint32_t col_span_docs(const uint64_t* starts, uint32_t k, uint32_t k_bound, uint64_t n_docs, uint64_t p_first, uint64_t p_last,
+                              uint32_t& d_lo, uint32_t& d_hi, const Count& count) {
+    d_lo = 0;
+    const uint32_t r_lo = col_kary_search(starts, k, d_lo, (uint32_t)(n_docs - 1), p_first, count);
+    d_hi = d_lo;
+    const uint32_t r_hi = col_kary_search(starts, k, d_hi, col_span_hi_bound(d_lo, n_docs, k_bound), p_last, count);
+    return r_lo > r_hi ? r_lo : r_hi;
+}
 
 // A lane's search, from the document d_prev of its previous element (of the span's first position for its first element) on: the
 // LARGEST d of [d_prev, d_hi] with start_d <= p.  Nearly always the next start lies beyond p and one read settles it.
@@ -186,6 +211,37 @@ template <bool I64> __device__ __forceinline__ void col_store1(void* rows, uint6
     if (I64) static_cast<uint64_t*>(rows)[e] = (uint64_t)v;
     else static_cast<uint32_t*>(rows)[e] = v;
 }
+// What the gather kernels of this family (here, spl_k_window.h, spl_k_pair.h, spl_k_chat.h, spl_k_seqpack.h) store of one lane's group
+// of n (0..COL_VEC) flat elements from e0 on: all four in one wide store, or -- the final partial group of an output -- one by one, so
+// that nothing is written past the output's end.  The partial paths index the group's registers with constants (a lane's own index
+// would put the group into scratch memory: sqp_store_labels, spl_k_seqpack.h).  The rows (k_collate_chat and k_seqpack_gather keep a
+// rows tail of their own and say why; their byte and int32 arrays go through the two functions below):
+template <bool I64> __device__ __forceinline__ void col_store_group(void* rows, uint64_t e0, uint32_t n, const uint32_t v[COL_VEC]) {
+    if (n == COL_VEC) { col_store4<I64>(rows, e0, v); return; }
+#pragma unroll
+    for (uint32_t i = 0; i < COL_VEC; i++) if (i < n) col_store1<I64>(rows, e0 + i, v[i]);
+}
+// a byte array (null: not wanted), byte i of `bytes` for element i
+__device__ __forceinline__ void col_store_bytes(uint8_t* out, uint64_t e0, uint32_t n, uint32_t bytes) {
+    if (!out) return;
+    if (n == COL_VEC) { *reinterpret_cast<uint32_t*>(out + e0) = bytes; return; }
+    for (uint32_t i = 0; i < n; i++) out[e0 + i] = (uint8_t)(bytes >> (8 * i));
+}
+// an int32 array (null: not wanted)
+__device__ __forceinline__ void col_store_i32(int32_t* out, uint64_t e0, uint32_t n, const int32_t x[COL_VEC]) {
+    if (!out) return;
+    if (n == COL_VEC) { *reinterpret_cast<int4*>(out + e0) = make_int4(x[0], x[1], x[2], x[3]); return; }
+#pragma unroll
+    for (uint32_t i = 0; i < COL_VEC; i++) if (i < n) out[e0 + i] = x[i];
+}
+
+// The starts of documents d_lo .. d_hi (at most COL_WIN of them) into the LDS window, readable by every lane on return; their number.
+__device__ __forceinline__ uint32_t col_fill_window(uint64_t* s_win, const uint64_t* starts, uint32_t k, uint32_t d_lo, uint32_t d_hi) {
+    const uint32_t n_win = d_hi - d_lo + 1;
+    for (uint32_t i = threadIdx.x; i < n_win; i += COL_NT) s_win[i] = col_doc_start(starts, (uint64_t)d_lo + i, k);
+    __syncthreads();
+    return n_win;
+}
 
 // grid: one workgroup per span of COL_SPAN flat elements (beyond 2^31 - 1 spans a workgroup takes several)
 template <bool I64>
@@ -199,20 +255,14 @@ __global__ __launch_bounds__(COL_NT) void k_collate_pad(const uint32_t* __restri
         const uint32_t n = total - e0 < COL_VEC ? (uint32_t)(total - e0) : COL_VEC;
         uint32_t v[COL_VEC], m;
         col_pad_group(ids, off, e0, n, o, v, m, len);
-        if (n == COL_VEC) {
-            col_store4<I64>(rows, e0, v);
-            if (mask) *reinterpret_cast<uint32_t*>(mask + e0) = m;
-        } else {                                        // the final partial group: nothing is written past n_docs * L
-            for (uint32_t i = 0; i < n; i++) {
-                col_store1<I64>(rows, e0 + i, v[i]);
-                if (mask) mask[e0 + i] = (uint8_t)((m >> (8 * i)) & 1u);
-            }
-        }
+        col_store_group<I64>(rows, e0, n, v);           // (the final group may be partial: nothing is written past n_docs * L)
+        col_store_bytes(mask, e0, n, m);                // (col_pad_group sets a mask byte to 0 or 1: stored as it is)
     }
 }
 
-// (tests/hostsim/collate_sim.cpp shares the mapping functions above, NOT this kernel's driver: the span loop, p_last, the two searches'
-//  bounds and the window fill are restated there, so a change to them here is checked by tests/test_gpu_collate.py alone.)
+// (tests/hostsim/collate_sim.cpp runs the mapping functions above and col_span_docs -- both searches and the bound between them -- with
+//  a count over its own lanes.  What it still restates of this kernel: the span loop with p_last, the choice between window and global
+//  search, and the window fill; a change to those here is checked by tests/test_gpu_collate.py alone.)
 // total = rows_cap * L: every element below it is written (beyond the stream: pad_id, doc -1, pos 0), nothing at or beyond it.
 // n_out[0] = the rows the stream needs, n_out[1] = its length -- always.
 template <bool I64>
@@ -235,23 +285,10 @@ __global__ __launch_bounds__(COL_NT) void k_collate_pack(const uint32_t* __restr
         if (in_stream) {
             // the documents of the span's first and last stream position: uniform, every lane takes part in every round
             const uint64_t p_last = (s_end < S ? s_end : S) - 1;
-            uint32_t d_lo = 0, hi = (uint32_t)(n_docs - 1);
-            while (d_lo < hi) {
-                const uint32_t step = col_kary_step(d_lo, hi);
-                const uint32_t cnt = (uint32_t)__syncthreads_count(col_kary_pred(off, k, d_lo, hi, step, threadIdx.x, s0));
-                col_kary_narrow(d_lo, hi, step, cnt);
-            }
-            uint32_t d_hi = d_lo;
-            hi = col_span_hi_bound(d_lo, n_docs, k);
-            while (d_hi < hi) {
-                const uint32_t step = col_kary_step(d_hi, hi);
-                const uint32_t cnt = (uint32_t)__syncthreads_count(col_kary_pred(off, k, d_hi, hi, step, threadIdx.x, p_last));
-                col_kary_narrow(d_hi, hi, step, cnt);
-            }
+            uint32_t d_lo, d_hi;
+            col_span_docs(off, k, k, n_docs, s0, p_last, d_lo, d_hi, WgCount{});
             if (col_use_window(d_lo, d_hi)) {
-                const uint32_t n_win = d_hi - d_lo + 1;
-                for (uint32_t i = threadIdx.x; i < n_win; i += COL_NT) s_win[i] = col_doc_start(off, (uint64_t)d_lo + i, k);
-                __syncthreads();
+                const uint32_t n_win = col_fill_window(s_win, off, k, d_lo, d_hi);
                 if (n) col_pack_group(ids, off, S, e0, n, d_lo, o, ColLocWin{s_win, n_win, d_lo}, v, doc, pos);
                 __syncthreads();                        // (the next span of this workgroup fills the window again)
             } else if (n) {
@@ -260,17 +297,9 @@ __global__ __launch_bounds__(COL_NT) void k_collate_pack(const uint32_t* __restr
         } else {
             for (uint32_t i = 0; i < COL_VEC; i++) { v[i] = o.pad_id; doc[i] = -1; pos[i] = 0; }
         }
-        if (n == COL_VEC) {
-            col_store4<I64>(rows, e0, v);
-            if (doc_out) *reinterpret_cast<int4*>(doc_out + e0) = make_int4(doc[0], doc[1], doc[2], doc[3]);
-            if (pos_out) *reinterpret_cast<uint4*>(pos_out + e0) = make_uint4(pos[0], pos[1], pos[2], pos[3]);
-        } else {                                        // the final partial group: nothing is written past rows_cap * L
-            for (uint32_t i = 0; i < n; i++) {
-                col_store1<I64>(rows, e0 + i, v[i]);
-                if (doc_out) doc_out[e0 + i] = doc[i];
-                if (pos_out) pos_out[e0 + i] = (int32_t)pos[i];
-            }
-        }
+        col_store_group<I64>(rows, e0, n, v);           // (the final group may be partial: nothing is written past rows_cap * L)
+        col_store_i32(doc_out, e0, n, doc);
+        col_store_i32(pos_out, e0, n, reinterpret_cast<const int32_t*>(pos));       // (position ids are stored as int32)
     }
 }
 #endif  // __HIPCC__

@@ -61,9 +61,7 @@ __global__ __launch_bounds__(1024) void k_decode_scan(uint64_t* blk, uint64_t n_
     for (uint64_t base = 0; base < n_blk; base += 1024) {
         const uint64_t i = base + tid;
         const uint64_t v = i < n_blk ? blk[i] : 0ull;
-        uint64_t x = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const uint64_t y = __shfl_up(x, d); if ((tid & 63) >= d) x += y; }
+        const uint64_t x = wave_scan_incl64(v);
         if ((tid & 63) == 63) s_w[tid >> 6] = x;
         __syncthreads();
         uint64_t pre = s_carry;

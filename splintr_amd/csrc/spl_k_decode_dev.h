@@ -191,6 +191,21 @@ SPL_HD uint64_t dd_first_doc_rows(const DecIn& a, uint64_t base) {
     const uint64_t d = (base + a.row_len - 1) / a.row_len;
     return d <= a.n_docs ? d : a.n_docs + 1;
 }
+// Either mode: the first document of the block whose slots begin at base.  lanes: the workgroup's size (DD_NT in the kernels; the host
+// simulations run several); count(pred) = how many of those lanes hold pred(lane): one barrier in a kernel (WgCount of
+// spl_k_merge.h), a loop over the lanes in a simulation, which also counts its calls -- the rounds.  Uniform: every lane of the
+// workgroup calls it.
+template <class Count>
+SPL_HD uint64_t dd_first_doc(const DecIn& a, uint64_t base, uint32_t lanes, const Count& count) {
+    if (a.row_len) return dd_first_doc_rows(a, base);
+    uint64_t lo = 0, hi = a.n_docs + 1;
+    while (lo < hi) {
+        const uint64_t step = dd_kary_step(lo, hi, lanes);
+        const uint32_t cnt = count([&](uint32_t lane) { return dd_kary_pred(a, lo, hi, step, lane, base); });
+        dd_kary_narrow(lo, hi, step, cnt);
+    }
+    return lo;
+}
 
 #if defined(__HIPCC__)
 // ------------------------------------------------------------------------------------------ the kernels
@@ -224,8 +239,9 @@ __device__ __forceinline__ void dd_store_group(uint8_t* p, const uint32_t w[DD_W
 }
 
 // blk: the exclusive scan of k_dec_len's sums.  out (16-byte aligned) receives the bytes below cap, out_off all n_docs + 1 offsets.
-// (tests/hostsim/decode_sim.cpp shares the mapping functions above, NOT this kernel's driver: the in-block scan, the group loop and the
-//  two document loops are restated there, so a change to them here is checked by tests/test_gpu_decode_device.py alone.)
+// (tests/hostsim/decode_sim.cpp runs the mapping functions above and dd_first_doc with a count over its own lanes.  What it still
+//  restates of this kernel: the in-block scan, the group loop and the document loop; a change to those here is checked by
+//  tests/test_gpu_decode_device.py alone.)
 template <bool I64>
 __global__ __launch_bounds__(DD_NT) void k_dec_gather(DecIn a, DecTab t, uint64_t n_blk, const uint64_t* __restrict__ blk,
                                                       uint8_t* __restrict__ out, uint64_t cap, uint64_t* __restrict__ out_off) {
@@ -264,18 +280,7 @@ __global__ __launch_bounds__(DD_NT) void k_dec_gather(DecIn a, DecTab t, uint64_
             }
         }
         // the documents whose clamped start lies in this block's slots (the end, "document" n_docs, among them)
-        uint64_t first;
-        if (a.row_len) {
-            first = dd_first_doc_rows(a, base);
-        } else {
-            uint64_t lo = 0, hi = a.n_docs + 1;
-            while (lo < hi) {
-                const uint64_t step = dd_kary_step(lo, hi, DD_NT);
-                const uint32_t cnt = (uint32_t)__syncthreads_count(dd_kary_pred(a, lo, hi, step, tid, base));
-                dd_kary_narrow(lo, hi, step, cnt);
-            }
-            first = lo;
-        }
+        const uint64_t first = dd_first_doc(a, base, DD_NT, WgCount{});
         for (uint64_t d = first + tid; d <= a.n_docs; d += DD_NT) {
             const uint64_t s = dd_doc_start(a, d);
             if (!dd_owns(s, base, DD_BLK)) break;         // (the starts are non-decreasing)

@@ -145,8 +145,24 @@ __device__ __forceinline__ uint32_t wave_scan_incl(uint32_t x) {
     x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);   // row_bcast:31 -> rows 2, 3
     return x;
 }
+// The same over 64-bit values, by shuffles (DPP moves 32 bits): the scans of row, byte and token counts that may exceed 2^32 -- the
+// collators' and decoders' scan kernels, never the tile kernel.
+__device__ __forceinline__ uint64_t wave_scan_incl64(uint64_t x) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const uint64_t y = (uint64_t)__shfl_up((unsigned long long)x, d); if ((int)(threadIdx.x & 63) >= d) x += y; }
+    return x;
+}
 
-// The same for the running maximum (values are non-negative: shifted-in zeros are neutral).
+// How many of the WORKGROUP's lanes hold pred(their own number): the count the cooperative searches of the gather and block kernels take
+// as a parameter (col_span_docs of spl_k_collate.h, dd_first_doc of spl_k_decode_dev.h; a host simulation passes a loop over the lanes).
+// One barrier; every lane of the workgroup calls it.
+struct WgCount {
+    template <class Pred> __device__ __forceinline__ uint32_t operator()(const Pred& pred) const {
+        return (uint32_t)__syncthreads_count(pred(threadIdx.x));
+    }
+};
+
+// wave_scan_incl for the running maximum (values are non-negative: shifted-in zeros are neutral).
 __device__ __forceinline__ uint32_t wave_scan_max(uint32_t x) {
     auto mx = [](uint32_t a, int b) { return a > (uint32_t)b ? a : (uint32_t)b; };
     x = mx(x, __builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, true));

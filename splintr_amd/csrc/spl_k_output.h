@@ -38,9 +38,7 @@ __global__ __launch_bounds__(256) void k_group_scan(const uint32_t* gs, uint32_t
     const uint32_t per = (n + 255u) / 256u, lo = (uint32_t)tid * per, hi = lo + per < n ? lo + per : n;
     unsigned long long sum = 0;
     for (uint32_t k = lo; k < hi; k++) sum += gs[k];
-    unsigned long long incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const unsigned long long v = __shfl_up(incl, d); if (lane >= d) incl += v; }
+    const unsigned long long incl = wave_scan_incl64(sum);
     if (lane == 63) s_w[wv] = incl;
     __syncthreads();
     unsigned long long run = incl - sum;

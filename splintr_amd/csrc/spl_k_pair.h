@@ -6,9 +6,10 @@
 //
 // The kernel of spl_k_collate.h's family: a pure gather, every output element written once by the lane that owns it -- no atomics, no
 // LDS, no workspace, no second pass.  A lane owns COL_VEC consecutive flat elements (one 16-byte store of int32, two of int64, one
-// 4-byte store per byte array), a workgroup COL_SPAN of them; L need not be a multiple of COL_VEC: the elements of a lane's group are
-// resolved one by one, and where the group crosses a row boundary the next pair is resolved again.  A side's document is named by an
-// index array (or the pair's own number): a query that exists once in HBM is read by every pair that names it.
+// 4-byte store per byte array: col_store_group and col_store_bytes of spl_k_collate.h), a workgroup COL_SPAN of them; L need not be
+// a multiple of COL_VEC: the elements of a lane's group are resolved one by one, and where the group crosses a row boundary the next
+// pair is resolved again.  A side's document is named by an index array (or the pair's own number): a query that exists once in HBM
+// is read by every pair that names it.
 //
 // The mapping from an output element to its source is the plain C++ of the first half of this file (values and pointers only; the one
 // HIP builtin, CPAIR_UNIFORM, is the identity in a host build): tests/hostsim/pair_sim.cpp includes it in a g++ build and evaluates it
@@ -187,13 +188,6 @@ SPL_HD void cpair_group(const PairSrc& s, uint64_t e0, uint32_t n, const PairGeo
 
 #if defined(__HIPCC__)
 // ------------------------------------------------------------------------------------------ the kernel
-// a group's four bytes of one byte array (null: not wanted): one 4-byte store, or for the final partial group n single bytes
-__device__ __forceinline__ void cpair_store_bytes(uint8_t* out, uint64_t e0, uint32_t n, uint32_t bytes) {
-    if (!out) return;
-    if (n == COL_VEC) { *reinterpret_cast<uint32_t*>(out + e0) = bytes; return; }
-    for (uint32_t i = 0; i < n; i++) out[e0 + i] = (uint8_t)(bytes >> (8 * i));
-}
-
 // grid: cpair_grid(n_pairs * L) -- one workgroup per span of COL_SPAN flat elements
 template <bool I64>
 __global__ __launch_bounds__(COL_NT) void k_collate_pair(PairSrc s, uint32_t n_pairs, PairOpts o, void* __restrict__ rows,
@@ -205,14 +199,10 @@ __global__ __launch_bounds__(COL_NT) void k_collate_pair(PairSrc s, uint32_t n_p
     const uint32_t n = total - e0 < COL_VEC ? (uint32_t)(total - e0) : COL_VEC;
     uint32_t v[COL_VEC], m, ty, sp;
     cpair_group(s, e0, n, o.g, o.fixed, v, m, ty, sp, len, kept, status);
-    if (n == COL_VEC) {
-        col_store4<I64>(rows, e0, v);
-    } else {                                            // the final partial group: nothing is written past n_pairs * L
-        for (uint32_t i = 0; i < n; i++) col_store1<I64>(rows, e0 + i, v[i]);
-    }
-    cpair_store_bytes(mask, e0, n, m);                  // (an output that is not wanted: one uniform test each)
-    cpair_store_bytes(type, e0, n, ty);
-    cpair_store_bytes(special, e0, n, sp);
+    col_store_group<I64>(rows, e0, n, v);               // (the final group may be partial: nothing is written past n_pairs * L)
+    col_store_bytes(mask, e0, n, m);                    // (an output that is not wanted: one uniform test each)
+    col_store_bytes(type, e0, n, ty);
+    col_store_bytes(special, e0, n, sp);
 }
 #endif  // __HIPCC__
 

@@ -268,11 +268,11 @@ SPL_HD void sqp_group(const SqpIn& in, const SqpGeo& g, const SqpWork& w, uint32
 // the inclusive scan of v over the workgroup's SQP_NT lanes and its total; s_ws: SQP_NT / 64 + 1 words
 __device__ __forceinline__ uint64_t sqp_scan(uint64_t v, uint64_t* s_ws, uint64_t& total) {
     const uint32_t wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const uint64_t x = seq_wave_scan64(v);
+    const uint64_t x = wave_scan_incl64(v);
     if (lane == 63) s_ws[wv] = x;
     __syncthreads();
     if (wv == 0) {
-        const uint64_t y = lane < SQP_NT / 64 ? s_ws[lane] : 0ull, ys = seq_wave_scan64(y);
+        const uint64_t y = lane < SQP_NT / 64 ? s_ws[lane] : 0ull, ys = wave_scan_incl64(y);
         if (lane < SQP_NT / 64) s_ws[lane] = ys - y;
         if (lane == SQP_NT / 64 - 1) s_ws[SQP_NT / 64] = ys;
     }
@@ -474,12 +474,6 @@ template <bool I64> __device__ __forceinline__ void sqp_store_labels(void* label
         }
     }
 }
-__device__ __forceinline__ void sqp_store_i32(int32_t* out, uint64_t e, uint32_t n, const int32_t x[COL_VEC]) {
-    if (!out) return;
-    if (n == COL_VEC) { *reinterpret_cast<int4*>(out + e) = make_int4(x[0], x[1], x[2], x[3]); return; }
-#pragma unroll
-    for (uint32_t i = 0; i < COL_VEC; i++) if (i < n) out[e + i] = x[i];
-}
 
 // grid: cpair_grid(R * L) -- one workgroup per span of COL_SPAN flat elements; every element of the [R, L] outputs is written
 template <bool I64>
@@ -491,22 +485,24 @@ __global__ __launch_bounds__(COL_NT) void k_seqpack_gather(SqpIn in, SqpGeo g, v
     const SqpWork w = sqp_work(work, in.n, g.R);
     SqpGroup q;
     sqp_group(in, g, w, (uint32_t)w.hdr[4], e0, n, q);
+    // (The rows' tail and the copy of pos are this kernel's own, NOT col_store_group and a cast: through those the int64 gather measured
+    //  1 .. 3 % slower than before -- profiles/shared_prims_ab.txt -- and as written here the kernel compiles to the code it had.)
     if (n == COL_VEC) col_store4<I64>(o.rows, e0, q.v);
     else {                                              // the final partial group: nothing is written past R * L
 #pragma unroll
         for (uint32_t i = 0; i < COL_VEC; i++) if (i < n) col_store1<I64>(o.rows, e0 + i, q.v[i]);
     }
     if (o.labels) sqp_store_labels<I64>(o.labels, e0, n, q.lab, g.ignore_id);
-    cpair_store_bytes(o.b0, e0, n, q.by[0]);
-    cpair_store_bytes(o.b1, e0, n, q.by[1]);
-    cpair_store_bytes(o.b2, e0, n, q.by[2]);
-    cpair_store_bytes(o.b3, e0, n, q.by[3]);
-    cpair_store_bytes(o.mask, e0, n, q.mask);
+    col_store_bytes(o.b0, e0, n, q.by[0]);
+    col_store_bytes(o.b1, e0, n, q.by[1]);
+    col_store_bytes(o.b2, e0, n, q.by[2]);
+    col_store_bytes(o.b3, e0, n, q.by[3]);
+    col_store_bytes(o.mask, e0, n, q.mask);
     int32_t pos[COL_VEC];
 #pragma unroll
     for (uint32_t i = 0; i < COL_VEC; i++) pos[i] = (int32_t)q.pos[i];
-    sqp_store_i32(o.pos, e0, n, pos);
-    sqp_store_i32(o.sid, e0, n, q.sid);
+    col_store_i32(o.pos, e0, n, pos);
+    col_store_i32(o.sid, e0, n, q.sid);
 }
 #endif  // __HIPCC__
 

@@ -9,7 +9,8 @@
 // An op has Wave (a wavefront's LDS), Carry (what a sequence's count hands its write), count(b, Wave&, Carry&) -> the bytes sequence b emits,
 // and write(b, Wave&, const Carry&, o0); every lane of the wavefront calls them.  A keep is where the carries wait between the passes:
 // put(b, carry) by lane 0, get(b) by every lane (LDS in the one-launch form, the scratch in the three-launch form; the op chooses the widths).
-// The first half is plain C++: tests/hostsim/seqscan_sim.h restates the two drivers over it for the ops' simulators.
+// The first half is plain C++: tests/hostsim/seqscan_sim.h restates the two drivers over it for the ops' simulators.  The device half
+// scans with wave_scan_incl64 (spl_k_merge.h, in front of this file in the kernels' translation unit).
 #pragma once
 #include "spl_common.h"
 
@@ -23,8 +24,6 @@ static_assert(SEQ_BLK <= 64, "one wave scan gives a block's starts");
 
 // blocks of the three-launch form: block 0 exists even for no sequence (it writes the closing offset)
 SPL_HD uint64_t seq_n_blocks(uint64_t n_seqs) { const uint64_t n = (n_seqs + SEQ_BLK - 1) / SEQ_BLK; return n ? n : 1; }
-constexpr uint32_t ST_SEQ_BLK = SEQ_BLK;            // (the two names the geometry had in spl_k_stream.h: simulators written against them still build)
-SPL_HD uint64_t st_n_blocks(uint64_t n_seqs) { return seq_n_blocks(n_seqs); }
 // an output byte: need may exceed the capacity, and what lies beyond it is counted, not written
 SPL_HD void seq_put(uint8_t* __restrict__ out, uint64_t cap, uint64_t o, uint32_t x) { if (o < cap) out[o] = (uint8_t)x; }
 
@@ -34,12 +33,6 @@ struct SeqNoKeep {
     __device__ __forceinline__ void put(uint64_t, const SeqNoCarry&) const {}
     __device__ __forceinline__ SeqNoCarry get(uint64_t) const { return {}; }
 };
-__device__ __forceinline__ uint64_t seq_wave_scan64(uint64_t v) {
-    uint64_t x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint64_t y = (uint64_t)__shfl_up((unsigned long long)x, d); if ((int)(threadIdx.x & 63) >= d) x += y; }
-    return x;
-}
 
 // ------------------------------------------------------------------------------------------ three launches
 // cnt[b]: the bytes sequence b emits; blk[g]: their sum over block g's SEQ_BLK sequences (k_decode_scan scans those).  s_sum: SEQ_NT / 64 words
@@ -76,7 +69,7 @@ __device__ __forceinline__ void seq_write_body(const Op& op, const Keep& keep, u
     for (uint64_t g = blockIdx.x; g < n_blk; g += gridDim.x) {
         const uint64_t b_lane = g * SEQ_BLK + lane;
         const uint64_t mine = lane < SEQ_BLK && b_lane < n_seqs ? cnt[b_lane] : 0ull;
-        const uint64_t excl = seq_wave_scan64(mine) - mine + blk[g];
+        const uint64_t excl = wave_scan_incl64(mine) - mine + blk[g];
         for (uint32_t i = wv; i < SEQ_BLK; i += SEQ_NT / 64) {
             const uint64_t b = g * SEQ_BLK + i;
             if (b >= n_seqs) break;
@@ -103,7 +96,7 @@ __device__ __forceinline__ void seq_one_body(const Op& op, const Keep& keep, uin
         uint64_t carry = 0;
         for (uint32_t base = 0; base < n; base += 64) {
             const uint64_t v = base + lane < n ? s_cnt[base + lane] : 0ull;
-            const uint64_t x = seq_wave_scan64(v);
+            const uint64_t x = wave_scan_incl64(v);
             if (base + lane < n) s_cnt[base + lane] = carry + x - v;
             carry += (uint64_t)__shfl((unsigned long long)x, 63);
         }

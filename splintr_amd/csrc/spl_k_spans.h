@@ -80,7 +80,7 @@ SPL_HD void sn_lane(const DecIn& a, const DecTab& t, const SpanTab& s, uint64_t 
 }
 
 // ------------------------------------------------------------------------------------------ the carry-in
-// `first` is the first document whose clamped start is >= base (dd_kary_* / dd_first_doc_rows).  Slots of the block below that start
+// `first` is the first document whose clamped start is >= base (dd_first_doc).  Slots of the block below that start
 // belong to document first - 1, which starts BEFORE the block: true where there are such slots.
 SPL_HD bool sn_has_carry(const DecIn& a, uint64_t first, uint64_t base) {
     return first >= 1 && first <= a.n_docs && dd_doc_start(a, first) > base;
@@ -169,8 +169,9 @@ __device__ __forceinline__ void sn_store(void* out, uint64_t i0, uint32_t n, con
 }
 
 // blk_b / blk_c: the exclusive scans of k_span_len's sums.  Every span entry below dd_slots(a) and every offset is written.
-// (tests/hostsim/spans_sim.cpp shares the mapping functions above, NOT this kernel's driver: the in-block scans, the running maximum
-//  ACROSS lanes, the carry-in's reduction and the document loop are restated there, so a change to them here is checked by tests/test_gpu_spans.py alone.)
+// (tests/hostsim/spans_sim.cpp runs the mapping functions above and dd_first_doc with a count over its own lanes.  What it still restates
+//  of this kernel: the in-block scans, the running maximum ACROSS lanes, the carry-in's reduction and the document loop; a change to
+//  those here is checked by tests/test_gpu_spans.py alone.)
 template <bool I64, bool S64>
 __global__ __launch_bounds__(DD_NT) void k_span_write(DecIn a, DecTab t, SpanTab s, uint64_t n_blk, const uint64_t* __restrict__ blk_b,
                                                       const uint64_t* __restrict__ blk_c, SpanOut o) {
@@ -210,18 +211,7 @@ __global__ __launch_bounds__(DD_NT) void k_span_write(DecIn a, DecTab t, SpanTab
         __syncthreads();
         const uint64_t B0 = blk_b[b], C0 = blk_c[b];
         // the documents whose clamped start lies in this block's slots (the end, "document" n_docs, among them): offsets and marks
-        uint64_t first;
-        if (a.row_len) {
-            first = dd_first_doc_rows(a, base);
-        } else {
-            uint64_t lo = 0, hi = a.n_docs + 1;
-            while (lo < hi) {
-                const uint64_t step = dd_kary_step(lo, hi, DD_NT);
-                const uint32_t cnt = (uint32_t)__syncthreads_count(dd_kary_pred(a, lo, hi, step, tid, base));
-                dd_kary_narrow(lo, hi, step, cnt);
-            }
-            first = lo;
-        }
+        const uint64_t first = dd_first_doc(a, base, DD_NT, WgCount{});
         for (uint64_t d = first + tid; d <= a.n_docs; d += DD_NT) {
             const uint64_t st = dd_doc_start(a, d);
             if (!dd_owns(st, base, DD_BLK)) break;        // (the starts are non-decreasing)

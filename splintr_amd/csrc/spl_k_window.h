@@ -123,11 +123,7 @@ SPL_HD void win_group(const uint32_t* ids, const uint64_t* off, uint64_t R, uint
 // wavefronts' totals through LDS.  total: the sum over the workgroup.  Every lane calls it; s_wave is free again on return.
 __device__ __forceinline__ uint64_t win_block_scan(uint64_t x, uint64_t* s_wave, uint64_t& total) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (uint32_t dlt = 1; dlt < 64; dlt <<= 1) {
-        const uint64_t y = __shfl_up((unsigned long long)x, dlt, 64);
-        if (lane >= dlt) x += y;
-    }
+    x = wave_scan_incl64(x);
     if (lane == 63) s_wave[wave] = x;
     __syncthreads();
     uint64_t base = 0, sum = 0;
@@ -185,8 +181,9 @@ __global__ __launch_bounds__(COL_NT) void k_window_add(uint64_t n_docs, uint64_t
     }
 }
 
-// (tests/hostsim/window_sim.cpp shares the mapping functions, NOT this kernel's driver: the span loop, the searches' bounds and the window
-//  fill are restated there, so a change to them here is checked by tests/test_gpu_window.py alone.)
+// (tests/hostsim/window_sim.cpp runs the mapping functions and col_span_docs -- both searches and the bound between them -- with a count
+//  over its own lanes.  What it still restates of this kernel: the span loop with r_first and r_last, and the window fill; a change to
+//  those here is checked by tests/test_gpu_window.py alone.)
 // total = rows_cap * L: every element below it is written, nothing at or beyond it; the per-row outputs likewise below rows_cap.
 template <bool I64>
 __global__ __launch_bounds__(COL_NT) void k_window_gather(const uint32_t* __restrict__ ids, const uint64_t* __restrict__ off,
@@ -209,35 +206,16 @@ __global__ __launch_bounds__(COL_NT) void k_window_gather(const uint32_t* __rest
         if (r_first < R) {                              // (uniform over the workgroup: every lane takes part in every round)
             col_rowcol(s_end - 1, o.L, r_last, c);
             if (r_last >= R) r_last = R - 1;
-            // the documents of the span's first and last row, over row_off (k = 0: a document's start is row_off[d] itself)
-            uint32_t hi = (uint32_t)(n_docs - 1);
-            while (d_lo < hi) {
-                const uint32_t step = col_kary_step(d_lo, hi);
-                const uint32_t cnt = (uint32_t)__syncthreads_count(col_kary_pred(row_off, 0u, d_lo, hi, step, threadIdx.x, r_first));
-                col_kary_narrow(d_lo, hi, step, cnt);
-            }
-            uint32_t d_hi = d_lo;
-            hi = col_span_hi_bound(d_lo, n_docs, 1u);   // (every document takes a row of its own: at most COL_SPAN of them in the span)
-            while (d_hi < hi) {
-                const uint32_t step = col_kary_step(d_hi, hi);
-                const uint32_t cnt = (uint32_t)__syncthreads_count(col_kary_pred(row_off, 0u, d_hi, hi, step, threadIdx.x, r_last));
-                col_kary_narrow(d_hi, hi, step, cnt);
-            }
-            n_win = d_hi - d_lo + 1;                    // <= COL_WIN, by the bound above
-            for (uint32_t i = threadIdx.x; i < n_win; i += COL_NT) s_win[i] = row_off[(uint64_t)d_lo + i];
-            __syncthreads();
+            // the documents of the span's first and last row, over row_off (k = 0: a document's start is row_off[d] itself; the bound's
+            // k = 1: every document takes a row of its own, so the span holds at most COL_SPAN of them and n_win <= COL_WIN)
+            uint32_t d_hi;
+            col_span_docs(row_off, 0u, 1u, n_docs, r_first, r_last, d_lo, d_hi, WgCount{});
+            n_win = col_fill_window(s_win, row_off, 0u, d_lo, d_hi);
         }
         if (n) win_group(ids, off, R, e0, n, d_lo, o, g, ColLocWin{s_win, n_win, d_lo}, v, m, len, row_doc, row_start);
         if (r_first < R) __syncthreads();               // (the next span of this workgroup fills the window again)
-        if (n == COL_VEC) {
-            col_store4<I64>(rows, e0, v);
-            if (mask) *reinterpret_cast<uint32_t*>(mask + e0) = m;
-        } else {                                        // the final partial group: nothing is written past rows_cap * L
-            for (uint32_t i = 0; i < n; i++) {
-                col_store1<I64>(rows, e0 + i, v[i]);
-                if (mask) mask[e0 + i] = (uint8_t)((m >> (8 * i)) & 1u);
-            }
-        }
+        col_store_group<I64>(rows, e0, n, v);           // (the final group may be partial: nothing is written past rows_cap * L)
+        col_store_bytes(mask, e0, n, m);                // (win_group sets a mask byte to 0 or 1: stored as it is)
     }
 }
 #endif  // __HIPCC__

@@ -4,7 +4,8 @@
 //   this file          constants, TileDesc, Batch (the per-call argument struct), small wave helpers
 //   spl_k_special.h    k_mark_docs / k_special_scan / _ends / _select: text-start bitmap from the document offsets,
 //                      special-token literals (SPL_WITH_SPECIAL)
-//   spl_k_merge.h      text accessors, wave-level minima and scans, the vocabulary probes, byte_pair_encode
+//   spl_k_merge.h      text accessors, wave-level minima and scans (wave_scan_incl64 too: the one 64-bit scan of every scan kernel
+//                      below), the vocabulary probes, byte_pair_encode
 //                      (src/core/bpe.rs:67-197) as merge loops with one node per lane and tabulated pair ranks;
 //                      queue mode's k_deferred_wave
 //   spl_k_tile.h       tile geometry, LDS layout, the tail that finishes a tile's long chunks (bpe_tail_segments)
@@ -17,12 +18,14 @@
 //   spl_k_output.h     k_tile_out: tile records -> dense ids[] and per-document offsets (CSR); queue mode's
 //                      k_range_count / k_range_out, k_bpe_segments, k_bpe_long
 //   spl_k_decode.h     id -> bytes gather (k_decode_*), k_ext_specials, slabs around the RCCL all-gather, CSR rebase
-//   spl_k_collate.h    k_collate_pad / k_collate_pack: the CSR as padded rows, or as one stream cut into rows (and their host-testable mapping)
+//   spl_k_collate.h    k_collate_pad / k_collate_pack: the CSR as padded rows, or as one stream cut into rows (and their host-testable mapping);
+//                      what the gathers below share: the span's two searches (col_span_docs), the window fill, the group store tails (col_store_*)
 //   spl_k_pair.h       k_collate_pair: two CSRs joined into one row per pair of documents -- prefix A' middle B' suffix, truncated by rule (and its host-testable mapping)
 //   spl_k_chat.h       k_chat_turns, k_collate_chat: a CSR of messages joined into one row per multi-turn conversation -- role headers and footers, labels, oldest turns dropped (and its host-testable mapping)
 //   spl_k_seqpack.h    k_seqpack_next_fit / _bfd, k_seqpack_gather: whole sequences binned into rows, none cut -- the plan in one workgroup, labels, position ids, cu_seqlens (and its host-testable decisions)
 //   spl_k_window.h     k_window_scan / _totals / _add / _gather: the CSR as overlapping windows of every document (rows per document by a scan over launches)
-//   spl_k_decode_dev.h k_dec_len / k_dec_gather: ids in HBM (CSR or rows) to a bytes CSR in HBM (and their host-testable mapping)
+//   spl_k_decode_dev.h k_dec_len / k_dec_gather: ids in HBM (CSR or rows) to a bytes CSR in HBM (and their host-testable mapping; dd_first_doc, the
+//                      search for a block's first document, is spl_k_spans.h's too)
 //   spl_k_spans.h      k_span_len / k_span_write: ids in HBM (CSR or rows) to per-id byte and character spans (and their host-testable mapping)
 //   spl_k_seqscan.h    seq_one_body / seq_len_body / seq_write_body: the count-scan-write driver of the per-sequence ops below, one launch or three
 //   spl_k_stream.h     k_stream_one / k_stream_len / k_stream_write: one step of B streaming decoders, per-sequence UTF-8 state (and their host-testable mapping)

@@ -59,7 +59,7 @@ void turns(const Args& a, void* work, int32_t* len, int32_t* kept, int32_t* turn
                 }
             }
             uint64_t run = 0;
-            for (uint32_t lane = 0; lane < 64; lane++) { run += ext[lane]; x[lane] = run; }       // (seq_wave_scan64: inclusive)
+            for (uint32_t lane = 0; lane < 64; lane++) { run += ext[lane]; x[lane] = run; }       // (wave_scan_incl64: inclusive)
             for (uint32_t lane = 0; lane < 64; lane++) {
                 st[lane] = S + x[lane] - ext[lane];
                 if (base + lane < n) start[base + lane] = st[lane];

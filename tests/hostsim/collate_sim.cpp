@@ -1,12 +1,14 @@
 // collate_sim.cpp -- TEST TOOL: the mapping functions of splintr_amd/csrc/spl_k_collate.h (the code k_collate_pad / k_collate_pack run)
 // evaluated on the CPU for every output element, with the kernels' geometry: workgroups of COL_NT lanes, COL_VEC elements a lane, the
-// cooperative k-ary search played lane by lane, the window of COL_WIN document starts (guarded by canaries: it must never be indexed
-// beyond its size) and the global search for spans that hold more documents than the window.  Built with g++; no GPU.
+// kernel's own two cooperative k-ary searches (col_span_docs) with the workgroup's count played lane by lane (gather_sim.h), the window
+// of COL_WIN document starts (guarded by canaries: it must never be indexed beyond its size) and the global search for spans that hold
+// more documents than the window.  Built with g++; no GPU.
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
 #include "../../splintr_amd/csrc/spl_k_collate.h"
+#include "gather_sim.h"
 
 using namespace spl;
 
@@ -34,19 +36,6 @@ int cs_pad(const uint32_t* ids, const uint64_t* off, uint64_t n_docs, uint32_t f
     return 0;
 }
 
-// the cooperative search of one workgroup, lane by lane; returns the rounds it took
-static uint32_t kary(const uint64_t* off, uint32_t k, uint32_t& lo, uint32_t hi, uint64_t p) {
-    uint32_t rounds = 0;
-    while (lo < hi) {
-        const uint32_t step = col_kary_step(lo, hi);
-        uint32_t cnt = 0;
-        for (uint32_t lane = 0; lane < COL_NT; lane++) cnt += col_kary_pred(off, k, lo, hi, step, lane, p) ? 1u : 0u;
-        col_kary_narrow(lo, hi, step, cnt);
-        rounds++;
-    }
-    return rounds;
-}
-
 // total = rows_cap * L elements of rows / doc / pos are written (doc / pos may be null); n_out[0] = rows needed, n_out[1] = S.
 // stats: [0] spans that used the window, [1] spans that searched the global array, [2] most rounds of one search, [3] canary damage.
 int cs_pack(const uint32_t* ids, const uint64_t* off, uint64_t n_docs, uint32_t flags, uint32_t L, uint32_t pad_id, uint32_t bos_id,
@@ -68,10 +57,7 @@ int cs_pack(const uint32_t* ids, const uint64_t* off, uint64_t n_docs, uint32_t 
         bool use_win = false;
         if (in_stream) {
             const uint64_t p_last = (s_end < S ? s_end : S) - 1;
-            uint32_t r = kary(off, k, d_lo, (uint32_t)(n_docs - 1), s0);
-            if (r > stats[2]) stats[2] = r;
-            d_hi = d_lo;
-            r = kary(off, k, d_hi, col_span_hi_bound(d_lo, n_docs, k), p_last);
+            const uint32_t r = col_span_docs(off, k, k, n_docs, s0, p_last, d_lo, d_hi, LaneCount{COL_NT, nullptr});
             if (r > stats[2]) stats[2] = r;
             use_win = col_use_window(d_lo, d_hi);
             if (use_win) {

@@ -15,7 +15,7 @@ TAIL = 64
 
 def build():
     src = os.path.join(_HERE, "decode_sim.cpp")
-    deps = [src, os.path.join(_CSRC, "spl_k_decode_dev.h"), os.path.join(_CSRC, "spl_common.h")]
+    deps = [src, os.path.join(_HERE, "gather_sim.h"), os.path.join(_CSRC, "spl_k_decode_dev.h"), os.path.join(_CSRC, "spl_common.h")]
     if not os.path.exists(_LIB) or any(os.path.getmtime(d) > os.path.getmtime(_LIB) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-o", _LIB, src])
     return _LIB

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../splintr_amd/csrc/spl_k_spans.h"
+#include "gather_sim.h"
 
 using namespace spl;
 
@@ -80,21 +81,9 @@ static int run(const DecIn& a, const DecTab& t, const SpanTab& s, uint32_t lanes
         }
         s_b[BLK] = rb; s_c[BLK] = rc;
         const uint64_t B0 = blk_b[b], C0 = blk_c[b];
-        uint64_t first;
-        if (a.row_len) {
-            first = dd_first_doc_rows(a, base);
-        } else {
-            uint64_t lo = 0, hi = a.n_docs + 1, rounds = 0;
-            while (lo < hi) {
-                const uint64_t step = dd_kary_step(lo, hi, lanes);
-                uint32_t cnt = 0;
-                for (uint32_t lane = 0; lane < lanes; lane++) cnt += dd_kary_pred(a, lo, hi, step, lane, base) ? 1u : 0u;
-                dd_kary_narrow(lo, hi, step, cnt);
-                rounds++;
-            }
-            if (rounds > stats[1]) stats[1] = rounds;
-            first = lo;
-        }
+        uint64_t rounds = 0;
+        const uint64_t first = dd_first_doc(a, base, lanes, LaneCount{lanes, &rounds});
+        if (rounds > stats[1]) stats[1] = rounds;
         for (uint32_t lane = 0; lane < lanes; lane++)
             for (uint64_t d = first + lane; d <= a.n_docs; d += lanes) {
                 const uint64_t st = dd_doc_start(a, d);

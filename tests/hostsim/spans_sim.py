@@ -17,7 +17,7 @@ TAIL = 16                     # canary words behind the span arrays
 
 def build():
     src = os.path.join(_HERE, "spans_sim.cpp")
-    deps = [src] + [os.path.join(_CSRC, h) for h in ("spl_k_spans.h", "spl_k_decode_dev.h", "spl_common.h")]
+    deps = [src, os.path.join(_HERE, "gather_sim.h")] + [os.path.join(_CSRC, h) for h in ("spl_k_spans.h", "spl_k_decode_dev.h", "spl_common.h")]
     if not os.path.exists(_LIB) or any(os.path.getmtime(d) > os.path.getmtime(_LIB) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-Wno-unknown-pragmas", "-o", _LIB, src])
     return _LIB

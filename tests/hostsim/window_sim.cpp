@@ -1,13 +1,15 @@
 // window_sim.cpp -- TEST TOOL: the mapping functions of splintr_amd/csrc/spl_k_window.h (the code k_window_scan / _totals / _add /
 // _gather run) evaluated on the CPU with the kernels' geometry.  The scan: every lane's run by win_scan_lane, the sums over a workgroup's
 // lanes restated in plain code, the spans' totals chunk by chunk, the bases added.  The gather: every output element lane by lane, the
-// cooperative k-ary search over row_off played lane by lane, the window of COL_WIN row starts guarded by canaries -- and the bound that
-// makes pack mode's global fall-back unnecessary here (a span never holds more than COL_WIN documents) asserted.  Built with g++; no GPU.
+// kernel's own two cooperative searches over row_off (col_span_docs) with the count played lane by lane (gather_sim.h), the window of
+// COL_WIN row starts guarded by canaries -- and the bound that makes pack mode's global fall-back unnecessary here (a span never holds
+// more than COL_WIN documents) asserted.  Built with g++; no GPU.
 #include <cstdint>
 #include <cstring>
 #include <vector>
 
 #include "../../splintr_amd/csrc/spl_k_window.h"
+#include "gather_sim.h"
 
 using namespace spl;
 
@@ -66,18 +68,6 @@ int ws_scan(const uint64_t* off, uint64_t n_docs, uint32_t B, uint32_t step, uin
     return 0;
 }
 
-static uint32_t kary(const uint64_t* row_off, uint32_t& lo, uint32_t hi, uint64_t p) {
-    uint32_t rounds = 0;
-    while (lo < hi) {
-        const uint32_t step = col_kary_step(lo, hi);
-        uint32_t cnt = 0;
-        for (uint32_t lane = 0; lane < COL_NT; lane++) cnt += col_kary_pred(row_off, 0u, lo, hi, step, lane, p) ? 1u : 0u;
-        col_kary_narrow(lo, hi, step, cnt);
-        rounds++;
-    }
-    return rounds;
-}
-
 // total = rows_cap * L elements of rows / mask are written, rows_cap entries of len / doc / start (each may be null).
 // stats: [0] spans that hold rows of documents, [1] the most documents one span's window held, [2] most rounds of one search,
 // [3] canary damage.  Returns -1 if a span would need more than COL_WIN window entries (the bound of spl_k_window.h's header comment).
@@ -101,13 +91,11 @@ int ws_gather(const uint32_t* ids, const uint64_t* off, const uint64_t* row_off,
         if (r_first < R) {
             col_rowcol(s_end - 1, L, r_last, c);
             if (r_last >= R) r_last = R - 1;
-            uint32_t r = kary(row_off, d_lo, (uint32_t)(n_docs - 1), r_first);
-            if (r > stats[2]) stats[2] = r;
-            uint32_t d_hi = d_lo;
-            const uint32_t hi = col_span_hi_bound(d_lo, n_docs, 1u);
-            r = kary(row_off, d_hi, hi, r_last);
+            uint32_t d_hi;
+            const uint32_t r = col_span_docs(row_off, 0u, 1u, n_docs, r_first, r_last, d_lo, d_hi, LaneCount{COL_NT, nullptr});
             if (r > stats[2]) stats[2] = r;
             // the search stopped at the bound: the document behind it must start beyond the span's last row, or the bound is wrong
+            const uint32_t hi = col_span_hi_bound(d_lo, n_docs, 1u);
             if (d_hi == hi && (uint64_t)hi + 1 < n_docs && row_off[(uint64_t)hi + 1] <= r_last) return -1;
             n_win = d_hi - d_lo + 1;
             if (n_win > COL_WIN) return -1;
