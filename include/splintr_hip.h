@@ -960,7 +960,8 @@ int spl_stop_match_device(spl_tokenizer* t,
  * once; long after every prompt has healed the call then writes nothing.
  *
  * What the rule is NOT: the allowed set ignores the split pattern, as every implementation of healing does, so the healed ids need not be
- * the canonical encoding of the text; and UTF-8 validity of the continuation is not part of it.
+ * the canonical encoding of the text; and UTF-8 validity of the continuation is not part of it (spl_utf8_mask_device below is, and ANDs
+ * its rows into these).
  *
  * Two launches on hip_stream: a plan (a wavefront per sequence: the transition, then the covering ids as ONE range of the ordinary ids
  * sorted by their bytes, found with one pivot per lane, then the partial ids from the prefix order) and a fill (whole words, each written
@@ -1006,6 +1007,75 @@ typedef struct spl_heal_out {
 int spl_heal_reserve_device(spl_tokenizer* t, uint64_t max_seqs);
 int spl_heal_begin_device(spl_tokenizer* t, const spl_heal_in* in, const spl_heal_opts* o, const spl_heal_out* out, void* hip_stream);
 int spl_heal_step_device(spl_tokenizer* t, const spl_heal_in* in, const spl_heal_opts* o, const spl_heal_out* out, void* hip_stream);
+
+/* UTF-8 CONTINUATION MASKS for n_seqs sequences at once, everything in DEVICE memory: which ids may be drawn next so that
+ * the streaming decode never stalls (hold mode) and never emits U+FFFD (SPL_STREAM_REPLACE).  A byte-level BPE vocabulary holds thousands
+ * of ids whose bytes are fragments of characters; one wrong draw behind a pending lead byte stalls a hold-mode sequence for good.
+ *
+ * THE RULE.  d_state [n_seqs] are the state words spl_stream_decode_device keeps (bits 0..23 the pending bytes, 24..25 their count, 26
+ * stalled), o the decode options of that stream.  With p the pending bytes of a word -- 0 to 3 bytes, the well-formed beginning of one
+ * character -- and e(t) the bytes the streaming decode emits for id t under o (nothing for an id only the special map holds under
+ * SPL_DECODE_SKIP_SPECIAL): bit t & 31 of word t >> 5 of the row is 1 iff t is KNOWN (the vocabulary proper or the special map holds it)
+ * and p + e(t) is PREFIX-VALID -- well-formed UTF-8, optionally followed by the well-formed beginning of one character that reaches the
+ * end.  Well-formed is Unicode's table, the decoder's own: leads C2 .. F4, the second byte narrowed after E0, ED, F0 and F4.  Every other
+ * bit is 0, those from the largest known id + 1 up to 32 * n_words included.  A known id with no bytes is allowed in every state.  In hold
+ * mode the rule is "feeding t now does not stall the decoder".  A sequence that is STALLED has nothing left to protect: its row is all
+ * ones and d_live[b] is 0; so is a word no decoder leaves (pending bytes that are not the beginning of a character).  Every other
+ * sequence has d_live[b] 1.  Only SPL_DECODE_SKIP_SPECIAL of o->flags matters; o->row_len is not read.
+ *
+ * p matters only through one of eight classes -- start; one, two or three continuation bytes of any value owed; the four narrowed
+ * second-byte states behind E0, ED, F0 and F4 -- so a call is a row gather from a table of 17 rows (per class the vocabulary's ids and,
+ * apart, the special ids; the special ids of every class for SPL_DECODE_SKIP_SPECIAL) that spl_utf8_mask_reserve_device builds ON THE
+ * DEVICE, once per handle and again after spl_add_special (it uploads the decode tables and synchronises once).
+ *
+ * SPL_UTF8_AND: the row is ANDed into what d_mask holds (spl_heal_step_device's mask, a grammar's), and a stalled sequence's row is not
+ * touched; without it the row is written, every word exactly once.  d_live may be NULL.  ONE launch on hip_stream, asynchronous; after the
+ * reserve a call neither allocates nor synchronises.  No atomics on global memory, no wait between workgroups.
+ *
+ * SPL_EINVAL, with the cause in spl_last_error() and before anything touches the device: a null t, o, d_state or d_mask; a struct_size
+ * shorter than spl_decode_opts or above 4096; an unknown bit in flags or in o->flags; n_words * 32 below the largest known id + 1 (the
+ * largest of the vocabulary's and the special map's: spl_vocab_size), or n_words above 2^26; n_seqs >= 2^31; d_state not 8-byte or d_mask
+ * not 4-byte aligned; two of d_state, d_mask and d_live at one address.  Arguments are refused, never clamped. */
+#define SPL_UTF8_AND 1u  /* AND the row into d_mask instead of writing it */
+int spl_utf8_mask_reserve_device(spl_tokenizer* t);
+int spl_utf8_mask_device(spl_tokenizer* t, const uint64_t* d_state /* [n_seqs] */, uint64_t n_seqs, const spl_decode_opts* o, uint32_t flags,
+                         uint32_t n_words, int32_t* d_mask /* [n_seqs, n_words] */, uint8_t* d_live /* [n_seqs], NULL ok */, void* hip_stream);
+
+/* An allowed-token BITMASK applied to the logits in place, everything in DEVICE memory: the last link between this
+ * library's masks and the sampler.  d_logits [n_rows, n_cols] of dtype, row r at element r * row_stride (row_stride >= n_cols, in elements);
+ * d_mask int32 rows of n_words words, row r at word r * mask_stride (mask_stride >= n_words) -- the layout spl_heal_*_device and
+ * spl_utf8_mask_device write, and xgrammar's; d_live uint8 [n_rows] or NULL.
+ *
+ * For every row r with d_live NULL or d_live[r] != 0 and every column c < min(n_cols, 32 * n_words): if bit c & 31 of word c >> 5 of mask
+ * row r is 0, logits[r, c] becomes -inf of the dtype -- a store, not arithmetic: a NaN there becomes -inf.  Everything else keeps its bits
+ * exactly, NaN payloads and -0.0 included: allowed columns, columns at or beyond 32 * n_words, the row_stride - n_cols elements behind a
+ * row, rows that are not live.  The mask rows of rows that are not live are not read.
+ *
+ * The logits need no alignment beyond their element type: an odd n_cols with row_stride == n_cols puts every second half-precision row
+ * on an odd 2-byte boundary, a sliced view moves the base.  A lane owns 16 bytes of a row by absolute address (8 half-precision columns or
+ * 4 floats); the pieces at a row's two ends are handled element by element, the ones between with 16-byte accesses: all bits 1 -- neither
+ * load nor store; all bits 0 -- a store without a load; mixed -- load, select, store.  ONE launch on hip_stream, asynchronous; it never
+ * allocates or synchronises and needs no reserve.  No LDS, no atomics, no wait between workgroups.
+ *
+ * SPL_EINVAL, with the cause in spl_last_error() and before anything touches the device: a null t or a; a struct_size shorter than the
+ * struct or above 4096; a dtype that is none of the three; a null d_logits or d_mask where there is a column to mask; row_stride below
+ * n_cols or mask_stride below n_words (or either 2^40 or more); n_rows >= 2^31; n_words above 2^26; d_logits not aligned to its element
+ * type, d_mask not 4-byte aligned.  Arguments are refused, never clamped. */
+#define SPL_F32  0u
+#define SPL_F16  1u
+#define SPL_BF16 2u
+typedef struct spl_mask_apply {
+    uint32_t struct_size;                 /* sizeof the struct as the CALLER was compiled */
+    uint32_t dtype;                       /* SPL_F32, SPL_F16 or SPL_BF16 */
+    void* d_logits;
+    uint64_t n_rows;
+    uint32_t n_cols, n_words;
+    uint64_t row_stride;                  /* elements from a row of the logits to the next */
+    uint64_t mask_stride;                 /* words from a row of the mask to the next */
+    const int32_t* d_mask;
+    const uint8_t* d_live;                /* NULL ok */
+} spl_mask_apply;
+int spl_mask_apply_device(spl_tokenizer* t, const spl_mask_apply* a, void* hip_stream);
 
 /* Host-side lookup of ONE id, for consumers that decode token by token on the CPU -- the streaming
  * decoders (src/core/streaming.rs, src/python/bindings.rs:465-834 take clones of Tokenizer::decoder

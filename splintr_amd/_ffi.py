@@ -34,6 +34,7 @@ SYMBOLS = [
     "spl_stream_reserve_device", "spl_stream_decode_device",
     "spl_get_option", "spl_stop_reserve_device", "spl_stop_match_device",
     "spl_heal_reserve_device", "spl_heal_begin_device", "spl_heal_step_device",
+    "spl_utf8_mask_reserve_device", "spl_utf8_mask_device", "spl_mask_apply_device",
 ]
 SPL_PATTERN_CUSTOM = 3
 SPL_OPT_BYTE_LEVEL = 1
@@ -50,6 +51,8 @@ SPL_STOP_SLOTS, SPL_STOP_MAX_LEN, SPL_STOP_TABLE_BYTES, SPL_STOP_STATE_WORDS = 6
 SPL_STOP_INCLUDE, SPL_STOP_FINAL_ALL = 1, 2
 SPL_HEAL_AUTO, SPL_HEAL_KEEP_FREE, SPL_HEAL_I64, SPL_HEAL_PAD_LEFT = 1, 2, 4, 8
 SPL_HEAL_STATE_WORDS, SPL_HEAL_MAX_PREFIX, SPL_HEAL_MAX_BACK = 9, 64, 8
+SPL_UTF8_AND = 1
+SPL_F32, SPL_F16, SPL_BF16 = 0, 1, 2
 
 
 class SplOpts(ctypes.Structure):
@@ -170,6 +173,16 @@ class SplHealOut(ctypes.Structure):
 
     def __init__(self, state=None, mask=None, live=None, n=None, n_back=None):
         super().__init__(ctypes.sizeof(SplHealOut), 0, state, mask, live, n, n_back)
+
+
+class SplMaskApply(ctypes.Structure):
+    """spl_mask_apply (include/splintr_hip.h): the logits, the mask rows and the live bytes of spl_mask_apply_device, device addresses."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("dtype", ctypes.c_uint32), ("d_logits", ctypes.c_void_p), ("n_rows", ctypes.c_uint64),
+                ("n_cols", ctypes.c_uint32), ("n_words", ctypes.c_uint32), ("row_stride", ctypes.c_uint64), ("mask_stride", ctypes.c_uint64),
+                ("d_mask", ctypes.c_void_p), ("d_live", ctypes.c_void_p)]
+
+    def __init__(self, dtype=0, logits=None, n_rows=0, n_cols=0, n_words=0, row_stride=0, mask_stride=0, mask=None, live=None):
+        super().__init__(ctypes.sizeof(SplMaskApply), dtype, logits, n_rows, n_cols, n_words, row_stride, mask_stride, mask, live)
 
 
 _lib = None
@@ -300,6 +313,9 @@ def lib() -> ctypes.CDLL:
     L.spl_heal_reserve_device.argtypes = [vp, ctypes.c_uint64]
     L.spl_heal_begin_device.argtypes = [vp, ctypes.POINTER(SplHealIn), ctypes.POINTER(SplHealOpts), ctypes.POINTER(SplHealOut), vp]
     L.spl_heal_step_device.argtypes = [vp, ctypes.POINTER(SplHealIn), ctypes.POINTER(SplHealOpts), ctypes.POINTER(SplHealOut), vp]
+    L.spl_utf8_mask_reserve_device.argtypes = [vp]
+    L.spl_utf8_mask_device.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(SplDecodeOpts), ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp]
+    L.spl_mask_apply_device.argtypes = [vp, ctypes.POINTER(SplMaskApply), vp]
     _lib = L
     return L
 

@@ -1,7 +1,7 @@
 // spl_api.hip -- the C ABI (include/splintr_hip.h): the root of the library's one HIP translation unit.  It includes the kernels
 // (spl_kernels.hip) and the host side, one file per concern and each building on the ones before it -- spl_host_res.h (resource owners,
 // pinned pool), spl_ctx.h (per-GPU context, handle, uploads), spl_streams.h (stream probe), spl_launch.h (memo, launch order, device
-// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_pair_host.h, spl_chat_host.h, spl_seqpack_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h, spl_seqscan_host.h, spl_stream_host.h, spl_stop_host.h, spl_heal_host.h -- and holds the entry points.
+// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_pair_host.h, spl_chat_host.h, spl_seqpack_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h, spl_seqscan_host.h, spl_stream_host.h, spl_stop_host.h, spl_heal_host.h, spl_mask_host.h -- and holds the entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -50,6 +50,7 @@ using namespace spl;
 #include "spl_stream_host.h"
 #include "spl_stop_host.h"
 #include "spl_heal_host.h"
+#include "spl_mask_host.h"
 
 namespace {
 // No exception crosses the C ABI: every entry point that allocates (std::bad_alloc), starts threads or grows
@@ -221,7 +222,7 @@ static int spl_add_special_impl(spl_tokenizer* t, const uint8_t* literal, size_t
         if (general) t->special_general = true;
         t->specials.push_back(Special{lit, id});
     }
-    for (auto& c : t->ctx) { c->sp_uploaded = false; c->dec_uploaded = false; c->heal_uploaded = false; if (c->twin) c->twin->sp_uploaded = false; }
+    for (auto& c : t->ctx) { c->sp_uploaded = false; c->dec_uploaded = false; c->heal_uploaded = false; c->u8_uploaded = false; if (c->twin) c->twin->sp_uploaded = false; }
     t->max_special_id = 0;
     t->max_tok_bytes = 0;
     for (const auto& sp : t->specials) t->max_special_id = std::max(t->max_special_id, sp.id);
@@ -490,6 +491,19 @@ int spl_heal_begin_device(spl_tokenizer* t, const spl_heal_in* in, const spl_hea
 
 int spl_heal_step_device(spl_tokenizer* t, const spl_heal_in* in, const spl_heal_opts* o, const spl_heal_out* out, void* hip_stream) {
     return guarded("spl_heal_step_device", [&] { return heal_device(t, false, in, o, out, (hipStream_t)hip_stream); });
+}
+
+int spl_utf8_mask_reserve_device(spl_tokenizer* t) {
+    return guarded("spl_utf8_mask_reserve_device", [&] { return utf8_mask_reserve_device(t); });
+}
+
+int spl_utf8_mask_device(spl_tokenizer* t, const uint64_t* d_state, uint64_t n_seqs, const spl_decode_opts* o, uint32_t flags, uint32_t n_words,
+                         int32_t* d_mask, uint8_t* d_live, void* hip_stream) {
+    return guarded("spl_utf8_mask_device", [&] { return utf8_mask_device(t, d_state, n_seqs, o, flags, n_words, d_mask, d_live, (hipStream_t)hip_stream); });
+}
+
+int spl_mask_apply_device(spl_tokenizer* t, const spl_mask_apply* a, void* hip_stream) {
+    return guarded("spl_mask_apply_device", [&] { return mask_apply_device(t, a, (hipStream_t)hip_stream); });
 }
 
 int spl_pack_device(spl_tokenizer* t, const uint32_t* d_ids, const uint64_t* d_out_off, uint64_t n_docs, const spl_collate_opts* o,

@@ -72,6 +72,8 @@ struct Ctx {
     DevBuf<uint32_t> d_heal_sorted, d_heal_rank, d_heal_parent; uint32_t heal_n = 0;   // spl_heal_*_device: the ordinary ids by their bytes, id -> rank, the prefix order (upload_heal; rebuilt after spl_add_special)
     bool heal_uploaded = false;
     DevBuf<uint32_t> d_heal_scr; uint64_t heal_cap = 0;   // ... lo, hi and up to 63 partial ids per sequence, 264 bytes each (grow-only; shared with nothing)
+    DevBuf<uint32_t> d_u8_present, d_u8_rows; uint32_t u8_stride = 0;   // spl_utf8_mask_device: the vocabulary proper as a bit per id, the class table's 17 rows of u8_stride words (upload_utf8; rebuilt after spl_add_special)
+    bool u8_uploaded = false;
     DevBuf<uint8_t> d_sp_lits;                 // uploaded lazily; invalidated by spl_add_special
     bool sp_uploaded = false;
     // workspace

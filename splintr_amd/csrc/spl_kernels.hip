@@ -31,6 +31,8 @@
 //   spl_k_stream.h     k_stream_one / k_stream_len / k_stream_write: one step of B streaming decoders, per-sequence UTF-8 state (and their host-testable mapping)
 //   spl_k_stop.h       k_stop_one / k_stop_len / k_stop_write: stop strings over the streaming decode's bytes, per-sequence match state and hold-back (and their host-testable mapping)
 //   spl_k_heal.h       k_heal_plan / k_heal_fill: token healing -- per-sequence byte prefixes to allowed-token bitmasks [B, n_words] (and their host-testable first half)
+//   spl_k_utf8mask.h   k_utf8_table / k_utf8_mask: UTF-8 continuation masks -- the stream decoder's state words to allowed-token bitmasks by a row gather from a class table built on the device (and their host-testable first half)
+//   spl_k_maskapply.h  k_mask_apply: a bitmask [B, n_words] applied to f32 / f16 / bf16 logits in place, 16 bytes a lane, traffic that follows the mask (and its host-testable index arithmetic)
 //   (spl_rx_split.h, included by spl_api.hip: the device splitter for custom split patterns; its host half is in spl_launch.h)
 // (The multi-pass pipeline of rounds 1-3 -- k_bpe_lanes64, k_count, k_scan, k_compact_docs and the k_pretok
 //  instantiations without tile records -- was removed in round 4: no BASELINE configuration reached it.)
@@ -201,3 +203,5 @@ __device__ __forceinline__ uint32_t tidx() {
 #include "spl_k_stream.h"
 #include "spl_k_stop.h"
 #include "spl_k_heal.h"
+#include "spl_k_utf8mask.h"
+#include "spl_k_maskapply.h"

@@ -1051,6 +1051,12 @@ class DeviceStreamingDecoder:
         else:
             self._smask[self._mask(rows).bool()] = mask
 
+    def allowed_mask(self, out: Optional[torch.Tensor] = None, *, and_into: bool = False, n_words: Optional[int] = None):
+        """The ids the next step may draw without stalling a sequence (errors "hold") or putting U+FFFD into its text ("replace"):
+        utf8_mask_device over the decoder's own state words and skip_special_tokens -> (mask int32 [B, n_words], live uint8 [B]).  out:
+        the mask to write (and_into: to AND the rows into -- a TokenHealer's mask, a grammar's).  Nothing synchronises."""
+        return utf8_mask_device(self._tok, self._state, n_words=n_words, skip_special_tokens=self._skip, out=out, and_into=and_into)
+
     @property
     def state(self) -> torch.Tensor:
         return self._state
@@ -1283,15 +1289,13 @@ class TokenHealer:
             self.mask[rows] = -1
             self.live[rows] = 0
 
-    def apply(self, logits: torch.Tensor) -> torch.Tensor:
-        """logits [B, V] with -inf wherever the mask forbids the id, IN PLACE (torch ops: a convenience, not a kernel of this library).
-        Columns beyond 32 * n_words are left as they are."""
-        if logits.dim() != 2 or logits.shape[0] != self.batch_size:
+    def apply(self, logits: torch.Tensor, *, live_only: bool = False) -> torch.Tensor:
+        """logits [B, V] (float32, float16 or bfloat16) with -inf wherever the mask forbids the id, IN PLACE: one launch of
+        mask_apply_device.  Columns beyond 32 * n_words are left as they are.  live_only: the rows of free sequences (`live` 0) are
+        skipped -- their mask rows hold ones, so the result is the same and such a row costs one byte."""
+        if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.shape[0] != self.batch_size:
             raise ValueError("logits must have shape [batch, vocabulary]")
-        V = min(int(logits.shape[1]), 32 * self.n_words)
-        bits = ((self.mask.unsqueeze(-1) >> torch.arange(32, device=self.mask.device, dtype=torch.int32)) & 1).reshape(self.batch_size, -1)
-        logits[:, :V].masked_fill_(bits[:, :V] == 0, float("-inf"))
-        return logits
+        return mask_apply_device(self._tok, logits, self.mask, live=self.live if live_only else None)
 
     @property
     def state(self) -> torch.Tensor:
@@ -1313,6 +1317,105 @@ class TokenHealer:
 
     def __repr__(self) -> str:
         return f"TokenHealer(batch_size={self.batch_size}, n_words={self.n_words}, max_back={self.max_back}, auto={self.auto})"
+
+
+# ---------------------------------------------------------------------------------------------- UTF-8 continuation masks, bitmask -> logits
+def utf8_mask_reserve(tok: Tokenizer) -> None:
+    """spl_utf8_mask_reserve_device: the decode tables on the device and, built there, the table of the eight UTF-8 classes (again after
+    spl_add_special); utf8_mask_device calls then neither allocate nor synchronise."""
+    rc = _ffi.lib().spl_utf8_mask_reserve_device(tok.handle)
+    if rc != 0:
+        _raise_rc(rc, "spl_utf8_mask_reserve_device")
+
+
+def check_utf8_mask_args(state, *, n_words=None, out=None, and_into: bool = False) -> None:
+    """ValueError for a dtype, rank, shape, layout or device that utf8_mask_device would refuse -- before anything goes to the device."""
+    if not isinstance(state, torch.Tensor) or state.dtype != torch.int64 or state.dim() != 1 or not state.is_contiguous():
+        raise ValueError("state must be a contiguous int64 tensor of shape [batch] (the streaming decode's state words)")
+    if state.shape[0] >= (1 << 31):
+        raise ValueError("the sequences must be fewer than 2**31")
+    if n_words is not None and (isinstance(n_words, bool) or not isinstance(n_words, (int, np.integer)) or not 1 <= int(n_words) <= (1 << 26)):
+        raise ValueError(f"n_words must be an integer in 1 .. 2**26, not {n_words!r}")
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or out.dim() != 2 or out.shape[0] != state.shape[0] or \
+                not out.is_contiguous() or not 1 <= out.shape[1] <= (1 << 26) or (n_words is not None and out.shape[1] != int(n_words)):
+            raise ValueError("out must be a contiguous int32 tensor of shape [batch, n_words]")
+    elif and_into:
+        raise ValueError("and_into needs out (the mask the rows are ANDed into)")
+    if not state.is_cuda:
+        raise ValueError("state must be on a GPU (the device-side UTF-8 mask takes no host tensor)")
+    if out is not None and out.device != state.device:
+        raise ValueError("out must be on the device of state")
+
+
+def utf8_mask_device(tok: Tokenizer, state: torch.Tensor, *, n_words: Optional[int] = None, skip_special_tokens: bool = False,
+                     out: Optional[torch.Tensor] = None, and_into: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """UTF-8 continuation masks (spl_utf8_mask_device), on torch's current stream; nothing synchronises.  state int64 [B]: the streaming
+    decode's state words.  Returns (mask int32 [B, n_words], live uint8 [B]): bit t & 31 of word t >> 5 is 1 iff id t is known and its
+    bytes (none for a special id with skip_special_tokens) keep the sequence's text well-formed UTF-8 behind what is pending; a stalled
+    sequence has a row of ones and live 0.  out: the mask to write; and_into: the rows are ANDed into it.  n_words: default
+    heal_n_words(tok), or out's."""
+    check_utf8_mask_args(state, n_words=n_words, out=out, and_into=and_into)
+    dev = state.device
+    B = int(state.shape[0])
+    n_words = int(out.shape[1]) if out is not None else (heal_n_words(tok) if n_words is None else int(n_words))
+    if out is None:
+        out = torch.empty((B, n_words), dtype=torch.int32, device=dev)            # (every word of every row is written by the kernel)
+    live = torch.empty(max(B, 1), dtype=torch.uint8, device=dev)[:B]
+    # (null state and mask pointers are refused by the library: an empty batch passes addresses of its own, which nothing dereferences)
+    spare = torch.empty(4, dtype=torch.int64, device=dev).data_ptr() if B == 0 else 0
+    o = _ffi.SplDecodeOpts(_ffi.SPL_DECODE_SKIP_SPECIAL if skip_special_tokens else 0, 1)
+    rc = _ffi.lib().spl_utf8_mask_device(tok.handle, _ptr(state) or spare, B, ctypes.byref(o), _ffi.SPL_UTF8_AND if and_into else 0, n_words,
+                                         _ptr(out) or spare + 16, _ptr(live), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        _raise_rc(rc, "spl_utf8_mask_device")
+    return out, live
+
+
+_MASK_DTYPES = {torch.float32: _ffi.SPL_F32, torch.float16: _ffi.SPL_F16, torch.bfloat16: _ffi.SPL_BF16}
+
+
+def check_mask_apply_args(logits, mask, *, live=None) -> None:
+    """ValueError for a dtype, rank, shape, layout or device that mask_apply_device would refuse -- before anything goes to the device."""
+    if not isinstance(logits, torch.Tensor) or logits.dtype not in _MASK_DTYPES:
+        raise ValueError(f"logits must be a torch tensor of dtype float32, float16 or bfloat16, not {getattr(logits, 'dtype', type(logits))}")
+    if logits.dim() != 2:
+        raise ValueError(f"logits must have rank 2 ([batch, vocabulary]), not {logits.dim()}")
+    R, C = int(logits.shape[0]), int(logits.shape[1])
+    if R >= (1 << 31) or C >= (1 << 32):
+        raise ValueError("the rows must be fewer than 2**31 and the columns fewer than 2**32")
+    if R and C > 1 and logits.stride(1) != 1 or R > 1 and C and logits.stride(0) < C:
+        raise ValueError("a row of the logits must be contiguous and the rows must not overlap (stride(1) == 1, stride(0) >= columns)")
+    if not isinstance(mask, torch.Tensor) or mask.dtype != torch.int32 or mask.dim() != 2 or mask.shape[0] != R:
+        raise ValueError("mask must be an int32 tensor of shape [batch, n_words]")
+    W = int(mask.shape[1])
+    if W > (1 << 26):
+        raise ValueError("mask must have at most 2**26 words a row")
+    if R and W > 1 and mask.stride(1) != 1 or R > 1 and W and mask.stride(0) < W:
+        raise ValueError("a row of the mask must be contiguous and the rows must not overlap (stride(1) == 1, stride(0) >= n_words)")
+    if live is not None:
+        _vec("live", live, R, (torch.uint8, torch.bool), "uint8 or bool")
+    if not logits.is_cuda:
+        raise ValueError("logits must be on a GPU (the device-side mask apply takes no host tensor)")
+    for name, t in (("mask", mask), ("live", live)):
+        if t is not None and t.device != logits.device:
+            raise ValueError(f"{name} must be on the device of the logits")
+
+
+def mask_apply_device(tok: Tokenizer, logits: torch.Tensor, mask: torch.Tensor, *, live: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """An allowed-token bitmask applied to the logits IN PLACE (spl_mask_apply_device), on torch's current stream; nothing synchronises.
+    logits [B, V] float32 / float16 / bfloat16 -- any view whose rows are contiguous (a sliced base and an odd row width are fine); mask
+    int32 [B, n_words], bit t & 31 of word t >> 5 for column t (heal_*_device's, utf8_mask_device's and xgrammar's layout); live uint8 /
+    bool [B]: rows with 0 are skipped, their mask rows not read.  Where a live row's bit is 0 the logit becomes -inf (a NaN too); every
+    other element keeps its bits, columns at or beyond 32 * n_words included.  Returns logits."""
+    check_mask_apply_args(logits, mask, live=live)
+    R, C, W = int(logits.shape[0]), int(logits.shape[1]), int(mask.shape[1])
+    a = _ffi.SplMaskApply(_MASK_DTYPES[logits.dtype], _ptr(logits), R, C, W, max(int(logits.stride(0)), C) if R > 1 else C,
+                          max(int(mask.stride(0)), W) if R > 1 else W, _ptr(mask), _ptr(live))
+    rc = _ffi.lib().spl_mask_apply_device(tok.handle, ctypes.byref(a), torch.cuda.current_stream(logits.device).cuda_stream)
+    if rc != 0:
+        _raise_rc(rc, "spl_mask_apply_device")
+    return logits
 
 
 class Comm:

@@ -603,6 +603,14 @@ class Tokenizer:
         from . import device as dv
         return dv.TokenHealer(self, batch_size, n_words=n_words, max_back=max_back, auto=auto)
 
+    def apply_token_bitmask(self, logits, mask, *, live=None):
+        """Extension: an allowed-token bitmask (int32 [B, n_words]: a TokenHealer's `mask`, DeviceStreamingDecoder.allowed_mask(), or
+        xgrammar's) applied to logits [B, V] float32 / float16 / bfloat16 IN PLACE on the GPU, one launch
+        (splintr_amd.device.mask_apply_device): -inf where a bit is 0, every other element untouched.  live uint8 [B]: rows with 0 are
+        skipped.  Returns logits."""
+        from . import device as dv
+        return dv.mask_apply_device(self, logits, mask, live=live)
+
     def heal(self, texts_or_ids, *, max_back: int = 1, auto: bool = True, min_keep: int = 0, n_words: Optional[int] = None):
         """The one-call convenience for a list of prompts (str: encoded here; or lists of ids): -> (the trimmed ids, list[list[int]] --
         what to feed the model --, the TokenHealer whose mask constrains the first steps).  Synchronises once, for the trimmed lengths."""
