@@ -1077,6 +1077,106 @@ typedef struct spl_mask_apply {
 } spl_mask_apply;
 int spl_mask_apply_device(spl_tokenizer* t, const spl_mask_apply* a, void* hip_stream);
 
+/* GUIDED CHOICE for n_seqs sequences at once, everything in DEVICE memory: the answer of a sequence is exactly ONE OF
+ * UP TO 64 BYTE STRINGS -- classification labels, yes / no, tool names, multiple choice (vLLM's guided_choice, Outlines' choice).  The
+ * tables token healing sorts the vocabulary into already lie in HBM, so the mask [n_seqs, n_words] is written where the sampler reads it:
+ * no trie on the host, no copy per step.  A finite set of strings needs no automaton; grammars and regular expressions stay out of scope.
+ *
+ * THE TABLE (SPL_CHOICE_TABLE_BYTES of device memory, the CALLER's; the stop table's layout): slot s is bytes [64 s, 64 s + len[s]) and
+ * spells the choice c_s; uint8 len[64] lies behind the 64 slots.  len[s] = 0 is an empty slot and is never a choice (nor is a length
+ * above 64).  One table serves every sequence of a call; a sequence selects its candidates in its state row.
+ *
+ * b(t) and ORDINARY are token healing's: b(t) is what spl_decode_batch_device emits for id t, and t is ordinary if it is an id of the
+ * vocabulary proper and b(t) has at least one byte.  END is o->end_ids[0 .. n_end), n_end in 0 .. SPL_CHOICE_MAX_END, any ids below
+ * 32 * n_words -- special tokens are the usual case (an end-of-turn id).
+ *
+ * The state row (SPL_CHOICE_STATE_WORDS uint64 per sequence; all zero is free and fresh, so a reset is the caller zeroing rows; every bit
+ * not named is 0, so rows compare bit for bit):
+ *     word 0      A: the slots that can still be spelled, bit s for slot s
+ *     word 1      bits 0..6 k, the bytes spelled so far     bit 8 broken     bit 9 done     bits 16..21 hit, the slot answered (with done)
+ * TO BEGIN the caller writes a candidate set into word 0 with word 1 = 0 (all slots of A share their first k bytes by construction; a
+ * caller who writes k > 0 itself guarantees that: the call only reads c_s[k:]).  ON LOAD k is clamped to 64; every slot with len[s] = 0,
+ * len[s] > 64 or len[s] < k leaves A; a row with done or broken set passes through with word 0 cleared (broken wins over done); a row
+ * whose A is empty then, with neither bit set, is free and is written back all zero.
+ *
+ * THE MASK ROW: int32 [n_seqs, n_words], bit t & 31 of word t >> 5 for id t, 1 = allowed, as spl_heal_step_device writes it.  With
+ * r_s = c_s[k:] for s in A:
+ *   A empty   the sequence is FREE (or done, or broken): its row is all ones, in every bit of every one of its n_words words.
+ *   otherwise it is CONSTRAINED: bit t is set iff (a) t is ordinary and some s in A has |b(t)| <= |r_s| with r_s starting with b(t), or
+ *             (b) SPL_CHOICE_THEN_FREE is not set, t is in END and some s in A has |r_s| = 0.  Every other bit of the row is 0, up to
+ *             32 * n_words.  A constrained row is NEVER ALL ZERO: where (a) and (b) yield no id -- the vocabulary lacks the single byte
+ *             that comes next -- the sequence becomes `broken` in that call and its row is ones.
+ *
+ * STEP: per sequence the first clamp(d_len[b], 0, row_len) ids of row b of d_ids [n_seqs, row_len] (d_len NULL: all; row_len may be 0)
+ * are read in order WHILE the sequence is constrained.  For an id t:
+ *   1. t is ordinary and S = {s in A : r_s starts with b(t)} is not empty: A := S and k += |b(t)|.  Under SPL_CHOICE_THEN_FREE, if some
+ *      s in A now has len[s] = k, the sequence is `done`, hit is the lowest such s and A becomes empty.
+ *   2. otherwise, SPL_CHOICE_THEN_FREE is not set, t is in END and E = {s in A : |r_s| = 0} is not empty: the sequence is `done`,
+ *      hit = min E, A becomes empty.
+ *   3. otherwise -- a special that is no END id, an id of neither map, an int64 value outside 0 .. 2^32 - 1, an ordinary id no remainder
+ *      starts with, an END id too early -- the sequence is `broken`, A becomes empty and k := 0.
+ * Later ids of a sequence that is free, done or broken are not read.  Equivalently: an id is accepted iff its bit was set in the mask of
+ * the state in front of it.  The call then writes the mask of the state it arrived at; row_len 0 only writes masks -- that is how the
+ * first mask is obtained after the caller wrote candidate sets.  Of equal choices in two slots the lower one is the hit.
+ *
+ * WRITE-BACK, canonical: constrained (A, k); done (0, k | done | hit << 16); broken (0, 1 << 8); free zeros.  d_state_out may be
+ * d_state_in.  No other output may coincide with an input or with another output.  d_live [n_seqs] uint8 (NULL ok): 1 iff the sequence
+ * is constrained after the call.  There is no count over the batch: it would need a second launch or an atomic on global memory;
+ * live.sum() is the caller's.  SPL_CHOICE_KEEP_FREE: the rows of sequences that are not constrained after the call are not written at
+ * all -- the caller filled them with ones once.
+ *
+ * What the rule is NOT, as healing's: it ignores the split pattern, so the ids need not be the canonical encoding of the choice; UTF-8
+ * validity is not part of it (spl_utf8_mask_device with SPL_UTF8_AND can AND its rows into these afterwards); more than 64 slots, choices
+ * over 64 bytes and a table per sequence are out of scope.
+ *
+ * ONE launch on hip_stream, asynchronous: a wavefront owns a sequence (workgroups of 64 threads, no workgroup barrier); the step tests a
+ * slot per lane; the row of a constrained sequence is a handful of ids, so it starts from zeros in LDS and the ids are SCATTERED into it
+ * -- per alive slot one search of the ordinary ids sorted by their bytes for the last one that is <= r_s, then its ancestors in the prefix
+ * order -- and streamed to the mask, every word of a written row stored exactly once; a free row is stored as ones.  No scratch, no
+ * atomics on global memory, no wait between workgroups.  spl_choice_reserve_device uploads the decode tables and token healing's sorted
+ * order, id -> rank and prefix order (shared with spl_heal_*_device; synchronises once, again after spl_add_special); after it a call
+ * neither allocates nor synchronises.  The row is built in LDS a PIECE at a time: the handle option "choice_piece_words" (spl_set_option /
+ * spl_get_option; a multiple of 4 in 4 .. 8192, default 8192; for tests and measuring only) is the words of a piece -- every shipped
+ * vocabulary's row is one piece, a smaller value takes a toy vocabulary's row through several.  Same results.
+ *
+ * SPL_EINVAL, with the cause in spl_last_error() and before anything touches the device: a null t, in, o, out, d_table, d_state_in,
+ * d_state_out or d_mask; a null d_ids where there is an id to read; a struct_size shorter than a struct or above 4096; an unknown flag
+ * bit; n_words * 32 below the largest vocabulary id + 1, or n_words above 2^26; n_end above SPL_CHOICE_MAX_END; an END id at or above
+ * 32 * n_words; n_end = 0 without SPL_CHOICE_THEN_FREE (no sequence could ever finish); n_seqs >= 2^31; an array not aligned to its
+ * element type; an output that coincides with an input (other than state out with state in) or with another output.  Arguments are
+ * refused, never clamped.  A vocabulary the healing reserve refuses is refused here too. */
+#define SPL_CHOICE_THEN_FREE   1u  /* a sequence is done as soon as one of its choices is spelled out; END ids play no part */
+#define SPL_CHOICE_KEEP_FREE   2u  /* rows of sequences that are not constrained after the call are not written */
+#define SPL_CHOICE_I64         4u  /* d_ids are int64 (torch.long); default int32 / uint32 bit patterns */
+#define SPL_CHOICE_SLOTS       64
+#define SPL_CHOICE_MAX_LEN     64
+#define SPL_CHOICE_TABLE_BYTES (64 * 64 + 64)
+#define SPL_CHOICE_STATE_WORDS 2
+#define SPL_CHOICE_MAX_END     8
+
+typedef struct spl_choice_opts {
+    uint32_t struct_size;                 /* sizeof the struct as the CALLER was compiled */
+    uint32_t flags, n_words;
+    uint32_t n_end;                       /* 0 .. SPL_CHOICE_MAX_END */
+    uint32_t end_ids[SPL_CHOICE_MAX_END];
+} spl_choice_opts;
+typedef struct spl_choice_in {
+    uint32_t struct_size, row_len;        /* row_len: the columns of d_ids (may be 0) */
+    uint64_t n_seqs;
+    const void* d_ids; const int32_t* d_len;
+    const uint64_t* d_state_in;           /* [n_seqs, SPL_CHOICE_STATE_WORDS] */
+    const uint8_t* d_table;               /* SPL_CHOICE_TABLE_BYTES */
+} spl_choice_in;
+typedef struct spl_choice_out {
+    uint32_t struct_size, reserved;
+    uint64_t* d_state_out;                /* [n_seqs, SPL_CHOICE_STATE_WORDS] */
+    int32_t* d_mask;                      /* [n_seqs, n_words] */
+    uint8_t* d_live;                      /* NULL ok */
+} spl_choice_out;
+
+int spl_choice_reserve_device(spl_tokenizer* t);
+int spl_choice_step_device(spl_tokenizer* t, const spl_choice_in* in, const spl_choice_opts* o, const spl_choice_out* out, void* hip_stream);
+
 /* Host-side lookup of ONE id, for consumers that decode token by token on the CPU -- the streaming
  * decoders (src/core/streaming.rs, src/python/bindings.rs:465-834 take clones of Tokenizer::decoder
  * and special_tokens_decoder).  *bytes / *len = what decode_bytes emits for the id; the pointer

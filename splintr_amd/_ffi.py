@@ -35,6 +35,7 @@ SYMBOLS = [
     "spl_get_option", "spl_stop_reserve_device", "spl_stop_match_device",
     "spl_heal_reserve_device", "spl_heal_begin_device", "spl_heal_step_device",
     "spl_utf8_mask_reserve_device", "spl_utf8_mask_device", "spl_mask_apply_device",
+    "spl_choice_reserve_device", "spl_choice_step_device",
 ]
 SPL_PATTERN_CUSTOM = 3
 SPL_OPT_BYTE_LEVEL = 1
@@ -53,6 +54,8 @@ SPL_HEAL_AUTO, SPL_HEAL_KEEP_FREE, SPL_HEAL_I64, SPL_HEAL_PAD_LEFT = 1, 2, 4, 8
 SPL_HEAL_STATE_WORDS, SPL_HEAL_MAX_PREFIX, SPL_HEAL_MAX_BACK = 9, 64, 8
 SPL_UTF8_AND = 1
 SPL_F32, SPL_F16, SPL_BF16 = 0, 1, 2
+SPL_CHOICE_THEN_FREE, SPL_CHOICE_KEEP_FREE, SPL_CHOICE_I64 = 1, 2, 4
+SPL_CHOICE_SLOTS, SPL_CHOICE_MAX_LEN, SPL_CHOICE_TABLE_BYTES, SPL_CHOICE_STATE_WORDS, SPL_CHOICE_MAX_END = 64, 64, 64 * 64 + 64, 2, 8
 
 
 class SplOpts(ctypes.Structure):
@@ -183,6 +186,34 @@ class SplMaskApply(ctypes.Structure):
 
     def __init__(self, dtype=0, logits=None, n_rows=0, n_cols=0, n_words=0, row_stride=0, mask_stride=0, mask=None, live=None):
         super().__init__(ctypes.sizeof(SplMaskApply), dtype, logits, n_rows, n_cols, n_words, row_stride, mask_stride, mask, live)
+
+
+class SplChoiceOpts(ctypes.Structure):
+    """spl_choice_opts (include/splintr_hip.h): flags, the words of a mask row and the END ids, by value."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("n_words", ctypes.c_uint32), ("n_end", ctypes.c_uint32),
+                ("end_ids", ctypes.c_uint32 * 8)]
+
+    def __init__(self, flags=0, n_words=0, end_ids=()):
+        end_ids = tuple(end_ids)
+        super().__init__(ctypes.sizeof(SplChoiceOpts), flags, n_words, len(end_ids), (ctypes.c_uint32 * 8)(*end_ids[:8]))
+
+
+class SplChoiceIn(ctypes.Structure):
+    """spl_choice_in: the rows of ids, their lengths, the state rows and the choice table, device addresses (None: not given)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("row_len", ctypes.c_uint32), ("n_seqs", ctypes.c_uint64), ("d_ids", ctypes.c_void_p),
+                ("d_len", ctypes.c_void_p), ("d_state_in", ctypes.c_void_p), ("d_table", ctypes.c_void_p)]
+
+    def __init__(self, n_seqs=0, row_len=0, ids=None, lengths=None, state=None, table=None):
+        super().__init__(ctypes.sizeof(SplChoiceIn), row_len, n_seqs, ids, lengths, state, table)
+
+
+class SplChoiceOut(ctypes.Structure):
+    """spl_choice_out: where the outputs go, device addresses (None: not wanted)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("d_state_out", ctypes.c_void_p), ("d_mask", ctypes.c_void_p),
+                ("d_live", ctypes.c_void_p)]
+
+    def __init__(self, state=None, mask=None, live=None):
+        super().__init__(ctypes.sizeof(SplChoiceOut), 0, state, mask, live)
 
 
 _lib = None
@@ -316,6 +347,8 @@ def lib() -> ctypes.CDLL:
     L.spl_utf8_mask_reserve_device.argtypes = [vp]
     L.spl_utf8_mask_device.argtypes = [vp, vp, ctypes.c_uint64, ctypes.POINTER(SplDecodeOpts), ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp]
     L.spl_mask_apply_device.argtypes = [vp, ctypes.POINTER(SplMaskApply), vp]
+    L.spl_choice_reserve_device.argtypes = [vp]
+    L.spl_choice_step_device.argtypes = [vp, ctypes.POINTER(SplChoiceIn), ctypes.POINTER(SplChoiceOpts), ctypes.POINTER(SplChoiceOut), vp]
     _lib = L
     return L
 

@@ -217,6 +217,7 @@ struct spl_tokenizer {
     int small_path = 1;                       // batches of up to 4 KB take the latency path (encode_small)
     int slab_pack24 = 0;                      // the ids of the all-gather slabs travel three bytes each (spl_set_option "slab_pack24": every rank alike)
     uint32_t stream_one_max = ST_ONE_DEFAULT;    // "stream_one_max": most sequences spl_stream_decode_device takes in its one-launch form
+    uint32_t choice_piece = CH_PIECE;            // "choice_piece_words": tests and measuring only -- the words of a mask row spl_choice_step_device builds in LDS at once
     uint32_t heal_phase = 0;                     // "heal_phase": measuring only -- 1 the healing calls launch their plan alone, 2 their fill alone (over the scratch the last plan left)
     uint32_t stop_one_max = SP_ONE_DEFAULT;      // "stop_one_max": most sequences spl_stop_match_device takes in its one-launch form
     uint32_t seqpack_lds_max = SQP_LDS_MAX;  // "seqpack_lds_max" (tests): most sequences whose plan arrays spl_seqpack_device keeps in LDS, so that a few hundred reach the work-buffer form

@@ -1418,6 +1418,276 @@ def mask_apply_device(tok: Tokenizer, logits: torch.Tensor, mask: torch.Tensor, 
     return logits
 
 
+# ---------------------------------------------------------------------------------------------- guided choice (masks for one-of-N answers)
+def _choice_table_host(choices) -> np.ndarray:
+    if isinstance(choices, (str, bytes, bytearray)) or not hasattr(choices, "__iter__"):
+        raise ValueError("choices must be a list of str or bytes")
+    choices = list(choices)
+    if len(choices) > _ffi.SPL_CHOICE_SLOTS:
+        raise ValueError(f"at most {_ffi.SPL_CHOICE_SLOTS} choices fit the table, not {len(choices)}")
+    tab = np.zeros(_ffi.SPL_CHOICE_TABLE_BYTES, dtype=np.uint8)
+    for s, x in enumerate(choices):
+        if isinstance(x, str):
+            x = x.encode("utf-8")
+        elif not isinstance(x, (bytes, bytearray)):
+            raise ValueError(f"choice {s} must be str or bytes, not {type(x).__name__}")
+        if not 1 <= len(x) <= _ffi.SPL_CHOICE_MAX_LEN:
+            raise ValueError(f"choice {s} must have 1 .. {_ffi.SPL_CHOICE_MAX_LEN} bytes, not {len(x)}")
+        tab[_ffi.SPL_CHOICE_MAX_LEN * s:_ffi.SPL_CHOICE_MAX_LEN * s + len(x)] = np.frombuffer(bytes(x), dtype=np.uint8)
+        tab[_ffi.SPL_CHOICE_SLOTS * _ffi.SPL_CHOICE_MAX_LEN + s] = len(x)
+    return tab
+
+
+def choice_table(choices, device=None) -> torch.Tensor:
+    """The choice table of spl_choice_step_device on the device (default: the current GPU): uint8 [4160], slot s = choices[s] (str: its
+    UTF-8).  ValueError for an empty choice, one over 64 bytes, or more than 64 choices.  The tensor is the caller's."""
+    tab = _choice_table_host(choices)
+    return torch.from_numpy(tab).to(torch.device("cuda") if device is None else device)
+
+
+def _choice_state_host(selections, n_choices: int) -> np.ndarray:
+    if isinstance(n_choices, bool) or not isinstance(n_choices, (int, np.integer)) or not 0 <= int(n_choices) <= _ffi.SPL_CHOICE_SLOTS:
+        raise ValueError(f"n_choices must be an integer in 0 .. {_ffi.SPL_CHOICE_SLOTS}, not {n_choices!r}")
+    if isinstance(selections, (str, bytes, bytearray)) or not hasattr(selections, "__iter__"):
+        raise ValueError("selections must be a list with None or an iterable of slot indices per sequence")
+    selections = list(selections)
+    rows = np.zeros((len(selections), _ffi.SPL_CHOICE_STATE_WORDS), dtype=np.uint64)
+    every = (1 << int(n_choices)) - 1
+    for b, sel in enumerate(selections):
+        if sel is None:
+            rows[b, 0] = every
+            continue
+        if isinstance(sel, (str, bytes, bytearray)) or not hasattr(sel, "__iter__"):
+            raise ValueError(f"selection {b} must be None or an iterable of slot indices")
+        w = 0
+        for s in sel:
+            if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 0 <= int(s) < int(n_choices):
+                raise ValueError(f"selection {b} names slot {s!r}: slots are 0 .. {int(n_choices) - 1}")
+            w |= 1 << int(s)
+        rows[b, 0] = w
+    return rows
+
+
+def choice_state(selections, n_choices: int, device=None) -> torch.Tensor:
+    """State rows int64 [len(selections), 2] for sequences that begin: per sequence None (every slot below n_choices) or an iterable of slot
+    indices (an empty one: a free row), built on the host -- choice_step_device with ids None then writes the first masks.  The tensor
+    goes to `device` (default: the current GPU)."""
+    rows = _choice_state_host(selections, n_choices)
+    return torch.from_numpy(rows.view(np.int64)).to(torch.device("cuda") if device is None else device)
+
+
+def choice_n_words(tok: Tokenizer) -> int:
+    """The words of a mask row that cover every id the tokenizer knows (specials included)."""
+    return heal_n_words(tok)
+
+
+def choice_reserve(tok: Tokenizer) -> None:
+    """spl_choice_reserve_device: the decode tables and token healing's sorted order and prefix order on the device (shared with
+    heal_reserve); choice_step_device calls then neither allocate nor synchronise."""
+    rc = _ffi.lib().spl_choice_reserve_device(tok.handle)
+    if rc != 0:
+        _raise_rc(rc, "spl_choice_reserve_device")
+
+
+def _choice_end_ids(end_ids, then_free: bool, n_words=None):
+    end_ids = [] if end_ids is None else ([end_ids] if isinstance(end_ids, (int, np.integer)) and not isinstance(end_ids, bool) else list(end_ids))
+    for e in end_ids:
+        if isinstance(e, bool) or not isinstance(e, (int, np.integer)) or not 0 <= int(e) < (1 << 32):
+            raise ValueError(f"an END id must be an integer in 0 .. 2**32 - 1, not {e!r}")
+        if n_words is not None and int(e) >= 32 * int(n_words):
+            raise ValueError(f"END id {int(e)} is at or above 32 * n_words")
+    if len(end_ids) > _ffi.SPL_CHOICE_MAX_END:
+        raise ValueError(f"at most {_ffi.SPL_CHOICE_MAX_END} END ids, not {len(end_ids)}")
+    if not end_ids and not then_free:
+        raise ValueError("end_ids is empty and then_free is not set: no sequence could ever finish")
+    return [int(e) for e in end_ids]
+
+
+def check_choice_args(ids, lengths, state, table, *, end_ids=None, then_free: bool = False, n_words=None, keep_free: bool = False, mask=None,
+                      state_out=None) -> None:
+    """ValueError for a dtype, rank, shape, layout, size or device that choice_step_device would refuse -- before anything goes to the
+    device."""
+    if not isinstance(ids, torch.Tensor) or ids.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"the ids must be a torch tensor of dtype int32 or int64, not {getattr(ids, 'dtype', type(ids))}")
+    if ids.dim() not in (1, 2):
+        raise ValueError("the ids must have rank 1 ([batch]) or 2 ([batch, steps])")
+    if not ids.is_contiguous():
+        raise ValueError("the ids must be contiguous")
+    B = int(ids.shape[0])
+    if B >= (1 << 31) or (ids.dim() == 2 and ids.shape[1] >= (1 << 32)):
+        raise ValueError("the sequences must be fewer than 2**31 and a row shorter than 2**32")
+    if n_words is not None and (isinstance(n_words, bool) or not isinstance(n_words, (int, np.integer)) or not 1 <= int(n_words) <= (1 << 26)):
+        raise ValueError(f"n_words must be an integer in 1 .. 2**26, not {n_words!r}")
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.uint8 or table.shape != (_ffi.SPL_CHOICE_TABLE_BYTES,) or not table.is_contiguous():
+        raise ValueError(f"table must be a contiguous uint8 tensor of shape [{_ffi.SPL_CHOICE_TABLE_BYTES}] (choice_table)")
+    others = [("table", table)]
+    if lengths is not None:
+        others.append(_vec("lengths", lengths, B, (torch.int32,), "int32"))
+
+    def rows(name, t):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.shape != (B, _ffi.SPL_CHOICE_STATE_WORDS) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous int64 tensor of shape [batch, {_ffi.SPL_CHOICE_STATE_WORDS}]")
+        others.append((name, t))
+
+    rows("state", state)
+    if state_out is not None:
+        rows("state_out", state_out)
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.int32 or mask.dim() != 2 or mask.shape[0] != B or not mask.is_contiguous() or \
+                (n_words is not None and mask.shape[1] != int(n_words)):
+            raise ValueError("mask must be a contiguous int32 tensor of shape [batch, n_words]")
+        others.append(("mask", mask))
+    elif keep_free:
+        raise ValueError("keep_free needs the caller's mask (the rows of sequences that are not constrained filled with ones once)")
+    _choice_end_ids(end_ids, then_free, int(mask.shape[1]) if mask is not None else n_words)
+    if not ids.is_cuda:
+        raise ValueError("the ids must be on a GPU (device-side guided choice takes no host tensor)")
+    for name, t in others:
+        if t.device != ids.device:
+            raise ValueError(f"{name} must be on the device of the ids")
+
+
+def choice_step_device(tok: Tokenizer, ids: Optional[torch.Tensor], lengths: Optional[torch.Tensor], state: torch.Tensor, table: torch.Tensor, *,
+                       end_ids=None, then_free: bool = False, n_words: Optional[int] = None, keep_free: bool = False,
+                       mask: Optional[torch.Tensor] = None, state_out: Optional[torch.Tensor] = None):
+    """Guided choice, one step (spl_choice_step_device), on torch's current stream; nothing synchronises.  state int64 [B, 2]: the rows
+    as include/splintr_hip.h lays them out (choice_state: the candidate sets of sequences that begin); table: choice_table(...); ids [B]
+    or [B, K] int32 / int64: what the sampler drew (a sequence's first lengths[b] entries count, all with lengths None); None: no ids, the
+    masks of the state rows as they are -- the first call after choice_state.  An id some remaining choice goes on with narrows the
+    candidates; an END id (end_ids: up to 8 ids, usually specials) behind a choice that is spelled out ends the sequence (`done`, with
+    `hit` the slot); with then_free a sequence is done as soon as a choice is spelled out and END ids play no part; anything else breaks
+    it (it runs free, `broken` set).  Returns (state_out int64 [B, 2], mask int32 [B, n_words], live uint8 [B]: 1 where the sequence is
+    constrained after the call).  state_out may be state.  keep_free: rows of sequences that are not constrained after the call are not
+    written -- pass the mask whose rows hold ones for them already.  n_words: default choice_n_words(tok), or mask's."""
+    if ids is None:
+        if not isinstance(state, torch.Tensor) or state.dim() != 2:
+            raise ValueError(f"state must be a contiguous int64 tensor of shape [batch, {_ffi.SPL_CHOICE_STATE_WORDS}]")
+        ids = torch.empty((state.shape[0], 0), dtype=torch.int32, device=state.device)
+    check_choice_args(ids, lengths, state, table, end_ids=end_ids, then_free=then_free, n_words=n_words, keep_free=keep_free, mask=mask,
+                      state_out=state_out)
+    dev = ids.device
+    B = int(ids.shape[0])
+    K = int(ids.shape[1]) if ids.dim() == 2 else 1
+    n_words = int(mask.shape[1]) if mask is not None else (choice_n_words(tok) if n_words is None else int(n_words))
+    ends = _choice_end_ids(end_ids, then_free, n_words)
+    if mask is None:
+        mask = torch.empty((B, n_words), dtype=torch.int32, device=dev)          # (every word of every row is written by the kernel)
+    if state_out is None:
+        state_out = torch.empty((B, _ffi.SPL_CHOICE_STATE_WORDS), dtype=torch.int64, device=dev)
+    live = torch.empty(max(B, 1), dtype=torch.uint8, device=dev)[:B]
+    flags = (_ffi.SPL_CHOICE_THEN_FREE if then_free else 0) | (_ffi.SPL_CHOICE_KEEP_FREE if keep_free else 0) | \
+        (_ffi.SPL_CHOICE_I64 if ids.dtype == torch.int64 else 0)
+    # (null state and mask pointers are refused by the library: an empty batch passes addresses of its own, which nothing dereferences)
+    spare = torch.empty(8, dtype=torch.int64, device=dev).data_ptr() if B == 0 else 0
+    si = _ffi.SplChoiceIn(B, K, _ptr(ids), _ptr(lengths), _ptr(state) or spare, _ptr(table))
+    o = _ffi.SplChoiceOpts(flags, n_words, ends)
+    so = _ffi.SplChoiceOut(_ptr(state_out) or spare + 16, _ptr(mask) or spare + 32, _ptr(live))
+    rc = _ffi.lib().spl_choice_step_device(tok.handle, ctypes.byref(si), ctypes.byref(o), ctypes.byref(so), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        _raise_rc(rc, "spl_choice_step_device")
+    return state_out, mask, live
+
+
+class ChoiceGuide:
+    """`tokenizer.choice_guide(batch_size, choices)`: "the answer is exactly one of these strings" for a batch whose state lives on the
+    GPU.  begin(selections) writes the candidate sets and the first masks; step(ids) follows the sampler; `mask` (int32 [B, n_words], the
+    apply_token_bitmask layout) always holds the ids the next step may draw -- all ones for a sequence that is free, done or broken.
+    Nothing here synchronises."""
+
+    def __init__(self, tok: Tokenizer, batch_size: int, choices, *, end_ids=None, then_free: bool = False, n_words: Optional[int] = None):
+        if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)) or not 0 <= int(batch_size) < (1 << 31):
+            raise ValueError(f"batch_size must be an integer in 0 .. 2**31 - 1, not {batch_size!r}")
+        self._tok, self.batch_size, self.then_free = tok, int(batch_size), bool(then_free)
+        self.n_words = choice_n_words(tok) if n_words is None else int(n_words)
+        if not isinstance(choices, (str, bytes, bytearray)) and hasattr(choices, "__iter__"):
+            choices = list(choices)
+        tab = _choice_table_host(choices)
+        self.n_choices = len(choices)
+        self.end_ids = _choice_end_ids(end_ids, self.then_free, self.n_words)
+        dev = torch.device("cuda", tok._device)
+        self.table = torch.from_numpy(tab).to(dev)
+        self.mask = torch.full((self.batch_size, self.n_words), -1, dtype=torch.int32, device=dev)
+        self._state = torch.zeros((self.batch_size, _ffi.SPL_CHOICE_STATE_WORDS), dtype=torch.int64, device=dev)
+        self.live = torch.zeros(self.batch_size, dtype=torch.uint8, device=dev)
+        check_choice_args(torch.empty((self.batch_size, 0), dtype=torch.int32, device=dev), None, self._state, self.table, end_ids=self.end_ids,
+                          then_free=self.then_free, n_words=self.n_words)
+        choice_reserve(tok)
+
+    def _call(self, ids, lengths, keep_free):
+        _, _, self.live = choice_step_device(self._tok, ids, lengths, self._state, self.table, end_ids=self.end_ids, then_free=self.then_free,
+                                             keep_free=keep_free, mask=self.mask, state_out=self._state)
+        return self.mask
+
+    def begin(self, selections=None, rows=None) -> torch.Tensor:
+        """The candidate sets of sequences that begin, and the first masks -> the mask.  selections: None (every sequence: every choice), or
+        per sequence None or an iterable of slot indices (an empty one: the sequence runs free).  rows: the sequences that begin (indices or
+        a bool mask; selections then has one entry per such sequence); the others keep their state."""
+        dev = self._state.device
+        if rows is None:
+            sel = [None] * self.batch_size if selections is None else list(selections)
+            if len(sel) != self.batch_size:
+                raise ValueError(f"selections must have one entry per sequence ({self.batch_size}), not {len(sel)}")
+            self._state.copy_(torch.from_numpy(_choice_state_host(sel, self.n_choices).view(np.int64)).to(dev), non_blocking=True)
+        else:
+            idx = torch.as_tensor(rows, device=dev)
+            idx = idx.nonzero().flatten() if idx.dtype == torch.bool else idx.to(torch.int64).flatten()
+            sel = [None] * int(idx.numel()) if selections is None else list(selections)
+            if len(sel) != int(idx.numel()):
+                raise ValueError(f"selections must have one entry per row that begins ({int(idx.numel())}), not {len(sel)}")
+            self._state[idx] = torch.from_numpy(_choice_state_host(sel, self.n_choices).view(np.int64)).to(dev)
+        return self._call(None, None, False)
+
+    def step(self, ids: Optional[torch.Tensor], lengths: Optional[torch.Tensor] = None, *, keep_free: bool = False) -> torch.Tensor:
+        """What the sampler drew, [B] or [B, K] (None: only the masks, after the caller wrote rows into `state`) -> the mask.  keep_free:
+        the rows of sequences that are not constrained are not written again -- right once a step WITHOUT it has run after the last
+        sequence left its constraint (its row holds ones since then)."""
+        return self._call(ids, lengths, keep_free)
+
+    def reset(self, rows=None) -> None:
+        """All sequences (rows None) or the given ones (indices or a bool mask) free and fresh, their mask rows ones."""
+        if rows is None:
+            self._state.zero_(); self.mask.fill_(-1); self.live.zero_()
+        else:
+            self._state[rows] = 0
+            self.mask[rows] = -1
+            self.live[rows] = 0
+
+    def apply(self, logits: torch.Tensor, *, live_only: bool = False) -> torch.Tensor:
+        """logits [B, V] (float32, float16 or bfloat16) with -inf wherever the mask forbids the id, IN PLACE: one launch of
+        mask_apply_device.  live_only: the rows of sequences that are not constrained (`live` 0) are skipped -- their mask rows hold ones,
+        so the result is the same."""
+        if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.shape[0] != self.batch_size:
+            raise ValueError("logits must have shape [batch, vocabulary]")
+        return mask_apply_device(self._tok, logits, self.mask, live=self.live if live_only else None)
+
+    @property
+    def state(self) -> torch.Tensor:
+        """int64 [B, 2] on the device, as include/splintr_hip.h lays it out (the guide's own tensor: a row written here counts)"""
+        return self._state
+
+    @property
+    def spelled(self) -> torch.Tensor:
+        """int64 [B] on the device: k, the bytes every sequence has spelled so far"""
+        return self._state[:, 1] & 0x7F
+
+    @property
+    def broken(self) -> torch.Tensor:
+        return ((self._state[:, 1] >> 8) & 1).bool()
+
+    @property
+    def done(self) -> torch.Tensor:
+        return ((self._state[:, 1] >> 9) & 1).bool()
+
+    @property
+    def hit(self) -> torch.Tensor:
+        """int64 [B] on the device: the slot a done sequence answered, -1 for every other sequence"""
+        w = self._state[:, 1]
+        return torch.where((w >> 9) & 1 != 0, (w >> 16) & 63, torch.full_like(w, -1))
+
+    def __repr__(self) -> str:
+        return f"ChoiceGuide(batch_size={self.batch_size}, n_choices={self.n_choices}, n_words={self.n_words}, then_free={self.then_free})"
+
+
 class Comm:
     """One rank of the library's own RCCL communicator (include/splintr_hip.h: spl_comm_*).  The 128-byte id is
     made by rank 0 and handed to the others by whatever the caller has; `from_torch_group` uses an existing

@@ -603,6 +603,15 @@ class Tokenizer:
         from . import device as dv
         return dv.TokenHealer(self, batch_size, n_words=n_words, max_back=max_back, auto=auto)
 
+    def choice_guide(self, batch_size: int, choices, *, end_ids=None, then_free: bool = False, n_words: Optional[int] = None):
+        """Extension: guided choice on the GPU (splintr_amd.device.ChoiceGuide): the answer of every sequence is exactly one of up to 64
+        `choices` (str or bytes, 1 .. 64 bytes each).  begin(selections) writes the candidate sets and the first masks, step(ids) follows
+        the sampler, and `mask` -- int32 [B, n_words], the apply_token_bitmask layout -- holds the ids some remaining choice goes on with.
+        end_ids: the ids (usually specials, up to 8) that may follow a choice that is spelled out and end the sequence; then_free: a
+        sequence is done as soon as a choice is spelled out.  `done`, `hit`, `broken` and `spelled` read the state on the device."""
+        from . import device as dv
+        return dv.ChoiceGuide(self, batch_size, choices, end_ids=end_ids, then_free=then_free, n_words=n_words)
+
     def apply_token_bitmask(self, logits, mask, *, live=None):
         """Extension: an allowed-token bitmask (int32 [B, n_words]: a TokenHealer's `mask`, DeviceStreamingDecoder.allowed_mask(), or
         xgrammar's) applied to logits [B, V] float32 / float16 / bfloat16 IN PLACE on the GPU, one launch
