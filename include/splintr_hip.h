@@ -1080,7 +1080,7 @@ int spl_mask_apply_device(spl_tokenizer* t, const spl_mask_apply* a, void* hip_s
 /* GUIDED CHOICE for n_seqs sequences at once, everything in DEVICE memory: the answer of a sequence is exactly ONE OF
  * UP TO 64 BYTE STRINGS -- classification labels, yes / no, tool names, multiple choice (vLLM's guided_choice, Outlines' choice).  The
  * tables token healing sorts the vocabulary into already lie in HBM, so the mask [n_seqs, n_words] is written where the sampler reads it:
- * no trie on the host, no copy per step.  A finite set of strings needs no automaton; grammars and regular expressions stay out of scope.
+ * no trie on the host, no copy per step.  A finite set of strings needs no automaton; regular expressions are spl_dfa_step_device's (below), grammars stay out of scope.
  *
  * THE TABLE (SPL_CHOICE_TABLE_BYTES of device memory, the CALLER's; the stop table's layout): slot s is bytes [64 s, 64 s + len[s]) and
  * spells the choice c_s; uint8 len[64] lies behind the 64 slots.  len[s] = 0 is an empty slot and is never a choice (nor is a length
@@ -1176,6 +1176,109 @@ typedef struct spl_choice_out {
 
 int spl_choice_reserve_device(spl_tokenizer* t);
 int spl_choice_step_device(spl_tokenizer* t, const spl_choice_in* in, const spl_choice_opts* o, const spl_choice_out* out, void* hip_stream);
+
+/* THE REGEX GUIDE for n_seqs sequences at once, everything in DEVICE memory: the answer of a sequence MATCHES A REGULAR
+ * EXPRESSION -- dates, numbers, identifiers, a fixed JSON shape (vLLM's guided_regex, Outlines' regex).  The library holds no automaton
+ * compiler: the calls take a deterministic automaton over BYTES as a table in the caller's device memory (splintr_amd/dfa.py compiles
+ * one from a pattern; the calls do not care how the table was made).  The expensive half -- which ids may follow which state, seconds to
+ * minutes on a host for 100 k to 200 k ids -- is spl_dfa_index_device, a GPU job; a step is then a row copy.
+ *
+ * THE TABLE (SPL_DFA_TABLE_BYTES(n_states) of device memory, the CALLER's, 2-byte aligned): uint16 trans[n_states][256], then
+ * uint8 accept[n_states].  trans[q][x] is the state behind byte x in state q; ON LOAD every value >= n_states is DEAD (SPL_DFA_DEAD is
+ * the one a builder writes) -- the kernels never index outside the table, whatever it holds.  accept[q] != 0: q accepts.  n_states is
+ * 1 .. SPL_DFA_MAX_STATES.  One table serves a call; a sequence's start state is whatever the caller writes into its state word, so
+ * several automata stacked into one table serve one batch.
+ *
+ * b(t) and ORDINARY are token healing's: b(t) is what spl_decode_batch_device emits for id t, and t is ordinary if it is an id of the
+ * vocabulary proper and b(t) has at least one byte.  walk(q, b(t)) follows trans byte by byte and is DEAD as soon as a step is.  END is
+ * o->end_ids[0 .. n_end), n_end in 1 .. SPL_DFA_MAX_END, any ids below 32 * n_words -- special tokens are the usual case.
+ *
+ * THE INDEX (SPL_DFA_INDEX_BYTES(n_states, n_words) of device memory, the CALLER's, 4-byte aligned), written by spl_dfa_index_device:
+ * int32 rows[n_states][stride], stride = n_words rounded up to a multiple of four, then uint8 some[n_states].  Bit t & 31 of word
+ * t >> 5 of row q is 1 iff t is ordinary and walk(q, b(t)) != DEAD; every other bit is 0, up to 32 * stride.  some[q] is 1 iff row q
+ * has a set bit.  Every word and every some byte is stored exactly once.  The index holds ordinary ids only, so it does not depend on
+ * the END ids; it belongs to (table, n_states, n_words, the handle's vocabulary) and a step must be given the n_words it was built with.
+ * It is rebuilt by the caller after spl_add_special, as the reserves rebuild their tables.
+ *
+ * THE STATE ROW (SPL_DFA_STATE_WORDS uint64 per sequence; all zero is free, so a reset is the caller zeroing words; every bit not named
+ * is 0, so rows compare bit for bit):    bits 0..15 q     bit 16 constrained     bit 17 broken     bit 18 done
+ * TO BEGIN the caller writes start | 1 << 16.  ON LOAD broken wins over done and done over constrained; a constrained row with
+ * q >= n_states becomes broken.
+ *
+ * THE MASK ROW: int32 [n_seqs, n_words], bit t & 31 of word t >> 5 for id t, 1 = allowed, as spl_heal_step_device writes it.
+ *   free, done or broken   every bit of every one of the row's n_words words is 1.
+ *   constrained            rows[q], ORed with the END bits if accept[q].  A constrained row is NEVER ALL ZERO: where that row is empty
+ *                          (some[q] = 0 and q does not accept) the sequence becomes `broken` in that call and its row is ones.
+ *
+ * STEP: per sequence the first clamp(d_len[b], 0, row_len) ids of row b of d_ids [n_seqs, row_len] (d_len NULL: all; row_len may be 0)
+ * are read in order WHILE the sequence is constrained.  For an id t:
+ *   1. t is ordinary and walk(q, b(t)) = q' != DEAD: q := q'.
+ *   2. otherwise, t is in END and accept[q]: the sequence is `done`; q stays the accepting state it ended in.
+ *   3. otherwise -- a special that is no END id, an id of neither map, an int64 value outside 0 .. 2^32 - 1, an ordinary id whose walk
+ *      dies, an END id in a state that does not accept -- the sequence is `broken`.
+ * An END id that is ordinary and walks on is an ordinary id (rule 1 wins).  Later ids of a sequence that is free, done or broken are
+ * not read.  Equivalently: an id is accepted iff its bit was set in the mask of the state in front of it.  The call then writes the mask
+ * of the state it arrived at; row_len 0 only writes masks -- that is how the first mask is obtained after the caller wrote start states.
+ *
+ * WRITE-BACK, canonical: constrained q | 1 << 16; done q | 1 << 18; broken 1 << 17; free 0.  d_state_out may be d_state_in.  No other
+ * output may coincide with an input or with another output.  d_live [n_seqs] uint8 (NULL ok): 1 iff the sequence is constrained after
+ * the call.  SPL_DFA_KEEP_FREE: the rows of sequences that are not constrained after the call are not written at all -- the caller
+ * filled them with ones once.  There is no "then free" flag: done at the first accepting state is not what a regular expression means.
+ *
+ * What the rule is NOT, as healing's: it ignores the split pattern, so the ids need not be the canonical encoding of the match; UTF-8
+ * validity is not part of it -- a `.` or a negated class of the pattern admits any byte (spl_utf8_mask_device with SPL_UTF8_AND can AND
+ * its rows into these afterwards); the table is assumed TRIMMED (every state reaches an accepting one, as splintr_amd/dfa.py leaves it):
+ * that is what makes "the walk does not die" the right rule, an untrimmed table merely allows ids that lead nowhere.  Context-free
+ * grammars, more than 4096 states and a table per sequence are out of scope.
+ *
+ * SHAPE.  spl_dfa_index_device: two launches on hip_stream, asynchronous -- a lane owns an id and tests its first byte before anything
+ * else, a wavefront's ballot is two words of a row; then a wavefront per state ORs its row into some[q].  spl_dfa_step_device: ONE
+ * launch -- a wavefront owns a sequence, walks the step's ids (serial, short) and copies the row, 16 bytes a lane where n_words is a
+ * multiple of four and the mask and the index are 16-byte aligned, word by word otherwise, the END bits ORed into a word before its one
+ * store.  No LDS, no scratch, no atomics on global memory, no wait between workgroups.  spl_dfa_reserve_device uploads the decode tables
+ * and token healing's id -> rank (shared with spl_heal_*_device and spl_choice_*_device; synchronises once, again after
+ * spl_add_special); after it neither call allocates nor synchronises.
+ *
+ * SPL_EINVAL, with the cause in spl_last_error() and before anything touches the device: a null t, in, o, out, d_table, d_index,
+ * d_state_in, d_state_out or d_mask; a null d_ids where there is an id to read; a struct_size shorter than a struct or above 4096; an
+ * unknown flag bit; n_states 0 or above SPL_DFA_MAX_STATES; n_words * 32 below the largest vocabulary id + 1, or n_words above 2^26;
+ * n_end 0 or above SPL_DFA_MAX_END; an END id at or above 32 * n_words; n_seqs >= 2^31; an array not aligned to its element type; an
+ * output that coincides with an input (other than state out with state in) or with another output.  Arguments are refused, never
+ * clamped.  A vocabulary the healing reserve refuses is refused here too. */
+#define SPL_DFA_KEEP_FREE   2u  /* rows of sequences that are not constrained after the call are not written */
+#define SPL_DFA_I64         4u  /* d_ids are int64 (torch.long); default int32 / uint32 bit patterns */
+#define SPL_DFA_DEAD        0xFFFF
+#define SPL_DFA_MAX_STATES  4096
+#define SPL_DFA_STATE_WORDS 1
+#define SPL_DFA_MAX_END     8
+#define SPL_DFA_TABLE_BYTES(n_states) ((size_t)(n_states) * 512 + (size_t)(n_states))
+#define SPL_DFA_INDEX_BYTES(n_states, n_words) ((size_t)(n_states) * ((((size_t)(n_words) + 3) & ~(size_t)3) * 4 + 1))
+
+typedef struct spl_dfa_opts {
+    uint32_t struct_size;                 /* sizeof the struct as the CALLER was compiled */
+    uint32_t flags, n_words;
+    uint32_t n_end;                       /* 1 .. SPL_DFA_MAX_END */
+    uint32_t end_ids[SPL_DFA_MAX_END];
+} spl_dfa_opts;
+typedef struct spl_dfa_in {
+    uint32_t struct_size, row_len;        /* row_len: the columns of d_ids (may be 0) */
+    uint64_t n_seqs;
+    const void* d_ids; const int32_t* d_len;
+    const uint64_t* d_state_in;           /* [n_seqs, SPL_DFA_STATE_WORDS] */
+    const uint8_t* d_table;               /* SPL_DFA_TABLE_BYTES(n_states) */
+    const int32_t* d_index;               /* SPL_DFA_INDEX_BYTES(n_states, n_words), as spl_dfa_index_device left it */
+    uint32_t n_states, reserved;
+} spl_dfa_in;
+typedef struct spl_dfa_out {
+    uint32_t struct_size, reserved;
+    uint64_t* d_state_out;                /* [n_seqs, SPL_DFA_STATE_WORDS] */
+    int32_t* d_mask;                      /* [n_seqs, n_words] */
+    uint8_t* d_live;                      /* NULL ok */
+} spl_dfa_out;
+
+int spl_dfa_reserve_device(spl_tokenizer* t);
+int spl_dfa_index_device(spl_tokenizer* t, const uint8_t* d_table, uint32_t n_states, uint32_t n_words, int32_t* d_index, void* hip_stream);
+int spl_dfa_step_device(spl_tokenizer* t, const spl_dfa_in* in, const spl_dfa_opts* o, const spl_dfa_out* out, void* hip_stream);
 
 /* Host-side lookup of ONE id, for consumers that decode token by token on the CPU -- the streaming
  * decoders (src/core/streaming.rs, src/python/bindings.rs:465-834 take clones of Tokenizer::decoder

@@ -36,6 +36,7 @@ SYMBOLS = [
     "spl_heal_reserve_device", "spl_heal_begin_device", "spl_heal_step_device",
     "spl_utf8_mask_reserve_device", "spl_utf8_mask_device", "spl_mask_apply_device",
     "spl_choice_reserve_device", "spl_choice_step_device",
+    "spl_dfa_reserve_device", "spl_dfa_index_device", "spl_dfa_step_device",
 ]
 SPL_PATTERN_CUSTOM = 3
 SPL_OPT_BYTE_LEVEL = 1
@@ -56,6 +57,16 @@ SPL_UTF8_AND = 1
 SPL_F32, SPL_F16, SPL_BF16 = 0, 1, 2
 SPL_CHOICE_THEN_FREE, SPL_CHOICE_KEEP_FREE, SPL_CHOICE_I64 = 1, 2, 4
 SPL_CHOICE_SLOTS, SPL_CHOICE_MAX_LEN, SPL_CHOICE_TABLE_BYTES, SPL_CHOICE_STATE_WORDS, SPL_CHOICE_MAX_END = 64, 64, 64 * 64 + 64, 2, 8
+SPL_DFA_KEEP_FREE, SPL_DFA_I64 = 2, 4
+SPL_DFA_DEAD, SPL_DFA_MAX_STATES, SPL_DFA_STATE_WORDS, SPL_DFA_MAX_END = 0xFFFF, 4096, 1, 8
+
+
+def SPL_DFA_TABLE_BYTES(n_states: int) -> int:
+    return n_states * 512 + n_states
+
+
+def SPL_DFA_INDEX_BYTES(n_states: int, n_words: int) -> int:
+    return n_states * (((n_words + 3) & ~3) * 4 + 1)
 
 
 class SplOpts(ctypes.Structure):
@@ -216,6 +227,35 @@ class SplChoiceOut(ctypes.Structure):
         super().__init__(ctypes.sizeof(SplChoiceOut), 0, state, mask, live)
 
 
+class SplDfaOpts(ctypes.Structure):
+    """spl_dfa_opts (include/splintr_hip.h): flags, the words of a mask row and the END ids, by value."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("n_words", ctypes.c_uint32), ("n_end", ctypes.c_uint32),
+                ("end_ids", ctypes.c_uint32 * 8)]
+
+    def __init__(self, flags=0, n_words=0, end_ids=()):
+        end_ids = tuple(end_ids)
+        super().__init__(ctypes.sizeof(SplDfaOpts), flags, n_words, len(end_ids), (ctypes.c_uint32 * 8)(*end_ids[:8]))
+
+
+class SplDfaIn(ctypes.Structure):
+    """spl_dfa_in: the rows of ids, their lengths, the state words, the DFA table and its index, device addresses (None: not given)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("row_len", ctypes.c_uint32), ("n_seqs", ctypes.c_uint64), ("d_ids", ctypes.c_void_p),
+                ("d_len", ctypes.c_void_p), ("d_state_in", ctypes.c_void_p), ("d_table", ctypes.c_void_p), ("d_index", ctypes.c_void_p),
+                ("n_states", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    def __init__(self, n_seqs=0, row_len=0, ids=None, lengths=None, state=None, table=None, index=None, n_states=0):
+        super().__init__(ctypes.sizeof(SplDfaIn), row_len, n_seqs, ids, lengths, state, table, index, n_states, 0)
+
+
+class SplDfaOut(ctypes.Structure):
+    """spl_dfa_out: where the outputs go, device addresses (None: not wanted)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("d_state_out", ctypes.c_void_p), ("d_mask", ctypes.c_void_p),
+                ("d_live", ctypes.c_void_p)]
+
+    def __init__(self, state=None, mask=None, live=None):
+        super().__init__(ctypes.sizeof(SplDfaOut), 0, state, mask, live)
+
+
 _lib = None
 
 
@@ -349,6 +389,9 @@ def lib() -> ctypes.CDLL:
     L.spl_mask_apply_device.argtypes = [vp, ctypes.POINTER(SplMaskApply), vp]
     L.spl_choice_reserve_device.argtypes = [vp]
     L.spl_choice_step_device.argtypes = [vp, ctypes.POINTER(SplChoiceIn), ctypes.POINTER(SplChoiceOpts), ctypes.POINTER(SplChoiceOut), vp]
+    L.spl_dfa_reserve_device.argtypes = [vp]
+    L.spl_dfa_index_device.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
+    L.spl_dfa_step_device.argtypes = [vp, ctypes.POINTER(SplDfaIn), ctypes.POINTER(SplDfaOpts), ctypes.POINTER(SplDfaOut), vp]
     _lib = L
     return L
 

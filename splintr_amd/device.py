@@ -1688,6 +1688,311 @@ class ChoiceGuide:
         return f"ChoiceGuide(batch_size={self.batch_size}, n_choices={self.n_choices}, n_words={self.n_words}, then_free={self.then_free})"
 
 
+# ---------------------------------------------------------------------------------------------- the regex guide (masks from a byte DFA)
+def _dfa_of(dfa):
+    """(trans uint16 [S, 256], accept uint8 [S]) of a splintr_amd.dfa.ByteDFA or of such a pair, checked."""
+    trans, accept = (dfa.trans, dfa.accept) if hasattr(dfa, "trans") else dfa
+    trans, accept = np.asarray(trans), np.asarray(accept)
+    if trans.dtype != np.uint16 or trans.ndim != 2 or trans.shape[1] != 256 or not 1 <= trans.shape[0] <= _ffi.SPL_DFA_MAX_STATES:
+        raise ValueError(f"the transitions must be a uint16 array of shape [n_states, 256] with n_states in 1 .. {_ffi.SPL_DFA_MAX_STATES}")
+    if accept.shape != (trans.shape[0],):
+        raise ValueError("accept must have one entry per state")
+    return trans, (accept != 0).astype(np.uint8)
+
+
+def _dfa_table_host(dfa) -> np.ndarray:
+    trans, accept = _dfa_of(dfa)
+    return np.concatenate([np.ascontiguousarray(trans, dtype="<u2").view(np.uint8).reshape(-1), accept])
+
+
+def dfa_table(dfa, device=None) -> torch.Tensor:
+    """The DFA table of spl_dfa_index_device / spl_dfa_step_device on the device (default: the current GPU): uint8 [S * 512 + S] -- uint16
+    trans[S][256], then accept[S].  dfa: a splintr_amd.dfa.ByteDFA (compile_regex, stack) or (trans, accept).  The tensor is the caller's."""
+    return torch.from_numpy(_dfa_table_host(dfa)).to(torch.device("cuda") if device is None else device)
+
+
+def _dfa_state_host(starts) -> np.ndarray:
+    if isinstance(starts, (str, bytes, bytearray)) or not hasattr(starts, "__iter__"):
+        raise ValueError("starts must be a list with None or a start state per sequence")
+    rows = []
+    for b, q in enumerate(starts):
+        if q is None:
+            rows.append(0)
+            continue
+        if isinstance(q, bool) or not isinstance(q, (int, np.integer)) or not 0 <= int(q) < _ffi.SPL_DFA_MAX_STATES:
+            raise ValueError(f"start {b} must be None or a state in 0 .. {_ffi.SPL_DFA_MAX_STATES - 1}, not {q!r}")
+        rows.append(int(q) | 1 << 16)
+    return np.array(rows, dtype=np.int64).reshape(len(rows))
+
+
+def dfa_state(starts, device=None) -> torch.Tensor:
+    """State words int64 [len(starts)] for sequences that begin: per sequence a start state (start | 1 << 16) or None (a free row), built
+    on the host -- dfa_step_device with ids None then writes the first masks.  The tensor goes to `device` (default: the current GPU)."""
+    return torch.from_numpy(_dfa_state_host(starts)).to(torch.device("cuda") if device is None else device)
+
+
+def dfa_n_words(tok: Tokenizer) -> int:
+    """The words of a mask row that cover every id the tokenizer knows (specials included)."""
+    return heal_n_words(tok)
+
+
+def dfa_reserve(tok: Tokenizer) -> None:
+    """spl_dfa_reserve_device: the decode tables and token healing's id -> rank on the device (shared with heal_reserve and
+    choice_reserve); dfa_index_device and dfa_step_device calls then neither allocate nor synchronise."""
+    rc = _ffi.lib().spl_dfa_reserve_device(tok.handle)
+    if rc != 0:
+        _raise_rc(rc, "spl_dfa_reserve_device")
+
+
+def _dfa_end_ids(end_ids, n_words=None):
+    end_ids = [] if end_ids is None else ([end_ids] if isinstance(end_ids, (int, np.integer)) and not isinstance(end_ids, bool) else list(end_ids))
+    for e in end_ids:
+        if isinstance(e, bool) or not isinstance(e, (int, np.integer)) or not 0 <= int(e) < (1 << 32):
+            raise ValueError(f"an END id must be an integer in 0 .. 2**32 - 1, not {e!r}")
+        if n_words is not None and int(e) >= 32 * int(n_words):
+            raise ValueError(f"END id {int(e)} is at or above 32 * n_words")
+    if not 1 <= len(end_ids) <= _ffi.SPL_DFA_MAX_END:
+        raise ValueError(f"1 .. {_ffi.SPL_DFA_MAX_END} END ids are needed (without one no sequence could ever finish), not {len(end_ids)}")
+    return [int(e) for e in end_ids]
+
+
+def _dfa_check_table(table, n_states):
+    if isinstance(n_states, bool) or not isinstance(n_states, (int, np.integer)) or not 1 <= int(n_states) <= _ffi.SPL_DFA_MAX_STATES:
+        raise ValueError(f"n_states must be an integer in 1 .. {_ffi.SPL_DFA_MAX_STATES}, not {n_states!r}")
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.uint8 or table.shape != (_ffi.SPL_DFA_TABLE_BYTES(int(n_states)),) or \
+            not table.is_contiguous():
+        raise ValueError(f"table must be a contiguous uint8 tensor of shape [{_ffi.SPL_DFA_TABLE_BYTES(int(n_states))}] (dfa_table) for {int(n_states)} states")
+
+
+def _dfa_check_n_words(n_words):
+    if n_words is not None and (isinstance(n_words, bool) or not isinstance(n_words, (int, np.integer)) or not 1 <= int(n_words) <= (1 << 26)):
+        raise ValueError(f"n_words must be an integer in 1 .. 2**26, not {n_words!r}")
+
+
+def check_dfa_args(ids, lengths, state, table, index, n_states, *, end_ids=None, n_words=None, keep_free: bool = False, mask=None, state_out=None) -> None:
+    """ValueError for a dtype, rank, shape, layout, size or device that dfa_step_device would refuse -- before anything goes to the device.
+    n_words (or mask's width) must be the one the index was built with: the index's size is checked against it."""
+    if not isinstance(ids, torch.Tensor) or ids.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"the ids must be a torch tensor of dtype int32 or int64, not {getattr(ids, 'dtype', type(ids))}")
+    if ids.dim() not in (1, 2):
+        raise ValueError("the ids must have rank 1 ([batch]) or 2 ([batch, steps])")
+    if not ids.is_contiguous():
+        raise ValueError("the ids must be contiguous")
+    B = int(ids.shape[0])
+    if B >= (1 << 31) or (ids.dim() == 2 and ids.shape[1] >= (1 << 32)):
+        raise ValueError("the sequences must be fewer than 2**31 and a row shorter than 2**32")
+    _dfa_check_n_words(n_words)
+    _dfa_check_table(table, n_states)
+    others = [("table", table)]
+    if lengths is not None:
+        others.append(_vec("lengths", lengths, B, (torch.int32,), "int32"))
+    others.append(_vec("state", state, B, (torch.int64,), "int64"))
+    if state_out is not None:
+        others.append(_vec("state_out", state_out, B, (torch.int64,), "int64"))
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.int32 or mask.dim() != 2 or mask.shape[0] != B or not mask.is_contiguous() or \
+                (n_words is not None and mask.shape[1] != int(n_words)):
+            raise ValueError("mask must be a contiguous int32 tensor of shape [batch, n_words]")
+        others.append(("mask", mask))
+    elif keep_free:
+        raise ValueError("keep_free needs the caller's mask (the rows of sequences that are not constrained filled with ones once)")
+    width = int(mask.shape[1]) if mask is not None else n_words
+    if width is not None:
+        want = _ffi.SPL_DFA_INDEX_BYTES(int(n_states), int(width))
+        if not isinstance(index, torch.Tensor) or index.dtype != torch.uint8 or index.shape != (want,) or not index.is_contiguous():
+            raise ValueError(f"index must be a contiguous uint8 tensor of shape [{want}] (dfa_index_device with the same n_states and n_words)")
+    elif not isinstance(index, torch.Tensor) or index.dtype != torch.uint8 or index.dim() != 1 or not index.is_contiguous():
+        raise ValueError("index must be a contiguous uint8 tensor (dfa_index_device)")
+    others.append(("index", index))
+    _dfa_end_ids(end_ids, width)
+    if not ids.is_cuda:
+        raise ValueError("the ids must be on a GPU (the device-side regex guide takes no host tensor)")
+    for name, t in others:
+        if t.device != ids.device:
+            raise ValueError(f"{name} must be on the device of the ids")
+
+
+def dfa_index_device(tok: Tokenizer, table: torch.Tensor, n_states: int, *, n_words: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The state x vocabulary index of a DFA table (spl_dfa_index_device), built on the GPU on torch's current stream; nothing
+    synchronises.  Returns uint8 [n_states * (stride * 4 + 1)], stride = n_words rounded up to four: int32 rows[n_states][stride] -- bit
+    t of row q is 1 iff id t is ordinary and its bytes can be walked from state q without dying -- then some[n_states].  dfa_index_rows
+    gives the two views.  n_words: default dfa_n_words(tok).  Build it again after add_special_tokens."""
+    _dfa_check_table(table, n_states)
+    _dfa_check_n_words(n_words)
+    if not table.is_cuda:
+        raise ValueError("table must be on a GPU (dfa_table)")
+    n_words = dfa_n_words(tok) if n_words is None else int(n_words)
+    want = _ffi.SPL_DFA_INDEX_BYTES(int(n_states), n_words)
+    if out is None:
+        out = torch.empty(want, dtype=torch.uint8, device=table.device)           # (every word and every byte is written by the kernels)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.shape != (want,) or not out.is_contiguous() or out.device != table.device:
+        raise ValueError(f"out must be a contiguous uint8 tensor of shape [{want}] on the device of the table")
+    rc = _ffi.lib().spl_dfa_index_device(tok.handle, _ptr(table), int(n_states), n_words, _ptr(out), torch.cuda.current_stream(table.device).cuda_stream)
+    if rc != 0:
+        _raise_rc(rc, "spl_dfa_index_device")
+    return out
+
+
+def dfa_index_rows(index: torch.Tensor, n_states: int, n_words: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(rows int32 [n_states, stride], some uint8 [n_states]): views of an index."""
+    stride = (int(n_words) + 3) & ~3
+    cut = int(n_states) * stride * 4
+    return index[:cut].view(torch.int32).view(int(n_states), stride), index[cut:cut + int(n_states)]
+
+
+def dfa_step_device(tok: Tokenizer, ids: Optional[torch.Tensor], lengths: Optional[torch.Tensor], state: torch.Tensor, table: torch.Tensor,
+                    index: torch.Tensor, *, end_ids, n_states: Optional[int] = None, keep_free: bool = False, mask: Optional[torch.Tensor] = None,
+                    state_out: Optional[torch.Tensor] = None, live: Optional[torch.Tensor] = None, n_words: Optional[int] = None):
+    """The regex guide, one step (spl_dfa_step_device), on torch's current stream; nothing synchronises.  state int64 [B]: the words as
+    include/splintr_hip.h lays them out (dfa_state: the start states of sequences that begin); table: dfa_table(...); index:
+    dfa_index_device(...) with the same n_words; ids [B] or [B, K] int32 / int64: what the sampler drew (a sequence's first lengths[b]
+    entries count, all with lengths None); None: no ids, the masks of the state words as they are -- the first call after dfa_state.  An
+    ordinary id whose bytes the automaton can walk moves the state; an END id (end_ids: 1 .. 8 ids, usually specials) in an accepting
+    state ends the sequence (`done`); anything else breaks it (it runs free, `broken` set).  Returns (state_out int64 [B], mask int32
+    [B, n_words], live uint8 [B]: 1 where the sequence is constrained after the call).  state_out may be state.  keep_free: rows of
+    sequences that are not constrained after the call are not written -- pass the mask whose rows hold ones for them already.  n_states:
+    default, the table's; n_words: default dfa_n_words(tok), or mask's."""
+    if n_states is None:
+        if not isinstance(table, torch.Tensor) or table.dim() != 1 or table.shape[0] % 513:
+            raise ValueError("table must be a contiguous uint8 tensor of shape [n_states * 513] (dfa_table)")
+        n_states = int(table.shape[0]) // 513
+    if ids is None:
+        if not isinstance(state, torch.Tensor) or state.dim() != 1:
+            raise ValueError("state must be a contiguous int64 tensor of shape [batch]")
+        ids = torch.empty((state.shape[0], 0), dtype=torch.int32, device=state.device)
+    if mask is None and n_words is None:
+        n_words = dfa_n_words(tok)
+    check_dfa_args(ids, lengths, state, table, index, n_states, end_ids=end_ids, n_words=n_words, keep_free=keep_free, mask=mask, state_out=state_out)
+    dev = ids.device
+    B = int(ids.shape[0])
+    K = int(ids.shape[1]) if ids.dim() == 2 else 1
+    n_words = int(mask.shape[1]) if mask is not None else int(n_words)
+    ends = _dfa_end_ids(end_ids, n_words)
+    if mask is None:
+        mask = torch.empty((B, n_words), dtype=torch.int32, device=dev)          # (every word of every row is written by the kernel)
+    if state_out is None:
+        state_out = torch.empty(B, dtype=torch.int64, device=dev)
+    if live is None:
+        live = torch.empty(max(B, 1), dtype=torch.uint8, device=dev)[:B]
+    else:
+        _vec("live", live, B, (torch.uint8,), "uint8")
+    flags = (_ffi.SPL_DFA_KEEP_FREE if keep_free else 0) | (_ffi.SPL_DFA_I64 if ids.dtype == torch.int64 else 0)
+    # (null state and mask pointers are refused by the library: an empty batch passes addresses of its own, which nothing dereferences)
+    spare = torch.empty(8, dtype=torch.int64, device=dev).data_ptr() if B == 0 else 0
+    si = _ffi.SplDfaIn(B, K, _ptr(ids), _ptr(lengths), _ptr(state) or spare, _ptr(table), _ptr(index), int(n_states))
+    o = _ffi.SplDfaOpts(flags, n_words, ends)
+    so = _ffi.SplDfaOut(_ptr(state_out) or spare + 16, _ptr(mask) or spare + 32, _ptr(live))
+    rc = _ffi.lib().spl_dfa_step_device(tok.handle, ctypes.byref(si), ctypes.byref(o), ctypes.byref(so), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        _raise_rc(rc, "spl_dfa_step_device")
+    return state_out, mask, live
+
+
+class RegexGuide:
+    """`tokenizer.regex_guide(batch_size, pattern)`: "the answer matches this regular expression" for a batch whose state lives on the
+    GPU.  The pattern (or each of a list of patterns, stacked into one table) is compiled on the host by splintr_amd.dfa.compile_regex
+    -- Python `re` semantics in bytes mode, fullmatch -- and its state x vocabulary index is built on the GPU once.  begin(select) writes
+    the start states and the first masks; step(ids) follows the sampler; `mask` (int32 [B, n_words], the apply_token_bitmask layout)
+    always holds the ids the next step may draw -- all ones for a sequence that is free, done or broken.  A sequence is done when an END
+    id follows an accepting state.  UTF-8 validity of `.` and negated classes is not the guide's:
+    DeviceStreamingDecoder.allowed_mask(guide.mask, and_into=True) ANDs it in.  Nothing here synchronises."""
+
+    def __init__(self, tok: Tokenizer, batch_size: int, pattern_or_patterns, *, end_ids, n_words: Optional[int] = None):
+        from . import dfa as _dfa
+        if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)) or not 0 <= int(batch_size) < (1 << 31):
+            raise ValueError(f"batch_size must be an integer in 0 .. 2**31 - 1, not {batch_size!r}")
+        self._tok, self.batch_size = tok, int(batch_size)
+        self.n_words = dfa_n_words(tok) if n_words is None else int(n_words)
+        _dfa_check_n_words(self.n_words)
+        single = isinstance(pattern_or_patterns, (str, bytes, bytearray, _dfa.ByteDFA))
+        pats = [pattern_or_patterns] if single else list(pattern_or_patterns)
+        if not pats:
+            raise ValueError("at least one pattern is needed")
+        self.dfas = [p if isinstance(p, _dfa.ByteDFA) else _dfa.compile_regex(p) for p in pats]
+        self.dfa, self.starts = _dfa.stack(self.dfas)
+        self.n_states = self.dfa.n_states
+        self.end_ids = _dfa_end_ids(end_ids, self.n_words)
+        dev = torch.device("cuda", tok._device)
+        dfa_reserve(tok)
+        self.table = dfa_table(self.dfa, dev)
+        self.index = dfa_index_device(tok, self.table, self.n_states, n_words=self.n_words)
+        self.mask = torch.full((self.batch_size, self.n_words), -1, dtype=torch.int32, device=dev)
+        self._state = torch.zeros(self.batch_size, dtype=torch.int64, device=dev)
+        self.live = torch.zeros(self.batch_size, dtype=torch.uint8, device=dev)
+
+    def _call(self, ids, lengths, keep_free):
+        dfa_step_device(self._tok, ids, lengths, self._state, self.table, self.index, end_ids=self.end_ids, n_states=self.n_states,
+                        keep_free=keep_free, mask=self.mask, state_out=self._state, live=self.live)
+        return self.mask
+
+    def begin(self, select=None, rows=None) -> torch.Tensor:
+        """The start states of sequences that begin, and the first masks -> the mask.  select: None (every sequence: pattern 0), or per
+        sequence the index of its pattern (None: the sequence runs free).  rows: the sequences that begin (indices or a bool mask; select
+        then has one entry per such sequence); the others keep their state."""
+        dev = self._state.device
+
+        def words(sel, n):
+            sel = [0] * n if sel is None else list(sel)
+            if len(sel) != n:
+                raise ValueError(f"select must have one entry per sequence that begins ({n}), not {len(sel)}")
+            for b, p in enumerate(sel):
+                if p is not None and (isinstance(p, bool) or not isinstance(p, (int, np.integer)) or not 0 <= int(p) < len(self.starts)):
+                    raise ValueError(f"select {b} names pattern {p!r}: patterns are 0 .. {len(self.starts) - 1}")
+            return torch.from_numpy(_dfa_state_host([None if p is None else self.starts[int(p)] for p in sel])).to(dev)
+
+        if rows is None:
+            self._state.copy_(words(select, self.batch_size), non_blocking=True)
+        else:
+            idx = torch.as_tensor(rows, device=dev)
+            idx = idx.nonzero().flatten() if idx.dtype == torch.bool else idx.to(torch.int64).flatten()
+            self._state[idx] = words(select, int(idx.numel()))
+        return self._call(None, None, False)
+
+    def step(self, ids: Optional[torch.Tensor], lengths: Optional[torch.Tensor] = None, *, keep_free: bool = False) -> torch.Tensor:
+        """What the sampler drew, [B] or [B, K] (None: only the masks, after the caller wrote words into `state`) -> the mask.  keep_free:
+        the rows of sequences that are not constrained are not written again -- right once a step WITHOUT it has run after the last
+        sequence left its constraint (its row holds ones since then)."""
+        return self._call(ids, lengths, keep_free)
+
+    def reset(self, rows=None) -> None:
+        """All sequences (rows None) or the given ones (indices or a bool mask) free, their mask rows ones."""
+        if rows is None:
+            self._state.zero_(); self.mask.fill_(-1); self.live.zero_()
+        else:
+            self._state[rows] = 0
+            self.mask[rows] = -1
+            self.live[rows] = 0
+
+    def apply(self, logits: torch.Tensor, *, live_only: bool = False) -> torch.Tensor:
+        """logits [B, V] (float32, float16 or bfloat16) with -inf wherever the mask forbids the id, IN PLACE: one launch of
+        mask_apply_device.  live_only: the rows of sequences that are not constrained (`live` 0) are skipped -- their mask rows hold ones,
+        so the result is the same."""
+        if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.shape[0] != self.batch_size:
+            raise ValueError("logits must have shape [batch, vocabulary]")
+        return mask_apply_device(self._tok, logits, self.mask, live=self.live if live_only else None)
+
+    @property
+    def state(self) -> torch.Tensor:
+        """int64 [B] on the device, as include/splintr_hip.h lays it out (the guide's own tensor: a word written here counts)"""
+        return self._state
+
+    @property
+    def q(self) -> torch.Tensor:
+        """int64 [B] on the device: the automaton's state of a constrained or done sequence (in the stacked table)"""
+        return self._state & 0xFFFF
+
+    @property
+    def broken(self) -> torch.Tensor:
+        return ((self._state >> 17) & 1).bool()
+
+    @property
+    def done(self) -> torch.Tensor:
+        return ((self._state >> 18) & 1).bool()
+
+    def __repr__(self) -> str:
+        return f"RegexGuide(batch_size={self.batch_size}, patterns={len(self.dfas)}, n_states={self.n_states}, n_words={self.n_words})"
+
+
 class Comm:
     """One rank of the library's own RCCL communicator (include/splintr_hip.h: spl_comm_*).  The 128-byte id is
     made by rank 0 and handed to the others by whatever the caller has; `from_torch_group` uses an existing
