@@ -149,6 +149,8 @@ uint32_t spl_n_devices(const spl_tokenizer* t);
  *                            beyond (0: always three; profiles/stop_match.txt has the measured crossing)
  *   "heal_phase"             0..2 (0): measuring only -- 1: spl_heal_begin_device / spl_heal_step_device launch their plan alone, 2: their fill
  *                            alone, over the scratch the last plan left (profiles/token_mask.txt)
+ *   "jump_phase"             0..3 (0): measuring only -- spl_dfa_jump_index_device returns behind 1: force and runs, 2: the compaction
+ *                            and the read-back of its total, 3: the encode; the jump index is then incomplete (profiles/dfa_jump.txt)
  *   "slab_pack24"            0/1 (0): the ids of the all-gather slabs travel three bytes each; every rank alike; refused (SPL_EINVAL) when an
  *                            id of the tokenizer -- vocabulary or special token -- does not fit 24 bits
  * Unknown names and values out of range: SPL_EINVAL. */
@@ -1279,6 +1281,68 @@ typedef struct spl_dfa_out {
 int spl_dfa_reserve_device(spl_tokenizer* t);
 int spl_dfa_index_device(spl_tokenizer* t, const uint8_t* d_table, uint32_t n_states, uint32_t n_words, int32_t* d_index, void* hip_stream);
 int spl_dfa_step_device(spl_tokenizer* t, const spl_dfa_in* in, const spl_dfa_opts* o, const spl_dfa_out* out, void* hip_stream);
+
+/* JUMP-FORWARD for the regex guide (csrc/spl_k_dfa_jump.h).  Where the automaton leaves no choice -- the fixed keys
+ * and punctuation of a JSON object, the tags of a tool call -- the forced bytes are handed back AS IDS and cost no forward pass of the
+ * model.  A forced run is a function of the state alone, so the runs of all n_states states are found on the GPU when the jump index
+ * is built and are encoded once by this handle's own encoder; a decode step is then a row gather of ids beside the mask: no encode,
+ * no trie on the host, no synchronisation.  walk, DEAD, ORDINARY, b(t) and the state word are spl_dfa_step_device's.
+ *
+ * FORCED BYTE.  force(q) = x iff accept[q] == 0 and exactly one byte x has trans[q][x] < n_states.  An accepting state is never forced:
+ * an END id may follow it.  Like the index, this does not depend on the END ids.
+ * RUN.  run(q) is the bytes x1 x2 ... with q1 = q and q(i+1) = trans[qi][xi], continued while force(qi) is defined, and capped at
+ * SPL_DFA_JUMP_MAX_BYTES bytes (a table need not be trimmed: the cap also ends cycles).
+ * UTF-8 TRIM.  After the cap the run is cut back to a character boundary of its own bytes: if it ends in a lead byte (>= 0xC0; C0..DF
+ * announce one continuation byte, E0..EF two, F0..FF three) with fewer continuation bytes (80..BF) behind it than it announces, the run
+ * is cut in front of that lead byte.  Leading continuation bytes stay: they finish a character begun before the run.  Example: (é|è)x
+ * forces C3 from the start state; after the trim that run is empty -- without it the model could no longer draw the token "é".
+ *
+ * THE JUMP INDEX (SPL_DFA_JUMP_INDEX_BYTES(n_states) of device memory, the CALLER's, 4-byte aligned), written by
+ * spl_dfa_jump_index_device: uint32 ids[n_states][64], then uint8 n_ids[n_states], then uint8 run_len[n_states], then uint8
+ * run[n_states][64].  run[q][0 .. run_len[q]) is run(q); ids[q][0 .. n_ids[q]) are the ids of run(q) encoded as a text of its own by
+ * this handle's encoder, with flags 0 and no specials; n_ids[q] == 0 iff the run is empty.  Every byte of the region is written, zeros
+ * where nothing is meant.  Build it again after spl_add_special.
+ *
+ * JUMP STEP (spl_dfa_jump_device).  Everything spl_dfa_step_device does, from the same spl_dfa_in and spl_dfa_opts, and between the walk
+ * of the sampler's ids and the mask: for a sequence still constrained in state q, n = min(n_ids[q], 64, row_len_out); the leading ids of
+ * ids[q][0 .. n) are emitted for as long as each is ordinary and walks -- the first id that does not walk ends the emission and does NOT
+ * break the sequence; q moves along what was emitted.  The emitted ids go to d_forced_ids[b][0 .. m) (int32 [n_seqs, row_len_out],
+ * row_len_out in 1 .. 64) and m to d_forced_len[b]; entries at and beyond m are not written.  The mask, live, done, broken and the
+ * empty-row break are spl_dfa_step_device's, for the state arrived at.  A sequence that is free, done or broken gets d_forced_len 0.
+ * The kernel trusts nothing in the jump index: it walks what it emits and never indexes outside a table, whatever the index holds.
+ * With every n_ids zero the call is spl_dfa_step_device bit for bit.
+ *
+ * What it is NOT: the ids are those of the run encoded ALONE -- the seam with the text in front of it is not re-tokenised (the known
+ * caveat of jump-forward; spl_heal_*_device heals a seam, composing the two is the caller's).  A state that is still forced after a
+ * jump (a run above 64 bytes, or row_len_out below n_ids[q]) is continued by the next call.
+ *
+ * SHAPE.  spl_dfa_jump_index_device is BUILD-TIME work: a wavefront per state finds the forced byte (the 512-byte row eight bytes a
+ * lane, ballots and a popcount); a second launch follows the chains of at most 64 forced bytes and trims them; the runs are compacted
+ * into a bytes CSR of n_states documents by the count-scan-write driver; the call then reads the runs' total bytes back -- its ONE
+ * host synchronisation of hip_stream, because spl_encode_batch_device takes n_bytes from the host (a handle with SPL_PATTERN_CUSTOM
+ * synchronises once more inside that encode, as every device encode of such a handle does) -- reserves workspace as needed and
+ * encodes the documents through the handle's device encode path (the chunk memo may take the runs' chunks in, as after any encode; it
+ * shares the handle's workspace with every other encode call: stream-ordered, as those); a last launch scatters the ids CSR into
+ * ids[][] and n_ids[].  This call may ALLOCATE and SYNCHRONISES.  spl_dfa_jump_device does neither after spl_dfa_reserve_device: ONE
+ * launch, a wavefront per sequence, no LDS, no scratch, no atomics on global memory, no polling.
+ *
+ * SPL_EINVAL, with the cause in spl_last_error() and before anything touches the device: a null handle; row_len_out 0 or above 64; a
+ * null or misaligned d_forced_ids, d_forced_len or d_jump_index; a null jump struct or a struct_size shorter than it; d_forced_ids or
+ * d_forced_len coinciding with any other array of the call; everything spl_dfa_step_device refuses. */
+#define SPL_DFA_JUMP_MAX_BYTES 64
+#define SPL_DFA_JUMP_MAX_IDS   64
+#define SPL_DFA_JUMP_INDEX_BYTES(n_states) ((size_t)(n_states) * (64 * 4 + 1 + 1 + 64))
+
+typedef struct spl_dfa_jump_out {
+    uint32_t struct_size, row_len_out;    /* row_len_out: the columns of d_forced_ids, 1 .. SPL_DFA_JUMP_MAX_IDS */
+    const void* d_jump_index;             /* SPL_DFA_JUMP_INDEX_BYTES(n_states), as spl_dfa_jump_index_device left it */
+    int32_t* d_forced_ids;                /* [n_seqs, row_len_out] */
+    int32_t* d_forced_len;                /* [n_seqs] */
+} spl_dfa_jump_out;
+
+int spl_dfa_jump_index_device(spl_tokenizer* t, const uint8_t* d_table, uint32_t n_states, void* d_jump_index, void* hip_stream);
+int spl_dfa_jump_device(spl_tokenizer* t, const spl_dfa_in* in, const spl_dfa_opts* o, const spl_dfa_out* out, const spl_dfa_jump_out* jump,
+                        void* hip_stream);
 
 /* Host-side lookup of ONE id, for consumers that decode token by token on the CPU -- the streaming
  * decoders (src/core/streaming.rs, src/python/bindings.rs:465-834 take clones of Tokenizer::decoder

@@ -36,7 +36,7 @@ SYMBOLS = [
     "spl_heal_reserve_device", "spl_heal_begin_device", "spl_heal_step_device",
     "spl_utf8_mask_reserve_device", "spl_utf8_mask_device", "spl_mask_apply_device",
     "spl_choice_reserve_device", "spl_choice_step_device",
-    "spl_dfa_reserve_device", "spl_dfa_index_device", "spl_dfa_step_device",
+    "spl_dfa_reserve_device", "spl_dfa_index_device", "spl_dfa_step_device", "spl_dfa_jump_index_device", "spl_dfa_jump_device",
 ]
 SPL_PATTERN_CUSTOM = 3
 SPL_OPT_BYTE_LEVEL = 1
@@ -59,10 +59,15 @@ SPL_CHOICE_THEN_FREE, SPL_CHOICE_KEEP_FREE, SPL_CHOICE_I64 = 1, 2, 4
 SPL_CHOICE_SLOTS, SPL_CHOICE_MAX_LEN, SPL_CHOICE_TABLE_BYTES, SPL_CHOICE_STATE_WORDS, SPL_CHOICE_MAX_END = 64, 64, 64 * 64 + 64, 2, 8
 SPL_DFA_KEEP_FREE, SPL_DFA_I64 = 2, 4
 SPL_DFA_DEAD, SPL_DFA_MAX_STATES, SPL_DFA_STATE_WORDS, SPL_DFA_MAX_END = 0xFFFF, 4096, 1, 8
+SPL_DFA_JUMP_MAX_BYTES, SPL_DFA_JUMP_MAX_IDS = 64, 64
 
 
 def SPL_DFA_TABLE_BYTES(n_states: int) -> int:
     return n_states * 512 + n_states
+
+
+def SPL_DFA_JUMP_INDEX_BYTES(n_states: int) -> int:
+    return n_states * (64 * 4 + 1 + 1 + 64)
 
 
 def SPL_DFA_INDEX_BYTES(n_states: int, n_words: int) -> int:
@@ -256,6 +261,15 @@ class SplDfaOut(ctypes.Structure):
         super().__init__(ctypes.sizeof(SplDfaOut), 0, state, mask, live)
 
 
+class SplDfaJumpOut(ctypes.Structure):
+    """spl_dfa_jump_out: the jump index and where the emitted ids and their counts go, device addresses."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("row_len_out", ctypes.c_uint32), ("d_jump_index", ctypes.c_void_p), ("d_forced_ids", ctypes.c_void_p),
+                ("d_forced_len", ctypes.c_void_p)]
+
+    def __init__(self, row_len_out=0, jump_index=None, forced_ids=None, forced_len=None):
+        super().__init__(ctypes.sizeof(SplDfaJumpOut), row_len_out, jump_index, forced_ids, forced_len)
+
+
 _lib = None
 
 
@@ -392,6 +406,8 @@ def lib() -> ctypes.CDLL:
     L.spl_dfa_reserve_device.argtypes = [vp]
     L.spl_dfa_index_device.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
     L.spl_dfa_step_device.argtypes = [vp, ctypes.POINTER(SplDfaIn), ctypes.POINTER(SplDfaOpts), ctypes.POINTER(SplDfaOut), vp]
+    L.spl_dfa_jump_index_device.argtypes = [vp, vp, ctypes.c_uint32, vp, vp]
+    L.spl_dfa_jump_device.argtypes = [vp, ctypes.POINTER(SplDfaIn), ctypes.POINTER(SplDfaOpts), ctypes.POINTER(SplDfaOut), ctypes.POINTER(SplDfaJumpOut), vp]
     _lib = L
     return L
 

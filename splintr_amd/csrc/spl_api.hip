@@ -1,7 +1,7 @@
 // spl_api.hip -- the C ABI (include/splintr_hip.h): the root of the library's one HIP translation unit.  It includes the kernels
 // (spl_kernels.hip) and the host side, one file per concern and each building on the ones before it -- spl_host_res.h (resource owners,
 // pinned pool), spl_ctx.h (per-GPU context, handle, uploads), spl_streams.h (stream probe), spl_launch.h (memo, launch order, device
-// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_pair_host.h, spl_chat_host.h, spl_seqpack_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h, spl_seqscan_host.h, spl_stream_host.h, spl_stop_host.h, spl_heal_host.h, spl_mask_host.h, spl_choice_host.h, spl_dfa_host.h -- and holds the entry points.
+// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_pair_host.h, spl_chat_host.h, spl_seqpack_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h, spl_seqscan_host.h, spl_stream_host.h, spl_stop_host.h, spl_heal_host.h, spl_mask_host.h, spl_choice_host.h, spl_dfa_host.h, spl_dfa_jump_host.h -- and holds the entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -53,6 +53,7 @@ using namespace spl;
 #include "spl_mask_host.h"
 #include "spl_choice_host.h"
 #include "spl_dfa_host.h"
+#include "spl_dfa_jump_host.h"
 
 namespace {
 // No exception crosses the C ABI: every entry point that allocates (std::bad_alloc), starts threads or grows
@@ -164,6 +165,7 @@ int spl_set_option(spl_tokenizer* t, const char* name, int64_t value) {
     else if (k == "stream_one_max" && value >= 0 && value <= (int64_t)ST_ONE_MAX) t->stream_one_max = (uint32_t)value;
     else if (k == "stop_one_max" && value >= 0 && value <= (int64_t)SP_ONE_MAX) t->stop_one_max = (uint32_t)value;
     else if (k == "heal_phase" && value >= 0 && value <= 2) t->heal_phase = (uint32_t)value;
+    else if (k == "jump_phase" && value >= 0 && value <= 3) t->jump_phase = (uint32_t)value;
     else if (k == "choice_piece_words" && value >= 4 && value <= (int64_t)CH_PIECE && value % 4 == 0) t->choice_piece = (uint32_t)value;
     else if (k == "slab_pack24") {
         if (value && std::max(t->ht.max_id, t->max_special_id) >= (1u << 24))
@@ -186,7 +188,7 @@ int spl_get_option(const spl_tokenizer* t, const char* name, int64_t* value) {
         {"memo_log_cap", t->memo_log_cap}, {"fuse_max_tiles", t->fuse_max_tiles}, {"copy_threads", t->copy_threads},
         {"decode_chunk_ids", (int64_t)t->dec_chunk_ids}, {"sdma_d2h", t->sdma_d2h}, {"window_totals_chunk", t->win_chunk},
         {"seqpack_lds_max", t->seqpack_lds_max},
-        {"stream_one_max", t->stream_one_max}, {"stop_one_max", t->stop_one_max}, {"heal_phase", t->heal_phase},
+        {"stream_one_max", t->stream_one_max}, {"stop_one_max", t->stop_one_max}, {"heal_phase", t->heal_phase}, {"jump_phase", t->jump_phase},
         {"choice_piece_words", t->choice_piece},
         {"slab_pack24", t->slab_pack24},
     };
@@ -515,6 +517,14 @@ int spl_dfa_index_device(spl_tokenizer* t, const uint8_t* d_table, uint32_t n_st
 
 int spl_dfa_step_device(spl_tokenizer* t, const spl_dfa_in* in, const spl_dfa_opts* o, const spl_dfa_out* out, void* hip_stream) {
     return guarded("spl_dfa_step_device", [&] { return dfa_step_device(t, in, o, out, (hipStream_t)hip_stream); });
+}
+
+int spl_dfa_jump_index_device(spl_tokenizer* t, const uint8_t* d_table, uint32_t n_states, void* d_jump_index, void* hip_stream) {
+    return guarded("spl_dfa_jump_index_device", [&] { return dfa_jump_index_device(t, d_table, n_states, d_jump_index, (hipStream_t)hip_stream); });
+}
+
+int spl_dfa_jump_device(spl_tokenizer* t, const spl_dfa_in* in, const spl_dfa_opts* o, const spl_dfa_out* out, const spl_dfa_jump_out* jump, void* hip_stream) {
+    return guarded("spl_dfa_jump_device", [&] { return dfa_jump_device(t, in, o, out, jump, (hipStream_t)hip_stream); });
 }
 
 int spl_utf8_mask_reserve_device(spl_tokenizer* t) {

@@ -72,6 +72,7 @@ struct Ctx {
     DevBuf<uint32_t> d_heal_sorted, d_heal_rank, d_heal_parent; uint32_t heal_n = 0;   // spl_heal_*_device: the ordinary ids by their bytes, id -> rank, the prefix order (upload_heal; rebuilt after spl_add_special)
     bool heal_uploaded = false;
     DevBuf<uint32_t> d_heal_scr; uint64_t heal_cap = 0;   // ... lo, hi and up to 63 partial ids per sequence, 264 bytes each (grow-only; shared with nothing)
+    DevBuf<uint64_t> d_jmscr; uint64_t jmscr_cap = 0;   // spl_dfa_jump_index_device: the runs' bytes CSR, their ids CSR and the scan's sums, 344 bytes per state (grow-only; shared with nothing)
     DevBuf<uint32_t> d_u8_present, d_u8_rows; uint32_t u8_stride = 0;   // spl_utf8_mask_device: the vocabulary proper as a bit per id, the class table's 17 rows of u8_stride words (upload_utf8; rebuilt after spl_add_special)
     bool u8_uploaded = false;
     DevBuf<uint8_t> d_sp_lits;                 // uploaded lazily; invalidated by spl_add_special
@@ -219,6 +220,7 @@ struct spl_tokenizer {
     uint32_t stream_one_max = ST_ONE_DEFAULT;    // "stream_one_max": most sequences spl_stream_decode_device takes in its one-launch form
     uint32_t choice_piece = CH_PIECE;            // "choice_piece_words": tests and measuring only -- the words of a mask row spl_choice_step_device builds in LDS at once
     uint32_t heal_phase = 0;                     // "heal_phase": measuring only -- 1 the healing calls launch their plan alone, 2 their fill alone (over the scratch the last plan left)
+    uint32_t jump_phase = 0;                     // "jump_phase": measuring only -- spl_dfa_jump_index_device returns behind 1 force and runs, 2 the compaction and its read-back, 3 the encode (the index is then incomplete)
     uint32_t stop_one_max = SP_ONE_DEFAULT;      // "stop_one_max": most sequences spl_stop_match_device takes in its one-launch form
     uint32_t seqpack_lds_max = SQP_LDS_MAX;  // "seqpack_lds_max" (tests): most sequences whose plan arrays spl_seqpack_device keeps in LDS, so that a few hundred reach the work-buffer form
     uint32_t win_chunk = WIN_CHUNK;          // "window_totals_chunk" (tests): span totals k_window_totals scans per round, so that a few thousand documents reach its second round

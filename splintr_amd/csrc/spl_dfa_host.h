@@ -18,12 +18,17 @@ int dfa_reserve_device(spl_tokenizer* t) {
     return upload_heal(t, c);
 }
 
-// what both calls ask of a table and a row width
-int dfa_refuse_shape(const spl_tokenizer* t, const std::string& who, const uint8_t* d_table, uint32_t n_states, uint32_t n_words) {
+// what every call asks of a table
+int dfa_refuse_table(const std::string& who, const uint8_t* d_table, uint32_t n_states) {
     if (!d_table) return fail(SPL_EINVAL, who + ": d_table is null");
     if (col_misaligned(d_table, 2)) return fail(SPL_EINVAL, who + ": d_table is not 2-byte aligned (uint16 transitions)");
     if (!n_states || n_states > SPL_DFA_MAX_STATES)
         return fail(SPL_EINVAL, who + ": n_states is " + std::to_string(n_states) + ", not in 1 .. SPL_DFA_MAX_STATES (4096)");
+    return SPL_OK;
+}
+// what the index and the steps ask of a table and a row width
+int dfa_refuse_shape(const spl_tokenizer* t, const std::string& who, const uint8_t* d_table, uint32_t n_states, uint32_t n_words) {
+    SPL_TRY(dfa_refuse_table(who, d_table, n_states));
     const uint32_t max_id = t->ht.max_id;
     if ((uint64_t)n_words * 32 < (uint64_t)max_id + 1)
         return fail(SPL_EINVAL, who + ": n_words is too small: " + std::to_string(n_words) + " words for ids up to " + std::to_string(max_id));
@@ -61,8 +66,8 @@ int dfa_index_device(spl_tokenizer* t, const uint8_t* d_table, uint32_t n_states
     return SPL_OK;
 }
 
-int dfa_step_device(spl_tokenizer* t, const spl_dfa_in* in, const spl_dfa_opts* o, const spl_dfa_out* out, hipStream_t st) {
-    const std::string who = "spl_dfa_step_device";
+// everything spl_dfa_step_device refuses (spl_dfa_jump_device refuses the same, under its own name)
+int dfa_refuse_step(const spl_tokenizer* t, const std::string& who, const spl_dfa_in* in, const spl_dfa_opts* o, const spl_dfa_out* out) {
     if (!t) return fail(SPL_EINVAL, who + ": null handle");
     if (!in) return fail(SPL_EINVAL, who + ": the input struct is null");
     if (!o) return fail(SPL_EINVAL, who + ": the options are null");
@@ -98,21 +103,37 @@ int dfa_step_device(spl_tokenizer* t, const spl_dfa_in* in, const spl_dfa_opts* 
     for (uint32_t i = 0; i < o->n_end; i++)
         if ((uint64_t)o->end_ids[i] >= (uint64_t)o->n_words * 32)
             return fail(SPL_EINVAL, who + ": END id " + std::to_string(o->end_ids[i]) + " is at or above 32 * n_words");
+    return SPL_OK;
+}
 
+// the kernels' arguments of a step that passed dfa_refuse_step
+DfIndex dfa_index_of(const spl_dfa_in* in, const spl_dfa_opts* o) {
+    const uint32_t stride = df_stride(o->n_words);
+    return DfIndex{reinterpret_cast<const uint32_t*>(in->d_index), reinterpret_cast<const uint8_t*>(in->d_index) + (size_t)in->n_states * stride * 4, stride};
+}
+DfIn dfa_in_of(const spl_dfa_in* in, const spl_dfa_opts* o, const spl_dfa_out* out) {
+    DfIn a{};
+    a.ids = in->d_ids; a.len = in->d_len; a.state_in = in->d_state_in; a.n_seqs = in->n_seqs;
+    a.row_len = in->row_len; a.flags = o->flags; a.n_words = o->n_words;
+    a.v4 = o->n_words % 4 == 0 && !col_misaligned(out->d_mask, 16) && !col_misaligned(in->d_index, 16) ? 1u : 0u;
+    a.n_end = o->n_end;
+    for (uint32_t i = 0; i < o->n_end; i++) a.end_ids[i] = o->end_ids[i];
+    return a;
+}
+DfOut dfa_out_of(const spl_dfa_opts* o, const spl_dfa_out* out) {
+    return DfOut{out->d_state_out, reinterpret_cast<uint32_t*>(out->d_mask), out->d_live, o->n_words};
+}
+
+int dfa_step_device(spl_tokenizer* t, const spl_dfa_in* in, const spl_dfa_opts* o, const spl_dfa_out* out, hipStream_t st) {
+    SPL_TRY(dfa_refuse_step(t, "spl_dfa_step_device", in, o, out));
     Ctx* c = t->ctx[0].get();
     HIP_TRY(hipSetDevice(c->device));
     SPL_TRY(upload_heal(t, c));
     const uint64_t B = in->n_seqs;
     if (!B) return SPL_OK;
-    const uint32_t stride = df_stride(o->n_words);
-    const DfIndex x{reinterpret_cast<const uint32_t*>(in->d_index), reinterpret_cast<const uint8_t*>(in->d_index) + (size_t)in->n_states * stride * 4, stride};
-    DfIn a{};
-    a.ids = in->d_ids; a.len = in->d_len; a.state_in = in->d_state_in; a.n_seqs = B;
-    a.row_len = in->row_len; a.flags = o->flags; a.n_words = o->n_words;
-    a.v4 = o->n_words % 4 == 0 && !col_misaligned(out->d_mask, 16) && !col_misaligned(in->d_index, 16) ? 1u : 0u;
-    a.n_end = o->n_end;
-    for (uint32_t i = 0; i < o->n_end; i++) a.end_ids[i] = o->end_ids[i];
-    const DfOut co{out->d_state_out, reinterpret_cast<uint32_t*>(out->d_mask), out->d_live, o->n_words};
+    const DfIndex x = dfa_index_of(in, o);
+    const DfIn a = dfa_in_of(in, o, out);
+    const DfOut co = dfa_out_of(o, out);
     const uint32_t gy = (uint32_t)std::min<uint64_t>(B, 65535), gz = (uint32_t)((B + gy - 1) / gy);
     hipLaunchKernelGGL(k_dfa_step, dim3(1, gy, gz), dim3(DF_WAVE), 0, st, a, dfa_hl_tab(c), dfa_tab(in->d_table, in->n_states), x, co);
     HIP_TRY(hipGetLastError());

@@ -162,7 +162,17 @@ SPL_HD uint64_t df_word(const DfState& s) {
     if (s.done) return (uint64_t)s.q | DF_DONE;
     return s.con ? ((uint64_t)s.q | DF_CON) : 0ull;
 }
-// the row's valid ids in order, while the sequence is constrained (the same for every lane: a serial walk)
+// one id of a constrained sequence: an ordinary id that walks moves q; an END id behind an accepting state ends the sequence; anything else breaks it
+SPL_HD void df_step_id(const HlTab& t, const DfTab& d, const DfIn& a, uint32_t id, bool is_id, DfState& s) {
+    uint32_t tl = 0;
+    const uint8_t* tb = is_id ? df_bytes(t, id, tl) : nullptr;
+    const uint32_t q1 = tb ? df_walk_from(d, s.q, tb, 0u, tl) : DF_DEAD;
+    if (q1 != DF_DEAD) { s.q = q1; return; }
+    s.con = false;
+    if (is_id && df_is_end(a, id) && df_ends(d, s.q)) s.done = true;
+    else { s.broken = true; s.q = 0; }
+}
+// THE WALK: the row's valid ids in order, while the sequence is constrained (the same for every lane: a serial walk)
 SPL_HD void df_step_seq(const HlTab& t, const DfTab& d, const DfIn& a, uint64_t b, DfState& s) {
     const uint32_t n = df_row_n(a, b);
     for (uint32_t i = 0; i < n && s.con; i++) {
@@ -171,13 +181,7 @@ SPL_HD void df_step_seq(const HlTab& t, const DfTab& d, const DfIn& a, uint64_t 
             const uint64_t v = static_cast<const uint64_t*>(a.ids)[b * a.row_len + i];
             is_id = (v >> 32) == 0; id = (uint32_t)v;
         } else id = static_cast<const uint32_t*>(a.ids)[b * a.row_len + i];
-        uint32_t tl = 0;
-        const uint8_t* tb = is_id ? df_bytes(t, id, tl) : nullptr;
-        const uint32_t q1 = tb ? df_walk_from(d, s.q, tb, 0u, tl) : DF_DEAD;
-        if (q1 != DF_DEAD) { s.q = q1; continue; }
-        s.con = false;
-        if (is_id && df_is_end(a, id) && df_ends(d, s.q)) s.done = true;
-        else { s.broken = true; s.q = 0; }
+        df_step_id(t, d, a, id, is_id, s);
     }
 }
 // the END bits that fall into word k
@@ -188,16 +192,17 @@ SPL_HD uint32_t df_end_bits(const DfIn& a, uint32_t k) {
     return v;
 }
 
-// everything of sequence b: the transition, the state row, live and the mask row.  put(b, word, value) and put4(b, word, four values) store.
-template <class W, class O> SPL_HD void df_seq(W& w, const HlTab& t, const DfTab& d, const DfIndex& x, const DfIn& a, uint64_t b, const O& out) {
+// THE SETTLE: the state a call leaves behind the state it arrived at -- a constrained state with nothing to draw breaks.  Returns whether
+// the END bits belong into the row.
+SPL_HD bool df_settle(const DfTab& d, const DfIndex& x, const DfIn& a, DfState& s) {
+    if (!s.con) return false;
+    const bool ends = a.n_end != 0 && df_ends(d, s.q);
+    if (!ends && !x.some[s.q]) { s.con = false; s.broken = true; s.q = 0; }       // nothing to draw: the sequence breaks, its row is ones
+    return ends;
+}
+// THE ROW WRITE: the state row, live and the mask row of a settled state.  put(b, word, value) and put4(b, word, four values) store.
+template <class W, class O> SPL_HD void df_write(W& w, const DfIndex& x, const DfIn& a, uint64_t b, const DfState& s, bool ends, const O& out) {
     const uint32_t L = w.lanes();
-    DfState s = df_load(d, a.state_in[b]);                                     // (state_out may be state_in: the row is read here, written once below)
-    df_step_seq(t, d, a, b, s);
-    bool ends = false;
-    if (s.con) {
-        ends = a.n_end != 0 && df_ends(d, s.q);
-        if (!ends && !x.some[s.q]) { s.con = false; s.broken = true; s.q = 0; }   // nothing to draw: the sequence breaks, its row is ones
-    }
     const uint64_t word = df_word(s);
     w.each([&](uint32_t l) { if (l == 0) { out.state(b, word); out.alive(b, s.con ? 1u : 0u); } });
     if (!s.con) {
@@ -223,6 +228,13 @@ template <class W, class O> SPL_HD void df_seq(W& w, const HlTab& t, const DfTab
             for (uint32_t i = l; i < a.n_words; i += L) out.put(b, i, row[i] | (ends ? df_end_bits(a, i) : 0u));
         }
     });
+}
+// everything of sequence b: the walk, the settle and the row write (spl_k_dfa_jump.h puts the jump between the first two)
+template <class W, class O> SPL_HD void df_seq(W& w, const HlTab& t, const DfTab& d, const DfIndex& x, const DfIn& a, uint64_t b, const O& out) {
+    DfState s = df_load(d, a.state_in[b]);                                     // (state_out may be state_in: the row is read here, written once below)
+    df_step_seq(t, d, a, b, s);
+    const bool ends = df_settle(d, x, a, s);
+    df_write(w, x, a, b, s, ends, out);
 }
 
 #if defined(__HIPCC__)

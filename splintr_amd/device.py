@@ -1888,6 +1888,115 @@ def dfa_step_device(tok: Tokenizer, ids: Optional[torch.Tensor], lengths: Option
     return state_out, mask, live
 
 
+def dfa_jump_index_device(tok: Tokenizer, table: torch.Tensor, n_states: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The jump index of a DFA table (spl_dfa_jump_index_device): the forced byte run of every state, found on the GPU and encoded once by
+    this tokenizer's own encoder, on torch's current stream.  BUILD-TIME work: the call may allocate and synchronises the stream once.
+    Returns uint8 [n_states * 322]: int32 ids[n_states][64], uint8 n_ids[n_states], uint8 run_len[n_states], uint8 run[n_states][64]
+    (dfa_jump_index_views gives the four views).  Build it again after add_special_tokens."""
+    _dfa_check_table(table, n_states)
+    if not table.is_cuda:
+        raise ValueError("table must be on a GPU (dfa_table)")
+    want = _ffi.SPL_DFA_JUMP_INDEX_BYTES(int(n_states))
+    if out is None:
+        out = torch.empty(want, dtype=torch.uint8, device=table.device)           # (every byte is written by the kernels)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.shape != (want,) or not out.is_contiguous() or out.device != table.device:
+        raise ValueError(f"out must be a contiguous uint8 tensor of shape [{want}] on the device of the table")
+    rc = _ffi.lib().spl_dfa_jump_index_device(tok.handle, _ptr(table), int(n_states), _ptr(out), torch.cuda.current_stream(table.device).cuda_stream)
+    if rc != 0:
+        _raise_rc(rc, "spl_dfa_jump_index_device")
+    return out
+
+
+def dfa_jump_index_views(index: torch.Tensor, n_states: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(ids int32 [n_states, 64], n_ids uint8 [n_states], run_len uint8 [n_states], run uint8 [n_states, 64]): views of a jump index (a
+    tensor on the host or on the device whose storage is 4-byte aligned)."""
+    S = int(n_states)
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.uint8 or index.shape != (_ffi.SPL_DFA_JUMP_INDEX_BYTES(S),) or not index.is_contiguous():
+        raise ValueError(f"the jump index must be a contiguous uint8 tensor of shape [{_ffi.SPL_DFA_JUMP_INDEX_BYTES(S)}] (dfa_jump_index_device)")
+    return index[:256 * S].view(torch.int32).view(S, 64), index[256 * S:257 * S], index[257 * S:258 * S], index[258 * S:].view(S, 64)
+
+
+def check_dfa_jump_args(ids, lengths, state, table, index, jump_index, n_states, *, end_ids=None, n_words=None, keep_free: bool = False, mask=None,
+                        state_out=None, forced_ids=None, forced_len=None, row_len_out=None) -> None:
+    """ValueError for whatever dfa_jump_device would refuse -- check_dfa_args, and the jump index, the rows of emitted ids and their
+    width -- before anything goes to the device."""
+    check_dfa_args(ids, lengths, state, table, index, n_states, end_ids=end_ids, n_words=n_words, keep_free=keep_free, mask=mask, state_out=state_out)
+    B = int(ids.shape[0])
+    want = _ffi.SPL_DFA_JUMP_INDEX_BYTES(int(n_states))
+    if not isinstance(jump_index, torch.Tensor) or jump_index.dtype != torch.uint8 or jump_index.shape != (want,) or not jump_index.is_contiguous():
+        raise ValueError(f"jump_index must be a contiguous uint8 tensor of shape [{want}] (dfa_jump_index_device with the same n_states)")
+    if jump_index.device != ids.device:
+        raise ValueError("jump_index must be on the device of the ids")
+    if forced_ids is not None:
+        if not isinstance(forced_ids, torch.Tensor) or forced_ids.dtype != torch.int32 or forced_ids.dim() != 2 or forced_ids.shape[0] != B or \
+                not forced_ids.is_contiguous() or forced_ids.device != ids.device:
+            raise ValueError("forced_ids must be a contiguous int32 tensor of shape [batch, row_len_out] on the device of the ids")
+        if row_len_out is not None and int(row_len_out) != int(forced_ids.shape[1]):
+            raise ValueError("row_len_out must be the width of forced_ids")
+        row_len_out = int(forced_ids.shape[1])
+    if isinstance(row_len_out, bool) or not isinstance(row_len_out, (int, np.integer)) or not 1 <= int(row_len_out) <= _ffi.SPL_DFA_JUMP_MAX_IDS:
+        raise ValueError(f"row_len_out (the width of forced_ids) must be an integer in 1 .. {_ffi.SPL_DFA_JUMP_MAX_IDS}, not {row_len_out!r}")
+    if forced_len is not None:
+        if _vec("forced_len", forced_len, B, (torch.int32,), "int32")[1].device != ids.device:
+            raise ValueError("forced_len must be on the device of the ids")
+
+
+def dfa_jump_device(tok: Tokenizer, ids: Optional[torch.Tensor], lengths: Optional[torch.Tensor], state: torch.Tensor, table: torch.Tensor,
+                    index: torch.Tensor, jump_index: torch.Tensor, *, end_ids, n_states: Optional[int] = None, keep_free: bool = False,
+                    mask: Optional[torch.Tensor] = None, state_out: Optional[torch.Tensor] = None, live: Optional[torch.Tensor] = None,
+                    n_words: Optional[int] = None, forced_ids: Optional[torch.Tensor] = None, forced_len: Optional[torch.Tensor] = None,
+                    row_len_out: Optional[int] = None):
+    """The regex guide's step WITH jump-forward (spl_dfa_jump_device), on torch's current stream; nothing synchronises.  Everything
+    dfa_step_device does, from the same arguments, and behind the sampler's ids the forced run of the state arrived at, as ids:
+    jump_index is dfa_jump_index_device(...) of the same table.  Returns (state_out, mask, live, forced_ids int32 [B, row_len_out],
+    forced_len int32 [B]): a sequence's first forced_len[b] entries of forced_ids[b] are ids the model need not be asked for -- the state
+    and the mask are those BEHIND them; entries at and beyond forced_len[b] are not written.  row_len_out: 1 .. 64, default 16 (or the
+    width of forced_ids); a run that does not fit is continued by the next call."""
+    if n_states is None:
+        if not isinstance(table, torch.Tensor) or table.dim() != 1 or table.shape[0] % 513:
+            raise ValueError("table must be a contiguous uint8 tensor of shape [n_states * 513] (dfa_table)")
+        n_states = int(table.shape[0]) // 513
+    if ids is None:
+        if not isinstance(state, torch.Tensor) or state.dim() != 1:
+            raise ValueError("state must be a contiguous int64 tensor of shape [batch]")
+        ids = torch.empty((state.shape[0], 0), dtype=torch.int32, device=state.device)
+    if mask is None and n_words is None:
+        n_words = dfa_n_words(tok)
+    if forced_ids is None and row_len_out is None:
+        row_len_out = 16
+    check_dfa_jump_args(ids, lengths, state, table, index, jump_index, n_states, end_ids=end_ids, n_words=n_words, keep_free=keep_free, mask=mask,
+                        state_out=state_out, forced_ids=forced_ids, forced_len=forced_len, row_len_out=row_len_out)
+    dev = ids.device
+    B = int(ids.shape[0])
+    K = int(ids.shape[1]) if ids.dim() == 2 else 1
+    n_words = int(mask.shape[1]) if mask is not None else int(n_words)
+    ends = _dfa_end_ids(end_ids, n_words)
+    if mask is None:
+        mask = torch.empty((B, n_words), dtype=torch.int32, device=dev)          # (every word of every row is written by the kernel)
+    if state_out is None:
+        state_out = torch.empty(B, dtype=torch.int64, device=dev)
+    if live is None:
+        live = torch.empty(max(B, 1), dtype=torch.uint8, device=dev)[:B]
+    else:
+        _vec("live", live, B, (torch.uint8,), "uint8")
+    if forced_ids is None:
+        forced_ids = torch.zeros((B, int(row_len_out)), dtype=torch.int32, device=dev)   # (entries behind forced_len are not written: zeros)
+    if forced_len is None:
+        forced_len = torch.empty(max(B, 1), dtype=torch.int32, device=dev)[:B]
+    flags = (_ffi.SPL_DFA_KEEP_FREE if keep_free else 0) | (_ffi.SPL_DFA_I64 if ids.dtype == torch.int64 else 0)
+    # (null pointers are refused by the library: an empty batch passes addresses of its own, which nothing dereferences)
+    spare = torch.empty(16, dtype=torch.int64, device=dev).data_ptr() if B == 0 else 0
+    si = _ffi.SplDfaIn(B, K, _ptr(ids), _ptr(lengths), _ptr(state) or spare, _ptr(table), _ptr(index), int(n_states))
+    o = _ffi.SplDfaOpts(flags, n_words, ends)
+    so = _ffi.SplDfaOut(_ptr(state_out) or spare + 16, _ptr(mask) or spare + 32, _ptr(live))
+    jo = _ffi.SplDfaJumpOut(int(forced_ids.shape[1]), _ptr(jump_index), _ptr(forced_ids) or spare + 48, _ptr(forced_len) or spare + 64)
+    rc = _ffi.lib().spl_dfa_jump_device(tok.handle, ctypes.byref(si), ctypes.byref(o), ctypes.byref(so), ctypes.byref(jo),
+                                        torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        _raise_rc(rc, "spl_dfa_jump_device")
+    return state_out, mask, live, forced_ids, forced_len
+
+
 class RegexGuide:
     """`tokenizer.regex_guide(batch_size, pattern)`: "the answer matches this regular expression" for a batch whose state lives on the
     GPU.  The pattern (or each of a list of patterns, stacked into one table) is compiled on the host by splintr_amd.dfa.compile_regex
@@ -1895,9 +2004,14 @@ class RegexGuide:
     the start states and the first masks; step(ids) follows the sampler; `mask` (int32 [B, n_words], the apply_token_bitmask layout)
     always holds the ids the next step may draw -- all ones for a sequence that is free, done or broken.  A sequence is done when an END
     id follows an accepting state.  UTF-8 validity of `.` and negated classes is not the guide's:
-    DeviceStreamingDecoder.allowed_mask(guide.mask, and_into=True) ANDs it in.  Nothing here synchronises."""
+    DeviceStreamingDecoder.allowed_mask(guide.mask, and_into=True) ANDs it in.  Nothing here synchronises.
 
-    def __init__(self, tok: Tokenizer, batch_size: int, pattern_or_patterns, *, end_ids, n_words: Optional[int] = None):
+    jump=True adds JUMP-FORWARD: the constructor also builds the jump index (the forced byte run of every state, encoded once -- build-time
+    work that synchronises once), and jump(ids) is step(ids) that also hands back, as ids, the run the automaton forces behind them:
+    `forced_ids` int32 [B, jump_ids] and `forced_len` int32 [B] -- tokens no forward pass is needed for."""
+
+    def __init__(self, tok: Tokenizer, batch_size: int, pattern_or_patterns, *, end_ids, n_words: Optional[int] = None, jump: bool = False,
+                 jump_ids: int = 16):
         from . import dfa as _dfa
         if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)) or not 0 <= int(batch_size) < (1 << 31):
             raise ValueError(f"batch_size must be an integer in 0 .. 2**31 - 1, not {batch_size!r}")
@@ -1919,6 +2033,15 @@ class RegexGuide:
         self.mask = torch.full((self.batch_size, self.n_words), -1, dtype=torch.int32, device=dev)
         self._state = torch.zeros(self.batch_size, dtype=torch.int64, device=dev)
         self.live = torch.zeros(self.batch_size, dtype=torch.uint8, device=dev)
+        self.jump_index = self.forced_ids = self.forced_len = self._runs = None
+        if jump:
+            if isinstance(jump_ids, bool) or not isinstance(jump_ids, (int, np.integer)) or not 1 <= int(jump_ids) <= _ffi.SPL_DFA_JUMP_MAX_IDS:
+                raise ValueError(f"jump_ids must be an integer in 1 .. {_ffi.SPL_DFA_JUMP_MAX_IDS}, not {jump_ids!r}")
+            self.jump_index = dfa_jump_index_device(tok, self.table, self.n_states)
+            self.forced_ids = torch.zeros((self.batch_size, int(jump_ids)), dtype=torch.int32, device=dev)
+            self.forced_len = torch.zeros(self.batch_size, dtype=torch.int32, device=dev)
+            _, _, run_len, run = dfa_jump_index_views(self.jump_index.cpu(), self.n_states)      # (the host copy forced_text answers from)
+            self._runs = [bytes(run[q, :int(run_len[q])].tolist()) for q in range(self.n_states)]
 
     def _call(self, ids, lengths, keep_free):
         dfa_step_device(self._tok, ids, lengths, self._state, self.table, self.index, end_ids=self.end_ids, n_states=self.n_states,
@@ -1954,14 +2077,46 @@ class RegexGuide:
         sequence left its constraint (its row holds ones since then)."""
         return self._call(ids, lengths, keep_free)
 
+    def jump(self, ids: Optional[torch.Tensor] = None, lengths: Optional[torch.Tensor] = None, *, keep_free: bool = False):
+        """step(ids, lengths) with jump-forward (a guide made with jump=True) -> (forced_ids int32 [B, jump_ids], forced_len int32 [B]):
+        behind what the sampler drew, the leading forced_len[b] entries of forced_ids[b] are the ids the automaton forces -- append them
+        to the sequence without a forward pass; `mask`, `state` and `live` are those BEHIND them.  ids None right after begin() emits the
+        start state's run.  A run longer than jump_ids ids (or 64 bytes) is continued by the next call: call jump(None) again while
+        forced_len is not zero, or simply go on -- the mask allows nothing but the run.  The pair has the [B, K] + lengths form the
+        streaming decoder takes:
+
+            forced, n = guide.jump(drawn)                       # drawn: [B] from the sampler
+            text = decoder.add_tokens(forced, lengths=n)        # DeviceStreamingDecoder: the run's text, no host round trip
+
+        The ids are those of the run encoded alone: the seam with the text in front of it is not re-tokenised."""
+        if self.jump_index is None:
+            raise ValueError("this guide was made without jump=True")
+        dfa_jump_device(self._tok, ids, lengths, self._state, self.table, self.index, self.jump_index, end_ids=self.end_ids, n_states=self.n_states,
+                        keep_free=keep_free, mask=self.mask, state_out=self._state, live=self.live, forced_ids=self.forced_ids,
+                        forced_len=self.forced_len)
+        return self.forced_ids, self.forced_len
+
+    def forced_text(self, q: int) -> bytes:
+        """The bytes state q (of the stacked table) forces: run(q) of include/splintr_hip.h, capped at 64 bytes and trimmed to a character
+        boundary; b"" where the state leaves a choice or accepts.  From a host copy made at construction."""
+        if self._runs is None:
+            raise ValueError("this guide was made without jump=True")
+        if isinstance(q, bool) or not isinstance(q, (int, np.integer)) or not 0 <= int(q) < self.n_states:
+            raise ValueError(f"q must be a state in 0 .. {self.n_states - 1}, not {q!r}")
+        return self._runs[int(q)]
+
     def reset(self, rows=None) -> None:
         """All sequences (rows None) or the given ones (indices or a bool mask) free, their mask rows ones."""
         if rows is None:
             self._state.zero_(); self.mask.fill_(-1); self.live.zero_()
+            if self.forced_len is not None:
+                self.forced_len.zero_()
         else:
             self._state[rows] = 0
             self.mask[rows] = -1
             self.live[rows] = 0
+            if self.forced_len is not None:
+                self.forced_len[rows] = 0
 
     def apply(self, logits: torch.Tensor, *, live_only: bool = False) -> torch.Tensor:
         """logits [B, V] (float32, float16 or bfloat16) with -inf wherever the mask forbids the id, IN PLACE: one launch of

@@ -612,15 +612,16 @@ class Tokenizer:
         from . import device as dv
         return dv.ChoiceGuide(self, batch_size, choices, end_ids=end_ids, then_free=then_free, n_words=n_words)
 
-    def regex_guide(self, batch_size: int, pattern_or_patterns, *, end_ids, n_words: Optional[int] = None):
+    def regex_guide(self, batch_size: int, pattern_or_patterns, *, end_ids, n_words: Optional[int] = None, jump: bool = False, jump_ids: int = 16):
         """Extension: the regex guide on the GPU (splintr_amd.device.RegexGuide): the answer of every sequence matches a regular
         expression -- Python `re` semantics in bytes mode, fullmatch; splintr_amd.dfa names what is supported.  A list of patterns is
         stacked into one table and begin(select) picks one per sequence.  begin() writes the start states and the first masks, step(ids)
         follows the sampler, and `mask` -- int32 [B, n_words], the apply_token_bitmask layout -- holds the ids the automaton can walk
         on with.  end_ids: the ids (usually specials, 1 .. 8) that may follow an accepting state and end the sequence.  `done`, `broken`
-        and `live` read the state on the device."""
+        and `live` read the state on the device.  jump=True adds jump-forward: jump(ids) is step(ids) that also returns, as ids
+        (int32 [B, jump_ids] and their counts), the run the automaton forces behind them -- tokens that need no forward pass."""
         from . import device as dv
-        return dv.RegexGuide(self, batch_size, pattern_or_patterns, end_ids=end_ids, n_words=n_words)
+        return dv.RegexGuide(self, batch_size, pattern_or_patterns, end_ids=end_ids, n_words=n_words, jump=jump, jump_ids=jump_ids)
 
     def apply_token_bitmask(self, logits, mask, *, live=None):
         """Extension: an allowed-token bitmask (int32 [B, n_words]: a TokenHealer's `mask`, DeviceStreamingDecoder.allowed_mask(), or
