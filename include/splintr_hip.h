@@ -1230,8 +1230,9 @@ int spl_choice_step_device(spl_tokenizer* t, const spl_choice_in* in, const spl_
  * What the rule is NOT, as healing's: it ignores the split pattern, so the ids need not be the canonical encoding of the match; UTF-8
  * validity is not part of it -- a `.` or a negated class of the pattern admits any byte (spl_utf8_mask_device with SPL_UTF8_AND can AND
  * its rows into these afterwards); the table is assumed TRIMMED (every state reaches an accepting one, as splintr_amd/dfa.py leaves it):
- * that is what makes "the walk does not die" the right rule, an untrimmed table merely allows ids that lead nowhere.  Context-free
- * grammars, more than 4096 states and a table per sequence are out of scope.
+ * that is what makes "the walk does not die" the right rule, an untrimmed table merely allows ids that lead nowhere.  Nested
+ * brackets (JSON mode) are spl_nest_step_device's (below); general context-free grammars, more than 4096 states and a table per
+ * sequence are out of scope.
  *
  * SHAPE.  spl_dfa_index_device: two launches on hip_stream, asynchronous -- a lane owns an id and tests its first byte before anything
  * else, a wavefront's ballot is two words of a row; then a wavefront per state ORs its row into some[q].  spl_dfa_step_device: ONE
@@ -1343,6 +1344,104 @@ typedef struct spl_dfa_jump_out {
 int spl_dfa_jump_index_device(spl_tokenizer* t, const uint8_t* d_table, uint32_t n_states, void* d_jump_index, void* hip_stream);
 int spl_dfa_jump_device(spl_tokenizer* t, const spl_dfa_in* in, const spl_dfa_opts* o, const spl_dfa_out* out, const spl_dfa_jump_out* jump,
                         void* hip_stream);
+
+/* NESTED LANGUAGES -- JSON MODE -- for n_seqs sequences at once, everything in DEVICE memory (csrc/spl_k_nest.h): the
+ * answer of a sequence is SOME valid JSON document (OpenAI's response_format json_object, vLLM's guided_json without a schema), or a
+ * word of any other language made of regular pieces inside nested brackets.  A regular expression cannot say that; the regex guide's
+ * byte automaton plus a small STACK per sequence can.  The library holds no builder: the calls take a table in the caller's device
+ * memory (splintr_amd/nest.py builds the JSON one).  walk, ORDINARY, b(t), END ids, KEEP_FREE, I64, live and the empty-row break mean
+ * what they mean for spl_dfa_step_device.
+ *
+ * THE TABLE (SPL_NEST_TABLE_BYTES(n_states, n_ret) of device memory, the CALLER's, 2-byte aligned), in this order: uint16
+ * trans[S][256], uint16 ret[n_ret][16], uint8 op[S][256], uint8 accept[S].  S = n_states is 1 .. SPL_NEST_MAX_STATES, n_ret is
+ * 0 .. SPL_NEST_MAX_RET.  A CONFIGURATION is (q, stack); the stack holds 4-bit symbols and is at most o->max_depth deep, max_depth in
+ * 1 .. SPL_NEST_MAX_DEPTH.  One byte x from (q, stack), with v = trans[q][x] and o = op[q][x]:
+ *   o == 0              (v, stack) if v < S, else DEAD.
+ *   o == 0x10 | y       PUSH y (0..15): (v, stack + y) if v < S and depth < max_depth, else DEAD.
+ *   o == 0x20           POP: with y the top symbol, (ret[v][y], stack - top) if depth > 0, v < n_ret and ret[v][y] < S, else DEAD.
+ *   any other o         DEAD.
+ * The kernels never index outside the table, whatever it holds.  END may follow (q, stack) iff accept[q] and the stack is empty.  The
+ * return state of a pop depends on the popped symbol: a JSON table keeps "which container am I in" in the state and "which container
+ * encloses it" on the stack.
+ *
+ * STACK-FREE AND TOUCHING PAIRS.  Walk b(t) from q and ignore the stack: the pair (q, t) TOUCHES iff the walk meets a byte with
+ * op != 0 before it dies or ends -- whether or not that op then turns out to be valid.
+ *
+ * THE INDEX (SPL_NEST_INDEX_BYTES(n_states, n_words, dep_cap) of device memory, the CALLER's, 4-byte aligned), written by
+ * spl_nest_index_device: int32 rows[S][stride] with the regex guide's stride, uint32 dep_off[S + 1], uint32 dep_ids[dep_cap], uint8
+ * some[S].  Bit t of rows[q] is 1 iff t is ordinary, the walk ends alive and the pair does not touch; dep_ids[dep_off[q] ..
+ * dep_off[q + 1]) are the ordinary ids that touch from q, ascending; some[q] is 1 iff the row has a bit.  The index depends on neither
+ * the END ids nor max_depth.  spl_nest_index_device is BUILD-TIME work: it may ALLOCATE scratch and SYNCHRONISES hip_stream once, to
+ * read the number of dependent entries, which it returns through *n_dep.  Where that is above dep_cap the call returns SPL_ECAPACITY
+ * ("dep_cap is too small") with *n_dep set: rows, some and dep_off are then written, no entry of dep_ids is, and nothing behind the
+ * index ever; call again with dep_cap >= *n_dep.
+ *
+ * THE STATE ROW (SPL_NEST_STATE_WORDS uint64 per sequence; all zero is free; every bit not named is 0, so rows compare bit for bit):
+ *   word 0       bits 0..15 q, bit 16 constrained, bit 17 broken, bit 18 done -- as spl_dfa_step_device's -- and bits 24..30 the depth
+ *   words 1..4   stack level i (0 = the bottom) in word 1 + i / 16, bits 4 * (i % 16) ..
+ * TO BEGIN the caller writes start | 1 << 16 and zeros.  ON LOAD a constrained row with q >= S or depth > max_depth is broken; nibbles
+ * at or above the depth are ignored and written back as zero.  A sequence that is done, broken or free is written with an empty stack.
+ *
+ * STEP AND MASK.  Per id, while the sequence is constrained: an ordinary id whose walk from the configuration lives moves the
+ * configuration; otherwise an END id where END may follow makes the sequence done; anything else breaks it.  The mask of the
+ * configuration arrived at is rows[q], ORed with the dependent ids of q whose walk from the REAL stack lives, ORed with the END bits
+ * where END may follow.  If that is empty the sequence breaks in that call and its row is ones.  Free, done and broken rows are ones.
+ * With every op zero, rows, some, the mask, live and state word 0 are spl_dfa_*'s bit for bit and every dep list is empty.
+ *
+ * SHAPE.  spl_nest_index_device: k_dfa_index's shape with two ballots per (state, 64 ids) -- alive and stack-free into rows, touching
+ * into a scratch bitmap --, a wavefront per state that ORs and popcounts, an exclusive scan of at most 4096 counts in one workgroup,
+ * and a wavefront per state that turns its scratch row into ascending ids.  spl_nest_step_device: ONE launch after
+ * spl_nest_reserve_device, a wavefront per sequence, neither allocating nor synchronising; a state without dependent ids takes the
+ * regex guide's row copy; otherwise the row goes out in pieces of 1024 words, the dependent ids of a piece walked a lane each against
+ * a private copy of the stack and merged in 4 KB of LDS BEFORE the copy: every mask word is stored exactly once, nothing is read back.
+ * No atomics on global memory, no wait between workgroups.
+ *
+ * SPL_EINVAL, before anything touches the device: everything spl_dfa_index_device and spl_dfa_step_device refuse; n_ret above
+ * SPL_NEST_MAX_RET; max_depth 0 or above SPL_NEST_MAX_DEPTH; a null n_dep; index_bytes below
+ * SPL_NEST_INDEX_BYTES(n_states, n_words, dep_cap).  JSON Schema, general context-free grammars, jump-forward for nest tables, more
+ * than 16 stack symbols or 64 levels are out of scope. */
+#define SPL_NEST_KEEP_FREE   2u
+#define SPL_NEST_I64         4u
+#define SPL_NEST_PUSH        0x10
+#define SPL_NEST_POP         0x20
+#define SPL_NEST_MAX_STATES  4096
+#define SPL_NEST_MAX_RET     4096
+#define SPL_NEST_MAX_DEPTH   64
+#define SPL_NEST_STATE_WORDS 5
+#define SPL_NEST_MAX_END     8
+#define SPL_NEST_TABLE_BYTES(n_states, n_ret) ((size_t)(n_states) * 769 + (size_t)(n_ret) * 32)
+#define SPL_NEST_INDEX_BYTES(n_states, n_words, dep_cap) \
+    ((size_t)(n_states) * ((((size_t)(n_words) + 3) & ~(size_t)3) * 4 + 5) + 4 + (size_t)(dep_cap) * 4)
+
+typedef struct spl_nest_opts {
+    uint32_t struct_size;                 /* sizeof the struct as the CALLER was compiled */
+    uint32_t flags, n_words;
+    uint32_t n_end;                       /* 1 .. SPL_NEST_MAX_END */
+    uint32_t end_ids[SPL_NEST_MAX_END];
+    uint32_t max_depth, reserved;         /* max_depth: 1 .. SPL_NEST_MAX_DEPTH */
+} spl_nest_opts;
+typedef struct spl_nest_in {
+    uint32_t struct_size, row_len;        /* row_len: the columns of d_ids (may be 0) */
+    uint64_t n_seqs;
+    const void* d_ids; const int32_t* d_len;
+    const uint64_t* d_state_in;           /* [n_seqs, SPL_NEST_STATE_WORDS] */
+    const uint8_t* d_table;               /* SPL_NEST_TABLE_BYTES(n_states, n_ret) */
+    const int32_t* d_index;               /* SPL_NEST_INDEX_BYTES(n_states, n_words, dep_cap), as spl_nest_index_device left it */
+    uint32_t n_states, n_ret;
+    uint32_t dep_cap, reserved;           /* dep_cap: the one the index was built with */
+    uint64_t index_bytes;                 /* the bytes behind d_index */
+} spl_nest_in;
+typedef struct spl_nest_out {
+    uint32_t struct_size, reserved;
+    uint64_t* d_state_out;                /* [n_seqs, SPL_NEST_STATE_WORDS]; may be d_state_in */
+    int32_t* d_mask;                      /* [n_seqs, n_words] */
+    uint8_t* d_live;                      /* NULL ok */
+} spl_nest_out;
+
+int spl_nest_reserve_device(spl_tokenizer* t);
+int spl_nest_index_device(spl_tokenizer* t, const uint8_t* d_table, uint32_t n_states, uint32_t n_ret, uint32_t n_words, int32_t* d_index,
+                          uint32_t dep_cap, uint32_t* n_dep, void* hip_stream);
+int spl_nest_step_device(spl_tokenizer* t, const spl_nest_in* in, const spl_nest_opts* o, const spl_nest_out* out, void* hip_stream);
 
 /* Host-side lookup of ONE id, for consumers that decode token by token on the CPU -- the streaming
  * decoders (src/core/streaming.rs, src/python/bindings.rs:465-834 take clones of Tokenizer::decoder

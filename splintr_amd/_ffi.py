@@ -37,6 +37,7 @@ SYMBOLS = [
     "spl_utf8_mask_reserve_device", "spl_utf8_mask_device", "spl_mask_apply_device",
     "spl_choice_reserve_device", "spl_choice_step_device",
     "spl_dfa_reserve_device", "spl_dfa_index_device", "spl_dfa_step_device", "spl_dfa_jump_index_device", "spl_dfa_jump_device",
+    "spl_nest_reserve_device", "spl_nest_index_device", "spl_nest_step_device",
 ]
 SPL_PATTERN_CUSTOM = 3
 SPL_OPT_BYTE_LEVEL = 1
@@ -60,6 +61,9 @@ SPL_CHOICE_SLOTS, SPL_CHOICE_MAX_LEN, SPL_CHOICE_TABLE_BYTES, SPL_CHOICE_STATE_W
 SPL_DFA_KEEP_FREE, SPL_DFA_I64 = 2, 4
 SPL_DFA_DEAD, SPL_DFA_MAX_STATES, SPL_DFA_STATE_WORDS, SPL_DFA_MAX_END = 0xFFFF, 4096, 1, 8
 SPL_DFA_JUMP_MAX_BYTES, SPL_DFA_JUMP_MAX_IDS = 64, 64
+SPL_NEST_KEEP_FREE, SPL_NEST_I64, SPL_NEST_PUSH, SPL_NEST_POP = 2, 4, 0x10, 0x20
+SPL_NEST_MAX_STATES, SPL_NEST_MAX_RET, SPL_NEST_MAX_DEPTH, SPL_NEST_STATE_WORDS, SPL_NEST_MAX_END = 4096, 4096, 64, 5, 8
+SPL_ECAPACITY = -3
 
 
 def SPL_DFA_TABLE_BYTES(n_states: int) -> int:
@@ -72,6 +76,14 @@ def SPL_DFA_JUMP_INDEX_BYTES(n_states: int) -> int:
 
 def SPL_DFA_INDEX_BYTES(n_states: int, n_words: int) -> int:
     return n_states * (((n_words + 3) & ~3) * 4 + 1)
+
+
+def SPL_NEST_TABLE_BYTES(n_states: int, n_ret: int) -> int:
+    return n_states * 769 + n_ret * 32
+
+
+def SPL_NEST_INDEX_BYTES(n_states: int, n_words: int, dep_cap: int) -> int:
+    return n_states * (((n_words + 3) & ~3) * 4 + 5) + 4 + dep_cap * 4
 
 
 class SplOpts(ctypes.Structure):
@@ -270,6 +282,36 @@ class SplDfaJumpOut(ctypes.Structure):
         super().__init__(ctypes.sizeof(SplDfaJumpOut), row_len_out, jump_index, forced_ids, forced_len)
 
 
+class SplNestOpts(ctypes.Structure):
+    """spl_nest_opts (include/splintr_hip.h): flags, the words of a mask row, the END ids by value and the deepest stack."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("n_words", ctypes.c_uint32), ("n_end", ctypes.c_uint32),
+                ("end_ids", ctypes.c_uint32 * 8), ("max_depth", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    def __init__(self, flags=0, n_words=0, end_ids=(), max_depth=0):
+        end_ids = tuple(end_ids)
+        super().__init__(ctypes.sizeof(SplNestOpts), flags, n_words, len(end_ids), (ctypes.c_uint32 * 8)(*end_ids[:8]), max_depth, 0)
+
+
+class SplNestIn(ctypes.Structure):
+    """spl_nest_in: the rows of ids, their lengths, the state rows, the nest table and its index, device addresses (None: not given)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("row_len", ctypes.c_uint32), ("n_seqs", ctypes.c_uint64), ("d_ids", ctypes.c_void_p),
+                ("d_len", ctypes.c_void_p), ("d_state_in", ctypes.c_void_p), ("d_table", ctypes.c_void_p), ("d_index", ctypes.c_void_p),
+                ("n_states", ctypes.c_uint32), ("n_ret", ctypes.c_uint32), ("dep_cap", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("index_bytes", ctypes.c_uint64)]
+
+    def __init__(self, n_seqs=0, row_len=0, ids=None, lengths=None, state=None, table=None, index=None, n_states=0, n_ret=0, dep_cap=0, index_bytes=0):
+        super().__init__(ctypes.sizeof(SplNestIn), row_len, n_seqs, ids, lengths, state, table, index, n_states, n_ret, dep_cap, 0, index_bytes)
+
+
+class SplNestOut(ctypes.Structure):
+    """spl_nest_out: where the outputs go, device addresses (None: not wanted)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("d_state_out", ctypes.c_void_p), ("d_mask", ctypes.c_void_p),
+                ("d_live", ctypes.c_void_p)]
+
+    def __init__(self, state=None, mask=None, live=None):
+        super().__init__(ctypes.sizeof(SplNestOut), 0, state, mask, live)
+
+
 _lib = None
 
 
@@ -408,6 +450,9 @@ def lib() -> ctypes.CDLL:
     L.spl_dfa_step_device.argtypes = [vp, ctypes.POINTER(SplDfaIn), ctypes.POINTER(SplDfaOpts), ctypes.POINTER(SplDfaOut), vp]
     L.spl_dfa_jump_index_device.argtypes = [vp, vp, ctypes.c_uint32, vp, vp]
     L.spl_dfa_jump_device.argtypes = [vp, ctypes.POINTER(SplDfaIn), ctypes.POINTER(SplDfaOpts), ctypes.POINTER(SplDfaOut), ctypes.POINTER(SplDfaJumpOut), vp]
+    L.spl_nest_reserve_device.argtypes = [vp]
+    L.spl_nest_index_device.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), vp]
+    L.spl_nest_step_device.argtypes = [vp, ctypes.POINTER(SplNestIn), ctypes.POINTER(SplNestOpts), ctypes.POINTER(SplNestOut), vp]
     _lib = L
     return L
 

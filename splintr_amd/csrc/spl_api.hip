@@ -1,7 +1,7 @@
 // spl_api.hip -- the C ABI (include/splintr_hip.h): the root of the library's one HIP translation unit.  It includes the kernels
 // (spl_kernels.hip) and the host side, one file per concern and each building on the ones before it -- spl_host_res.h (resource owners,
 // pinned pool), spl_ctx.h (per-GPU context, handle, uploads), spl_streams.h (stream probe), spl_launch.h (memo, launch order, device
-// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_pair_host.h, spl_chat_host.h, spl_seqpack_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h, spl_seqscan_host.h, spl_stream_host.h, spl_stop_host.h, spl_heal_host.h, spl_mask_host.h, spl_choice_host.h, spl_dfa_host.h, spl_dfa_jump_host.h -- and holds the entry points.
+// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_pair_host.h, spl_chat_host.h, spl_seqpack_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h, spl_seqscan_host.h, spl_stream_host.h, spl_stop_host.h, spl_heal_host.h, spl_mask_host.h, spl_choice_host.h, spl_dfa_host.h, spl_dfa_jump_host.h, spl_nest_host.h -- and holds the entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -54,6 +54,7 @@ using namespace spl;
 #include "spl_choice_host.h"
 #include "spl_dfa_host.h"
 #include "spl_dfa_jump_host.h"
+#include "spl_nest_host.h"
 
 namespace {
 // No exception crosses the C ABI: every entry point that allocates (std::bad_alloc), starts threads or grows
@@ -525,6 +526,19 @@ int spl_dfa_jump_index_device(spl_tokenizer* t, const uint8_t* d_table, uint32_t
 
 int spl_dfa_jump_device(spl_tokenizer* t, const spl_dfa_in* in, const spl_dfa_opts* o, const spl_dfa_out* out, const spl_dfa_jump_out* jump, void* hip_stream) {
     return guarded("spl_dfa_jump_device", [&] { return dfa_jump_device(t, in, o, out, jump, (hipStream_t)hip_stream); });
+}
+
+int spl_nest_reserve_device(spl_tokenizer* t) {
+    return guarded("spl_nest_reserve_device", [&] { return nest_reserve_device(t); });
+}
+
+int spl_nest_index_device(spl_tokenizer* t, const uint8_t* d_table, uint32_t n_states, uint32_t n_ret, uint32_t n_words, int32_t* d_index, uint32_t dep_cap,
+                          uint32_t* n_dep, void* hip_stream) {
+    return guarded("spl_nest_index_device", [&] { return nest_index_device(t, d_table, n_states, n_ret, n_words, d_index, dep_cap, n_dep, (hipStream_t)hip_stream); });
+}
+
+int spl_nest_step_device(spl_tokenizer* t, const spl_nest_in* in, const spl_nest_opts* o, const spl_nest_out* out, void* hip_stream) {
+    return guarded("spl_nest_step_device", [&] { return nest_step_device(t, in, o, out, (hipStream_t)hip_stream); });
 }
 
 int spl_utf8_mask_reserve_device(spl_tokenizer* t) {

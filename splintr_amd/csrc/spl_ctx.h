@@ -73,6 +73,7 @@ struct Ctx {
     bool heal_uploaded = false;
     DevBuf<uint32_t> d_heal_scr; uint64_t heal_cap = 0;   // ... lo, hi and up to 63 partial ids per sequence, 264 bytes each (grow-only; shared with nothing)
     DevBuf<uint64_t> d_jmscr; uint64_t jmscr_cap = 0;   // spl_dfa_jump_index_device: the runs' bytes CSR, their ids CSR and the scan's sums, 344 bytes per state (grow-only; shared with nothing)
+    DevBuf<uint32_t> d_nsscr; uint64_t nsscr_cap = 0;   // spl_nest_index_device: the touching bitmap, a word per word of the index's rows, and a count per state (grow-only; shared with nothing)
     DevBuf<uint32_t> d_u8_present, d_u8_rows; uint32_t u8_stride = 0;   // spl_utf8_mask_device: the vocabulary proper as a bit per id, the class table's 17 rows of u8_stride words (upload_utf8; rebuilt after spl_add_special)
     bool u8_uploaded = false;
     DevBuf<uint8_t> d_sp_lits;                 // uploaded lazily; invalidated by spl_add_special

@@ -2148,6 +2148,283 @@ class RegexGuide:
         return f"RegexGuide(batch_size={self.batch_size}, patterns={len(self.dfas)}, n_states={self.n_states}, n_words={self.n_words})"
 
 
+# ---------------------------------------------------------------------------------------------- nested languages: JSON mode (masks from a byte automaton with a stack)
+def _nest_of(table):
+    from . import nest as _nest
+    if isinstance(table, _nest.NestTable):
+        return table
+    if hasattr(table, "trans") and not hasattr(table, "op"):
+        return _nest.from_dfa(table)
+    raise ValueError("the table must be a splintr_amd.nest.NestTable (json_table, from_dfa) or a splintr_amd.dfa.ByteDFA")
+
+
+def nest_table(table, device=None) -> torch.Tensor:
+    """The nest table of spl_nest_index_device / spl_nest_step_device on the device (default: the current GPU): uint8 [S * 769 + n_ret *
+    32] -- uint16 trans[S][256], uint16 ret[n_ret][16], uint8 op[S][256], uint8 accept[S].  table: a splintr_amd.nest.NestTable, or a
+    splintr_amd.dfa.ByteDFA (every op zero).  The tensor is the caller's."""
+    return torch.from_numpy(_nest_of(table).table()).to(torch.device("cuda") if device is None else device)
+
+
+def _nest_state_host(starts) -> np.ndarray:
+    words = _dfa_state_host(starts)
+    rows = np.zeros((len(words), _ffi.SPL_NEST_STATE_WORDS), dtype=np.int64)
+    rows[:, 0] = words
+    return rows
+
+
+def nest_state(starts, device=None) -> torch.Tensor:
+    """State rows int64 [len(starts), 5] for sequences that begin with an empty stack: per sequence a start state or None (a free row),
+    built on the host -- nest_step_device with ids None then writes the first masks."""
+    return torch.from_numpy(_nest_state_host(starts)).to(torch.device("cuda") if device is None else device)
+
+
+def nest_reserve(tok: Tokenizer) -> None:
+    """spl_nest_reserve_device: the decode tables and token healing's id -> rank on the device (shared with dfa_reserve); nest_step_device
+    calls then neither allocate nor synchronise."""
+    rc = _ffi.lib().spl_nest_reserve_device(tok.handle)
+    if rc != 0:
+        _raise_rc(rc, "spl_nest_reserve_device")
+
+
+def _nest_check_table(table, n_states, n_ret):
+    if isinstance(n_states, bool) or not isinstance(n_states, (int, np.integer)) or not 1 <= int(n_states) <= _ffi.SPL_NEST_MAX_STATES:
+        raise ValueError(f"n_states must be an integer in 1 .. {_ffi.SPL_NEST_MAX_STATES}, not {n_states!r}")
+    if isinstance(n_ret, bool) or not isinstance(n_ret, (int, np.integer)) or not 0 <= int(n_ret) <= _ffi.SPL_NEST_MAX_RET:
+        raise ValueError(f"n_ret must be an integer in 0 .. {_ffi.SPL_NEST_MAX_RET}, not {n_ret!r}")
+    want = _ffi.SPL_NEST_TABLE_BYTES(int(n_states), int(n_ret))
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.uint8 or table.shape != (want,) or not table.is_contiguous():
+        raise ValueError(f"table must be a contiguous uint8 tensor of shape [{want}] (nest_table) for {int(n_states)} states and {int(n_ret)} ret rows")
+
+
+def nest_index_device(tok: Tokenizer, table: torch.Tensor, n_states: int, n_ret: int, *, n_words: Optional[int] = None,
+                      dep_cap: Optional[int] = None) -> Tuple[torch.Tensor, int]:
+    """The index of a nest table (spl_nest_index_device), built on the GPU on torch's current stream -> (index uint8
+    [SPL_NEST_INDEX_BYTES(n_states, n_words, n_dep)], n_dep): the stack-free rows, per state the ascending ids that touch the stack, and
+    some[] -- nest_index_views gives the views.  BUILD-TIME work: the call may allocate and synchronises the stream.  dep_cap: a guess
+    at the number of dependent entries (default 4096); where it is too small the build is repeated with the exact size, and an index
+    built larger is cut to it.  n_words: default dfa_n_words(tok).  Build it again after add_special_tokens."""
+    _nest_check_table(table, n_states, n_ret)
+    _dfa_check_n_words(n_words)
+    if not table.is_cuda:
+        raise ValueError("table must be on a GPU (nest_table)")
+    if dep_cap is not None and (isinstance(dep_cap, bool) or not isinstance(dep_cap, (int, np.integer)) or not 0 <= int(dep_cap) < (1 << 32)):
+        raise ValueError(f"dep_cap must be an integer in 0 .. 2**32 - 1, not {dep_cap!r}")
+    n_words = dfa_n_words(tok) if n_words is None else int(n_words)
+    cap = 4096 if dep_cap is None else int(dep_cap)
+    n_dep = ctypes.c_uint32(0)
+    for _ in range(2):
+        out = torch.empty(_ffi.SPL_NEST_INDEX_BYTES(int(n_states), n_words, cap), dtype=torch.uint8, device=table.device)
+        rc = _ffi.lib().spl_nest_index_device(tok.handle, _ptr(table), int(n_states), int(n_ret), n_words, _ptr(out), cap, ctypes.byref(n_dep),
+                                              torch.cuda.current_stream(table.device).cuda_stream)
+        if rc != _ffi.SPL_ECAPACITY or n_dep.value <= cap:
+            break
+        cap = int(n_dep.value)                                                   # (the exact size)
+    if rc != 0:
+        _raise_rc(rc, "spl_nest_index_device")
+    n = int(n_dep.value)
+    if n < cap:                                                                  # some[] moves up behind the entries in use
+        S, head = int(n_states), _ffi.SPL_NEST_INDEX_BYTES(int(n_states), n_words, 0) - int(n_states)
+        out = torch.cat([out[:head + 4 * n], out[head + 4 * cap:head + 4 * cap + S]])
+    return out, n
+
+
+def nest_index_views(index: torch.Tensor, n_states: int, n_words: int, dep_cap: int):
+    """(rows int32 [n_states, stride], dep_off int32 [n_states + 1], dep_ids int32 [dep_cap], some uint8 [n_states]): views of an index."""
+    S, stride, cap = int(n_states), (int(n_words) + 3) & ~3, int(dep_cap)
+    a = S * stride * 4
+    b = a + 4 * (S + 1)
+    c = b + 4 * cap
+    return index[:a].view(torch.int32).view(S, stride), index[a:b].view(torch.int32), index[b:c].view(torch.int32), index[c:c + S]
+
+
+def check_nest_args(ids, lengths, state, table, index, n_states, n_ret, dep_cap, *, end_ids=None, max_depth=64, n_words=None, keep_free: bool = False,
+                    mask=None, state_out=None) -> None:
+    """ValueError for a dtype, rank, shape, layout, size or device that nest_step_device would refuse -- before anything goes to the device."""
+    if not isinstance(ids, torch.Tensor) or ids.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"the ids must be a torch tensor of dtype int32 or int64, not {getattr(ids, 'dtype', type(ids))}")
+    if ids.dim() not in (1, 2):
+        raise ValueError("the ids must have rank 1 ([batch]) or 2 ([batch, steps])")
+    if not ids.is_contiguous():
+        raise ValueError("the ids must be contiguous")
+    B = int(ids.shape[0])
+    if B >= (1 << 31) or (ids.dim() == 2 and ids.shape[1] >= (1 << 32)):
+        raise ValueError("the sequences must be fewer than 2**31 and a row shorter than 2**32")
+    if isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) or not 1 <= int(max_depth) <= _ffi.SPL_NEST_MAX_DEPTH:
+        raise ValueError(f"max_depth must be an integer in 1 .. {_ffi.SPL_NEST_MAX_DEPTH}, not {max_depth!r}")
+    _dfa_check_n_words(n_words)
+    _nest_check_table(table, n_states, n_ret)
+    others = [("table", table)]
+    if lengths is not None:
+        others.append(_vec("lengths", lengths, B, (torch.int32,), "int32"))
+
+    def rows(name, t):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.shape != (B, _ffi.SPL_NEST_STATE_WORDS) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous int64 tensor of shape [batch, {_ffi.SPL_NEST_STATE_WORDS}]")
+        return name, t
+
+    others.append(rows("state", state))
+    if state_out is not None:
+        others.append(rows("state_out", state_out))
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.int32 or mask.dim() != 2 or mask.shape[0] != B or not mask.is_contiguous() or \
+                (n_words is not None and mask.shape[1] != int(n_words)):
+            raise ValueError("mask must be a contiguous int32 tensor of shape [batch, n_words]")
+        others.append(("mask", mask))
+    elif keep_free:
+        raise ValueError("keep_free needs the caller's mask (the rows of sequences that are not constrained filled with ones once)")
+    width = int(mask.shape[1]) if mask is not None else int(n_words)
+    want = _ffi.SPL_NEST_INDEX_BYTES(int(n_states), width, int(dep_cap))
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.uint8 or index.shape != (want,) or not index.is_contiguous():
+        raise ValueError(f"index must be a contiguous uint8 tensor of shape [{want}] (nest_index_device with the same n_states and n_words, and its n_dep)")
+    others.append(("index", index))
+    _dfa_end_ids(end_ids, width)
+    if not ids.is_cuda:
+        raise ValueError("the ids must be on a GPU (the device-side nest guide takes no host tensor)")
+    for name, t in others:
+        if t.device != ids.device:
+            raise ValueError(f"{name} must be on the device of the ids")
+
+
+def nest_step_device(tok: Tokenizer, ids: Optional[torch.Tensor], lengths: Optional[torch.Tensor], state: torch.Tensor, table: torch.Tensor,
+                     index: torch.Tensor, *, n_states: int, n_ret: int, dep_cap: int, end_ids, max_depth: int = 64, keep_free: bool = False,
+                     mask: Optional[torch.Tensor] = None, state_out: Optional[torch.Tensor] = None, live: Optional[torch.Tensor] = None,
+                     n_words: Optional[int] = None):
+    """The nest guide, one step (spl_nest_step_device), on torch's current stream; nothing synchronises.  state int64 [B, 5]: the rows as
+    include/splintr_hip.h lays them out (nest_state: sequences that begin); table: nest_table(...); index, dep_cap: what
+    nest_index_device returned; ids [B] or [B, K] int32 / int64: what the sampler drew (None: no ids, the masks of the rows as they are).
+    An ordinary id whose bytes the automaton can walk from the sequence's state AND STACK moves both; an END id in an accepting state
+    with an empty stack ends the sequence; anything else breaks it.  Returns (state_out int64 [B, 5], mask int32 [B, n_words], live uint8
+    [B]).  state_out may be state.  max_depth: the deepest stack, 1 .. 64 -- an opener beyond it is not allowed."""
+    if ids is None:
+        if not isinstance(state, torch.Tensor) or state.dim() != 2:
+            raise ValueError(f"state must be a contiguous int64 tensor of shape [batch, {_ffi.SPL_NEST_STATE_WORDS}]")
+        ids = torch.empty((state.shape[0], 0), dtype=torch.int32, device=state.device)
+    if mask is None and n_words is None:
+        n_words = dfa_n_words(tok)
+    check_nest_args(ids, lengths, state, table, index, n_states, n_ret, dep_cap, end_ids=end_ids, max_depth=max_depth, n_words=n_words,
+                    keep_free=keep_free, mask=mask, state_out=state_out)
+    dev = ids.device
+    B = int(ids.shape[0])
+    K = int(ids.shape[1]) if ids.dim() == 2 else 1
+    n_words = int(mask.shape[1]) if mask is not None else int(n_words)
+    ends = _dfa_end_ids(end_ids, n_words)
+    if mask is None:
+        mask = torch.empty((B, n_words), dtype=torch.int32, device=dev)          # (every word of every row is written by the kernel)
+    if state_out is None:
+        state_out = torch.empty((B, _ffi.SPL_NEST_STATE_WORDS), dtype=torch.int64, device=dev)
+    if live is None:
+        live = torch.empty(max(B, 1), dtype=torch.uint8, device=dev)[:B]
+    else:
+        _vec("live", live, B, (torch.uint8,), "uint8")
+    flags = (_ffi.SPL_NEST_KEEP_FREE if keep_free else 0) | (_ffi.SPL_NEST_I64 if ids.dtype == torch.int64 else 0)
+    # (null state and mask pointers are refused by the library: an empty batch passes addresses of its own, which nothing dereferences)
+    spare = torch.empty(8, dtype=torch.int64, device=dev).data_ptr() if B == 0 else 0
+    si = _ffi.SplNestIn(B, K, _ptr(ids), _ptr(lengths), _ptr(state) or spare, _ptr(table), _ptr(index), int(n_states), int(n_ret), int(dep_cap),
+                        int(index.numel()))
+    o = _ffi.SplNestOpts(flags, n_words, ends, int(max_depth))
+    so = _ffi.SplNestOut(_ptr(state_out) or spare + 16, _ptr(mask) or spare + 32, _ptr(live))
+    rc = _ffi.lib().spl_nest_step_device(tok.handle, ctypes.byref(si), ctypes.byref(o), ctypes.byref(so), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        _raise_rc(rc, "spl_nest_step_device")
+    return state_out, mask, live
+
+
+class NestGuide:
+    """`tokenizer.nest_guide(batch_size, table)` / `tokenizer.json_guide(batch_size)`: "the answer is a word of this nested language" --
+    JSON mode -- for a batch whose state AND STACK live on the GPU.  The table's index is built on the GPU once (build-time work that
+    synchronises); begin() writes the start state and the first masks; step(ids) follows the sampler; `mask` (int32 [B, n_words], the
+    apply_token_bitmask layout) always holds the ids the next step may draw -- all ones for a sequence that is free, done or broken.  A
+    sequence is done when an END id follows an accepting state with an empty stack.  After the constructor nothing synchronises."""
+
+    def __init__(self, tok: Tokenizer, batch_size: int, table, *, end_ids, max_depth: int = 64, n_words: Optional[int] = None):
+        if isinstance(batch_size, bool) or not isinstance(batch_size, (int, np.integer)) or not 0 <= int(batch_size) < (1 << 31):
+            raise ValueError(f"batch_size must be an integer in 0 .. 2**31 - 1, not {batch_size!r}")
+        if isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) or not 1 <= int(max_depth) <= _ffi.SPL_NEST_MAX_DEPTH:
+            raise ValueError(f"max_depth must be an integer in 1 .. {_ffi.SPL_NEST_MAX_DEPTH}, not {max_depth!r}")
+        self._tok, self.batch_size, self.max_depth = tok, int(batch_size), int(max_depth)
+        self.n_words = dfa_n_words(tok) if n_words is None else int(n_words)
+        _dfa_check_n_words(self.n_words)
+        self.nest = _nest_of(table)
+        self.n_states, self.n_ret, self.start = self.nest.n_states, self.nest.n_ret, self.nest.start
+        self.end_ids = _dfa_end_ids(end_ids, self.n_words)
+        dev = torch.device("cuda", tok._device)
+        nest_reserve(tok)
+        self.table = nest_table(self.nest, dev)
+        self.index, self.n_dep = nest_index_device(tok, self.table, self.n_states, self.n_ret, n_words=self.n_words)
+        self.mask = torch.full((self.batch_size, self.n_words), -1, dtype=torch.int32, device=dev)
+        self._state = torch.zeros((self.batch_size, _ffi.SPL_NEST_STATE_WORDS), dtype=torch.int64, device=dev)
+        self.live = torch.zeros(self.batch_size, dtype=torch.uint8, device=dev)
+
+    def _call(self, ids, lengths, keep_free):
+        nest_step_device(self._tok, ids, lengths, self._state, self.table, self.index, n_states=self.n_states, n_ret=self.n_ret, dep_cap=self.n_dep,
+                         end_ids=self.end_ids, max_depth=self.max_depth, keep_free=keep_free, mask=self.mask, state_out=self._state, live=self.live)
+        return self.mask
+
+    def begin(self, rows=None) -> torch.Tensor:
+        """The start state and an empty stack for every sequence (rows None) or the given ones (indices or a bool mask; the others keep
+        their state), and the first masks -> the mask."""
+        first = torch.zeros(_ffi.SPL_NEST_STATE_WORDS, dtype=torch.int64, device=self._state.device)
+        first[0] = self.start | 1 << 16
+        if rows is None:
+            self._state.copy_(first.expand_as(self._state))
+        else:
+            self._state[rows] = first
+        return self._call(None, None, False)
+
+    def step(self, ids: Optional[torch.Tensor], lengths: Optional[torch.Tensor] = None, *, keep_free: bool = False) -> torch.Tensor:
+        """What the sampler drew, [B] or [B, K] (None: only the masks, after the caller wrote rows into `state`) -> the mask.  keep_free:
+        the rows of sequences that are not constrained are not written again -- right once a step WITHOUT it has run after the last
+        sequence left its constraint (its row holds ones since then)."""
+        return self._call(ids, lengths, keep_free)
+
+    def reset(self, rows=None) -> None:
+        """All sequences (rows None) or the given ones (indices or a bool mask) free, their mask rows ones."""
+        if rows is None:
+            self._state.zero_(); self.mask.fill_(-1); self.live.zero_()
+        else:
+            self._state[rows] = 0
+            self.mask[rows] = -1
+            self.live[rows] = 0
+
+    def apply(self, logits: torch.Tensor, *, live_only: bool = False) -> torch.Tensor:
+        """logits [B, V] (float32, float16 or bfloat16) with -inf wherever the mask forbids the id, IN PLACE: one launch of
+        mask_apply_device.  live_only: the rows of sequences that are not constrained (`live` 0) are skipped."""
+        if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.shape[0] != self.batch_size:
+            raise ValueError("logits must have shape [batch, vocabulary]")
+        return mask_apply_device(self._tok, logits, self.mask, live=self.live if live_only else None)
+
+    @property
+    def state(self) -> torch.Tensor:
+        """int64 [B, 5] on the device, as include/splintr_hip.h lays it out (the guide's own tensor: a row written here counts)"""
+        return self._state
+
+    @property
+    def q(self) -> torch.Tensor:
+        """int64 [B] on the device: the automaton's state of a constrained or done sequence"""
+        return self._state[:, 0] & 0xFFFF
+
+    @property
+    def depth(self) -> torch.Tensor:
+        """int64 [B] on the device: the open brackets of a constrained sequence"""
+        return (self._state[:, 0] >> 24) & 0x7F
+
+    @property
+    def broken(self) -> torch.Tensor:
+        return ((self._state[:, 0] >> 17) & 1).bool()
+
+    @property
+    def done(self) -> torch.Tensor:
+        return ((self._state[:, 0] >> 18) & 1).bool()
+
+    def stacks(self):
+        """The stacks as tuples of symbols, the bottom first: a host copy (it synchronises)."""
+        rows = self._state.cpu().numpy().view(np.uint64)
+        return [tuple(int(r[1 + i // 16] >> np.uint64(4 * (i % 16))) & 15 for i in range(int(r[0] >> np.uint64(24)) & 0x7F)) for r in rows]
+
+    def __repr__(self) -> str:
+        return f"NestGuide(batch_size={self.batch_size}, n_states={self.n_states}, n_dep={self.n_dep}, max_depth={self.max_depth}, n_words={self.n_words})"
+
+
 class Comm:
     """One rank of the library's own RCCL communicator (include/splintr_hip.h: spl_comm_*).  The 128-byte id is
     made by rank 0 and handed to the others by whatever the caller has; `from_torch_group` uses an existing

@@ -623,6 +623,23 @@ class Tokenizer:
         from . import device as dv
         return dv.RegexGuide(self, batch_size, pattern_or_patterns, end_ids=end_ids, n_words=n_words, jump=jump, jump_ids=jump_ids)
 
+    def nest_guide(self, batch_size: int, table, *, end_ids, max_depth: int = 64, n_words: Optional[int] = None):
+        """Extension: the nest guide on the GPU (splintr_amd.device.NestGuide): the answer of every sequence is a word of a language made
+        of regular pieces inside nested brackets, given as a splintr_amd.nest.NestTable -- a byte automaton whose transitions may push
+        and pop a stack of at most max_depth (1 .. 64) 4-bit symbols per sequence.  begin() writes the start state and the first masks,
+        step(ids) follows the sampler, `mask` holds the ids the next step may draw.  end_ids: the ids (usually specials, 1 .. 8) that
+        may follow an accepting state with an empty stack and end the sequence.  `done`, `broken`, `live` and `depth` read the device."""
+        from . import device as dv
+        return dv.NestGuide(self, batch_size, table, end_ids=end_ids, max_depth=max_depth, n_words=n_words)
+
+    def json_guide(self, batch_size: int, *, end_ids, top: str = "object", ws: str = "json", max_depth: int = 32, n_words: Optional[int] = None):
+        """Extension: JSON MODE on the GPU -- the answer of every sequence is SOME valid JSON document (response_format json_object,
+        guided_json without a schema): nest_guide over splintr_amd.nest.json_table(top, ws).  top: "object" (the usual contract),
+        "array" or "value"; ws: "json" (any whitespace JSON allows), "compact" (at most one space after , and :) or "none";
+        max_depth: the deepest nesting the masks allow."""
+        from . import nest
+        return self.nest_guide(batch_size, nest.json_table(top, ws), end_ids=end_ids, max_depth=max_depth, n_words=n_words)
+
     def apply_token_bitmask(self, logits, mask, *, live=None):
         """Extension: an allowed-token bitmask (int32 [B, n_words]: a TokenHealer's `mask`, DeviceStreamingDecoder.allowed_mask(), or
         xgrammar's) applied to logits [B, V] float32 / float16 / bfloat16 IN PLACE on the GPU, one launch
