@@ -1443,6 +1443,66 @@ int spl_nest_index_device(spl_tokenizer* t, const uint8_t* d_table, uint32_t n_s
                           uint32_t dep_cap, uint32_t* n_dep, void* hip_stream);
 int spl_nest_step_device(spl_tokenizer* t, const spl_nest_in* in, const spl_nest_opts* o, const spl_nest_out* out, void* hip_stream);
 
+/* DRAFT VERIFICATION for the regex guide and the nest guide (csrc/spl_k_draft.h): the guide behind a SPECULATIVE
+ * sampler -- draft models, n-gram lookup, Medusa / EAGLE trees (xgrammar's "rollback", vLLM's structured output with spec decode).  The
+ * verifier's one forward pass yields logits in front of every draft position; it needs the guide's mask in front of each of them and
+ * where the draft leaves the language.  From ONE state row per sequence, which is only read, and a draft of up to SPL_DRAFT_MAX_NODES
+ * ids per sequence, a chain or a tree, ONE launch writes the mask in front of the first draft id, the mask behind every draft id,
+ * whether each id is acceptable, and optionally live and the state behind each.  Everything not named here -- table, index, state row,
+ * END, ORDINARY, b(t), walk, settle, flags, refusals -- is spl_dfa_step_device's / spl_nest_step_device's.
+ *
+ * INPUT.  The step's spl_dfa_in / spl_nest_in and opts as they are.  row_len is the number of NODES, 0 .. SPL_DRAFT_MAX_NODES: row b of
+ * d_ids holds the id of each.  d_len clamps as it does for the step; nodes at or beyond the clamped length are ABSENT.  d_parent NULL
+ * is a CHAIN: node i hangs below node i - 1, node 0 below the root.  Otherwise int32 [row_len], one row for all sequences, or
+ * [n_seqs, row_len] with SPL_DRAFT_PARENT_PER_SEQ in draft->flags: a parent is -1 (the root) or an index 0 .. i - 1, so every tree comes
+ * in topological order.  A node whose parent is anything else (>= i, < -1), or whose ancestor is such a node or is absent, is an ORPHAN.
+ * The kernel never follows a value it has not checked.  THE PATH of node i is the ids of its ancestors from the root down, then its own.
+ *
+ * OUTPUT.  d_mask int32 [n_seqs, 1 + row_len, n_words]: row 0 belongs to the root, row 1 + i to node i.  d_ok uint8 [n_seqs, row_len].
+ * d_live uint8 [n_seqs, 1 + row_len] (NULL ok).  d_state_out uint64 [n_seqs, 1 + row_len, STATE_WORDS] (NULL ok).  d_state_in is only
+ * read; no output may coincide with it, with another input or with another output.
+ *   row 0        what the step writes for row_len 0: the mask in front of the first draft id.
+ *   row 1 + i    of a node that is present and no orphan: mask row, state row and live are bit for bit what spl_*_step_device writes for
+ *                this sequence from d_state_in when given the node's path as its ids.  As in the step nothing settles between the ids of
+ *                a path; only the configuration arrived at is settled.
+ *   ok[i]        1 iff the sequence is free on input, or every id of the path was read and accepted by the step's rule 1 or 2: after the
+ *                walk and before the settle the sequence is constrained, or it became `done` at the path's LAST id.  A child of a node
+ *                that ended the sequence, and anything below a rejected id, has ok 0; its row follows from the line above (done or
+ *                broken: ones).
+ *   absent, orphan   ok 0, live 0, a state row of 1 << 17 (broken) and zeros, a mask row of ones.
+ * SPL_*_KEEP_FREE skips the mask rows of nodes that are not constrained, as the step does per sequence.  For a chain ok is monotone along
+ * the row and its sum is the number of leading draft ids the guide accepts: the sampler takes min(that, what the model accepts), draws a
+ * bonus id under the mask row of that position (row `accepted`), and commits with ONE ordinary step over the accepted ids and the bonus id.
+ * A tree commits by copying the accepted node's state row into the sequence's (d_state_out).  Jump-forward inside a draft, drafts for
+ * guided choice and token healing, and more than 64 nodes are out of scope.
+ *
+ * SHAPE.  ONE launch each, k_dfa_draft / k_nest_draft: a wavefront owns one (sequence, row) pair, the grid is (1 + row_len) by sequences.
+ * Because a parent's index is below its child's, the ancestors of a node fit ONE 64-bit word: the wavefront climbs from the node through
+ * d_parent setting bits -- every value checked against -1 <= p < the node it was read at, so the climb ends within 64 steps whatever the
+ * array holds -- and walks the set bits in ascending order, which is root-to-node order; no local array, no scratch.  The walk, the
+ * settle and the row write are the step's own code, handed the output row b * (1 + row_len) + r in place of the sequence.  A row re-walks
+ * its prefix: at most 64 short serial walks against a row copy of tens of kilobytes.  The nest kernel keeps the step's 4 KB of LDS.  No
+ * atomics on global memory, no wait between workgroups, no allocation and no synchronisation after spl_dfa_reserve_device /
+ * spl_nest_reserve_device.
+ *
+ * SPL_EINVAL, before anything touches the device: everything the step refuses (its d_state_out may be NULL here); a null or short draft
+ * struct; an unknown draft flag; row_len above SPL_DRAFT_MAX_NODES; a null d_ok or d_mask; d_parent not 4-byte aligned;
+ * SPL_DRAFT_PARENT_PER_SEQ without d_parent; (1 + row_len) * n_seqs >= 2^31; any output coinciding with any input or other output. */
+#define SPL_DRAFT_MAX_NODES      64
+#define SPL_DRAFT_PARENT_PER_SEQ 1u  /* d_parent is [n_seqs, row_len]; default one row [row_len] for all sequences */
+
+typedef struct spl_draft_out {
+    uint32_t struct_size, flags;          /* flags: SPL_DRAFT_PARENT_PER_SEQ */
+    const int32_t* d_parent;              /* NULL: a chain */
+    int32_t* d_mask;                      /* [n_seqs, 1 + row_len, n_words] */
+    uint8_t* d_ok;                        /* [n_seqs, row_len] */
+    uint8_t* d_live;                      /* [n_seqs, 1 + row_len]; NULL ok */
+    uint64_t* d_state_out;                /* [n_seqs, 1 + row_len, STATE_WORDS]; NULL ok */
+} spl_draft_out;
+
+int spl_dfa_draft_device(spl_tokenizer* t, const spl_dfa_in* in, const spl_dfa_opts* o, const spl_draft_out* draft, void* hip_stream);
+int spl_nest_draft_device(spl_tokenizer* t, const spl_nest_in* in, const spl_nest_opts* o, const spl_draft_out* draft, void* hip_stream);
+
 /* Host-side lookup of ONE id, for consumers that decode token by token on the CPU -- the streaming
  * decoders (src/core/streaming.rs, src/python/bindings.rs:465-834 take clones of Tokenizer::decoder
  * and special_tokens_decoder).  *bytes / *len = what decode_bytes emits for the id; the pointer

@@ -38,6 +38,7 @@ SYMBOLS = [
     "spl_choice_reserve_device", "spl_choice_step_device",
     "spl_dfa_reserve_device", "spl_dfa_index_device", "spl_dfa_step_device", "spl_dfa_jump_index_device", "spl_dfa_jump_device",
     "spl_nest_reserve_device", "spl_nest_index_device", "spl_nest_step_device",
+    "spl_dfa_draft_device", "spl_nest_draft_device",
 ]
 SPL_PATTERN_CUSTOM = 3
 SPL_OPT_BYTE_LEVEL = 1
@@ -63,6 +64,7 @@ SPL_DFA_DEAD, SPL_DFA_MAX_STATES, SPL_DFA_STATE_WORDS, SPL_DFA_MAX_END = 0xFFFF,
 SPL_DFA_JUMP_MAX_BYTES, SPL_DFA_JUMP_MAX_IDS = 64, 64
 SPL_NEST_KEEP_FREE, SPL_NEST_I64, SPL_NEST_PUSH, SPL_NEST_POP = 2, 4, 0x10, 0x20
 SPL_NEST_MAX_STATES, SPL_NEST_MAX_RET, SPL_NEST_MAX_DEPTH, SPL_NEST_STATE_WORDS, SPL_NEST_MAX_END = 4096, 4096, 64, 5, 8
+SPL_DRAFT_MAX_NODES, SPL_DRAFT_PARENT_PER_SEQ = 64, 1
 SPL_ECAPACITY = -3
 
 
@@ -312,6 +314,15 @@ class SplNestOut(ctypes.Structure):
         super().__init__(ctypes.sizeof(SplNestOut), 0, state, mask, live)
 
 
+class SplDraftOut(ctypes.Structure):
+    """spl_draft_out: the draft's parents (None: a chain) and where the rows of a draft call go, device addresses (None: not wanted)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("d_parent", ctypes.c_void_p), ("d_mask", ctypes.c_void_p),
+                ("d_ok", ctypes.c_void_p), ("d_live", ctypes.c_void_p), ("d_state_out", ctypes.c_void_p)]
+
+    def __init__(self, flags=0, parent=None, mask=None, ok=None, live=None, state=None):
+        super().__init__(ctypes.sizeof(SplDraftOut), flags, parent, mask, ok, live, state)
+
+
 _lib = None
 
 
@@ -453,6 +464,8 @@ def lib() -> ctypes.CDLL:
     L.spl_nest_reserve_device.argtypes = [vp]
     L.spl_nest_index_device.argtypes = [vp, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), vp]
     L.spl_nest_step_device.argtypes = [vp, ctypes.POINTER(SplNestIn), ctypes.POINTER(SplNestOpts), ctypes.POINTER(SplNestOut), vp]
+    L.spl_dfa_draft_device.argtypes = [vp, ctypes.POINTER(SplDfaIn), ctypes.POINTER(SplDfaOpts), ctypes.POINTER(SplDraftOut), vp]
+    L.spl_nest_draft_device.argtypes = [vp, ctypes.POINTER(SplNestIn), ctypes.POINTER(SplNestOpts), ctypes.POINTER(SplDraftOut), vp]
     _lib = L
     return L
 

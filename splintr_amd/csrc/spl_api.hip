@@ -1,7 +1,7 @@
 // spl_api.hip -- the C ABI (include/splintr_hip.h): the root of the library's one HIP translation unit.  It includes the kernels
 // (spl_kernels.hip) and the host side, one file per concern and each building on the ones before it -- spl_host_res.h (resource owners,
 // pinned pool), spl_ctx.h (per-GPU context, handle, uploads), spl_streams.h (stream probe), spl_launch.h (memo, launch order, device
-// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_pair_host.h, spl_chat_host.h, spl_seqpack_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h, spl_seqscan_host.h, spl_stream_host.h, spl_stop_host.h, spl_heal_host.h, spl_mask_host.h, spl_choice_host.h, spl_dfa_host.h, spl_dfa_jump_host.h, spl_nest_host.h -- and holds the entry points.
+// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_pair_host.h, spl_chat_host.h, spl_seqpack_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h, spl_seqscan_host.h, spl_stream_host.h, spl_stop_host.h, spl_heal_host.h, spl_mask_host.h, spl_choice_host.h, spl_dfa_host.h, spl_dfa_jump_host.h, spl_nest_host.h, spl_draft_host.h -- and holds the entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -55,6 +55,7 @@ using namespace spl;
 #include "spl_dfa_host.h"
 #include "spl_dfa_jump_host.h"
 #include "spl_nest_host.h"
+#include "spl_draft_host.h"
 
 namespace {
 // No exception crosses the C ABI: every entry point that allocates (std::bad_alloc), starts threads or grows
@@ -539,6 +540,14 @@ int spl_nest_index_device(spl_tokenizer* t, const uint8_t* d_table, uint32_t n_s
 
 int spl_nest_step_device(spl_tokenizer* t, const spl_nest_in* in, const spl_nest_opts* o, const spl_nest_out* out, void* hip_stream) {
     return guarded("spl_nest_step_device", [&] { return nest_step_device(t, in, o, out, (hipStream_t)hip_stream); });
+}
+
+int spl_dfa_draft_device(spl_tokenizer* t, const spl_dfa_in* in, const spl_dfa_opts* o, const spl_draft_out* draft, void* hip_stream) {
+    return guarded("spl_dfa_draft_device", [&] { return dfa_draft_device(t, in, o, draft, (hipStream_t)hip_stream); });
+}
+
+int spl_nest_draft_device(spl_tokenizer* t, const spl_nest_in* in, const spl_nest_opts* o, const spl_draft_out* draft, void* hip_stream) {
+    return guarded("spl_nest_draft_device", [&] { return nest_draft_device(t, in, o, draft, (hipStream_t)hip_stream); });
 }
 
 int spl_utf8_mask_reserve_device(spl_tokenizer* t) {

@@ -172,15 +172,22 @@ SPL_HD void df_step_id(const HlTab& t, const DfTab& d, const DfIn& a, uint32_t i
     if (is_id && df_is_end(a, id) && df_ends(d, s.q)) s.done = true;
     else { s.broken = true; s.q = 0; }
 }
+// entry i of row b of the ids: false for an int64 value outside 32 bits (id is then its low half, which no rule reads)
+SPL_HD bool df_read_id(const DfIn& a, uint64_t b, uint32_t i, uint32_t& id) {
+    if (a.flags & DF_I64) {
+        const uint64_t v = static_cast<const uint64_t*>(a.ids)[b * a.row_len + i];
+        id = (uint32_t)v;
+        return (v >> 32) == 0;
+    }
+    id = static_cast<const uint32_t*>(a.ids)[b * a.row_len + i];
+    return true;
+}
 // THE WALK: the row's valid ids in order, while the sequence is constrained (the same for every lane: a serial walk)
 SPL_HD void df_step_seq(const HlTab& t, const DfTab& d, const DfIn& a, uint64_t b, DfState& s) {
     const uint32_t n = df_row_n(a, b);
     for (uint32_t i = 0; i < n && s.con; i++) {
-        uint32_t id; bool is_id = true;
-        if (a.flags & DF_I64) {
-            const uint64_t v = static_cast<const uint64_t*>(a.ids)[b * a.row_len + i];
-            is_id = (v >> 32) == 0; id = (uint32_t)v;
-        } else id = static_cast<const uint32_t*>(a.ids)[b * a.row_len + i];
+        uint32_t id;
+        const bool is_id = df_read_id(a, b, i, id);
         df_step_id(t, d, a, id, is_id, s);
     }
 }

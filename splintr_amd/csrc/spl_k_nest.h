@@ -245,23 +245,24 @@ SPL_HD uint64_t ns_word(const DfState& st, const NsStack& s, uint32_t i) {
     if (!st.con) return 0ull;
     return i == 1 ? s.w0 : (i == 2 ? s.w1 : (i == 3 ? s.w2 : s.w3));
 }
+// one id of a constrained sequence: df_step_id's, over configurations
+SPL_HD void ns_step_id(const HlTab& t, const NsTab& d, const NsStep& p, const DfIn& a, uint32_t id, bool is_id, DfState& st, NsStack& s) {
+    uint32_t tl = 0;
+    const uint8_t* tb = is_id ? df_bytes(t, id, tl) : nullptr;
+    NsStack s1 = s;
+    const uint32_t q1 = tb ? ns_walk(d, st.q, s1, tb, tl, p.max_depth) : DF_DEAD;
+    if (q1 != DF_DEAD) { st.q = q1; s = s1; return; }
+    st.con = false;
+    if (is_id && df_is_end(a, id) && ns_ends(d, st.q, s)) st.done = true;
+    else { st.broken = true; st.q = 0; }
+}
 // THE WALK of the step's ids, serial and the same for every lane: df_step_seq's, over configurations
 SPL_HD void ns_step_seq(const HlTab& t, const NsTab& d, const NsStep& p, const DfIn& a, uint64_t b, DfState& st, NsStack& s) {
     const uint32_t n = df_row_n(a, b);
     for (uint32_t i = 0; i < n && st.con; i++) {
-        uint32_t id; bool is_id = true;
-        if (a.flags & DF_I64) {
-            const uint64_t v = static_cast<const uint64_t*>(a.ids)[b * a.row_len + i];
-            is_id = (v >> 32) == 0; id = (uint32_t)v;
-        } else id = static_cast<const uint32_t*>(a.ids)[b * a.row_len + i];
-        uint32_t tl = 0;
-        const uint8_t* tb = is_id ? df_bytes(t, id, tl) : nullptr;
-        NsStack s1 = s;
-        const uint32_t q1 = tb ? ns_walk(d, st.q, s1, tb, tl, p.max_depth) : DF_DEAD;
-        if (q1 != DF_DEAD) { st.q = q1; s = s1; continue; }
-        st.con = false;
-        if (is_id && df_is_end(a, id) && ns_ends(d, st.q, s)) st.done = true;
-        else { st.broken = true; st.q = 0; }
+        uint32_t id;
+        const bool is_id = df_read_id(a, b, i, id);
+        ns_step_id(t, d, p, a, id, is_id, st, s);
     }
 }
 // does the dependent id `id` live from (q, s): a lane's own copy of the stack
@@ -362,12 +363,11 @@ template <class O> struct NsMaskOnly {
     SPL_HD void put(uint64_t b, uint32_t k, uint32_t v) const { o.put(b, k, v); }
     SPL_HD void put4(uint64_t b, uint32_t k, const uint32_t* v) const { o.put4(b, k, v); }
 };
-// everything of sequence b: the walk, the settle and the row write.  out: state(b, word index, value), alive, put, put4.
+// THE SETTLE AND THE ROW WRITE of the configuration (st, s) a walk arrived at, into row b of the outputs.  out: state(b, word index,
+// value), alive, put, put4.
 template <class W, class O>
-SPL_HD void ns_seq(W& w, const HlTab& t, const NsTab& d, const NsIndex& x, const NsStep& p, const DfIn& a, uint64_t b, const O& out) {
-    NsStack s;
-    DfState st = ns_load(d, p, a.state_in + b * NS_STATE_WORDS, s);              // (state_out may be state_in: the row is read here, written once below)
-    ns_step_seq(t, d, p, a, b, st, s);
+SPL_HD void ns_finish(W& w, const HlTab& t, const NsTab& d, const NsIndex& x, const NsStep& p, const DfIn& a, uint64_t b, DfState st, const NsStack& s,
+                      const O& out) {
     bool ends = false;
     uint32_t n_dep = 0;
     if (st.con) {
@@ -388,6 +388,14 @@ SPL_HD void ns_seq(W& w, const HlTab& t, const NsTab& d, const NsIndex& x, const
     // no dependent id (or a row of ones): the regex guide's own row write
     const DfIndex dx{x.rows, x.some, x.stride};
     df_write(w, dx, a, b, st, st.con && ends, NsMaskOnly<O>{out});
+}
+// everything of sequence b: the walk, the settle and the row write
+template <class W, class O>
+SPL_HD void ns_seq(W& w, const HlTab& t, const NsTab& d, const NsIndex& x, const NsStep& p, const DfIn& a, uint64_t b, const O& out) {
+    NsStack s;
+    DfState st = ns_load(d, p, a.state_in + b * NS_STATE_WORDS, s);              // (state_out may be state_in: the row is read here, written once below)
+    ns_step_seq(t, d, p, a, b, st, s);
+    ns_finish(w, t, d, x, p, a, b, st, s, out);
 }
 
 #if defined(__HIPCC__)

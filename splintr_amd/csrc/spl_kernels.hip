@@ -37,6 +37,7 @@
 //   spl_k_dfa.h        k_dfa_index / k_dfa_some / k_dfa_step: the regex guide -- a byte DFA's state x vocabulary index built on the device, and per-sequence DFA states to allowed-token bitmasks [B, n_words] by a row copy (and their host-testable first half)
 //   spl_k_dfa_jump.h   k_dfa_force / k_dfa_runs / k_dfa_jump_len / _write / _one / k_dfa_jump_scatter / k_dfa_jump: jump-forward for the regex guide -- the forced byte runs of every state found and encoded once, a step then emits a state's run as ids beside the mask (and their host-testable first half)
 //   spl_k_nest.h       k_nest_index / k_nest_count / k_nest_scan / k_nest_write / k_nest_step: nested languages (JSON mode) -- a byte automaton with push and pop ops and a 64-level stack per sequence; the stack-free part of a mask row is a row copy, the few ids that touch the stack are walked against it and merged in LDS before the copy (and their host-testable first half)
+//   spl_k_draft.h      k_dfa_draft / k_nest_draft: draft verification for the regex and nest guides -- from one state row per sequence and a draft chain or tree of up to 64 ids, the mask in front of the draft and behind every draft id, and whether each id is acceptable; a wavefront per (sequence, row) walks the node's path and takes the step's settle and row write (and their host-testable first half)
 //   (spl_rx_split.h, included by spl_api.hip: the device splitter for custom split patterns; its host half is in spl_launch.h)
 // (The multi-pass pipeline of rounds 1-3 -- k_bpe_lanes64, k_count, k_scan, k_compact_docs and the k_pretok
 //  instantiations without tile records -- was removed in round 4: no BASELINE configuration reached it.)
@@ -213,3 +214,4 @@ __device__ __forceinline__ uint32_t tidx() {
 #include "spl_k_dfa.h"
 #include "spl_k_dfa_jump.h"
 #include "spl_k_nest.h"
+#include "spl_k_draft.h"

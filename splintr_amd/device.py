@@ -2096,6 +2096,33 @@ class RegexGuide:
                         forced_len=self.forced_len)
         return self.forced_ids, self.forced_len
 
+    def draft(self, ids: torch.Tensor, lengths: Optional[torch.Tensor] = None, parent: Optional[torch.Tensor] = None, *, states: bool = False,
+              keep_free: bool = False) -> DraftResult:
+        """A speculative sampler's draft, ids [B, K] with K <= 64 -- a chain (parent None) or a tree (parent int32 [K] or [B, K]: -1 or the
+        index of an earlier node) -> DraftResult, in ONE launch (dfa_draft_device): mask [B, 1 + K, n_words] -- row 0 in front of the first
+        draft id, row 1 + i behind node i, which is what apply(logits, mask=...) takes for the verifier's [B * (1 + K), V] logits --, ok
+        [B, K], live [B, 1 + K] and, with states=True, the state behind every node.  The guide's own state, mask and live are untouched:
+
+            d = guide.draft(drafted)                                   # drafted: [B, K] from the draft model
+            guide.apply(logits.view(B * (1 + K), V), mask=d.mask)      # the verifier's logits, every position masked
+            n = torch.minimum(d.accepted_len(), model_accepts)         # the leading ids both accept
+            guide.accept(accepted_then_bonus, n + 1)                   # [B, K + 1]: the accepted ids, then the bonus id -- ONE step
+
+        keep_free: the mask is made of ones and the rows of nodes that are not constrained are not written."""
+        _guide_draft_ids(self, ids)
+        mask = torch.full((self.batch_size, 1 + int(ids.shape[1]), self.n_words), -1, dtype=torch.int32, device=self._state.device) if keep_free else None
+        return dfa_draft_device(self._tok, ids, lengths, self._state, self.table, self.index, end_ids=self.end_ids, parent=parent, n_states=self.n_states,
+                                keep_free=keep_free, states=states, mask=mask, n_words=self.n_words)
+
+    def accept(self, ids: Optional[torch.Tensor], lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The ordinary step under the name a speculative loop wants: the accepted draft ids and the bonus id in one call -> the mask."""
+        return self._call(ids, lengths, False)
+
+    def accept_node(self, draft: DraftResult, node) -> torch.Tensor:
+        """The guide adopts the state behind node[b] of a draft made with states=True (-1: the root -- nothing was accepted) -> the mask.
+        A gather of the draft's state, mask and live rows; no step is run."""
+        return _guide_accept_node(self, draft, node)
+
     def forced_text(self, q: int) -> bytes:
         """The bytes state q (of the stacked table) forces: run(q) of include/splintr_hip.h, capped at 64 bytes and trimmed to a character
         boundary; b"" where the state leaves a choice or accepts.  From a host copy made at construction."""
@@ -2118,13 +2145,11 @@ class RegexGuide:
             if self.forced_len is not None:
                 self.forced_len[rows] = 0
 
-    def apply(self, logits: torch.Tensor, *, live_only: bool = False) -> torch.Tensor:
+    def apply(self, logits: torch.Tensor, *, live_only: bool = False, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """logits [B, V] (float32, float16 or bfloat16) with -inf wherever the mask forbids the id, IN PLACE: one launch of
         mask_apply_device.  live_only: the rows of sequences that are not constrained (`live` 0) are skipped -- their mask rows hold ones,
-        so the result is the same."""
-        if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.shape[0] != self.batch_size:
-            raise ValueError("logits must have shape [batch, vocabulary]")
-        return mask_apply_device(self._tok, logits, self.mask, live=self.live if live_only else None)
+        so the result is the same.  mask: a draft's mask [B, 1 + K, n_words] in place of the guide's own, for logits [B * (1 + K), V]."""
+        return _guide_apply(self, logits, mask, live_only)
 
     @property
     def state(self) -> torch.Tensor:
@@ -2386,12 +2411,31 @@ class NestGuide:
             self.mask[rows] = -1
             self.live[rows] = 0
 
-    def apply(self, logits: torch.Tensor, *, live_only: bool = False) -> torch.Tensor:
+    def draft(self, ids: torch.Tensor, lengths: Optional[torch.Tensor] = None, parent: Optional[torch.Tensor] = None, *, states: bool = False,
+              keep_free: bool = False) -> DraftResult:
+        """RegexGuide.draft's, over configurations (nest_draft_device, ONE launch): the masks in front of and behind every node of a
+        draft chain or tree, ok per node, live and -- with states=True -- the state and stack behind every node.  The guide's own state
+        is untouched."""
+        _guide_draft_ids(self, ids)
+        mask = torch.full((self.batch_size, 1 + int(ids.shape[1]), self.n_words), -1, dtype=torch.int32, device=self._state.device) if keep_free else None
+        return nest_draft_device(self._tok, ids, lengths, self._state, self.table, self.index, n_states=self.n_states, n_ret=self.n_ret, dep_cap=self.n_dep,
+                                 end_ids=self.end_ids, max_depth=self.max_depth, parent=parent, keep_free=keep_free, states=states, mask=mask,
+                                 n_words=self.n_words)
+
+    def accept(self, ids: Optional[torch.Tensor], lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The ordinary step under the name a speculative loop wants: the accepted draft ids and the bonus id in one call -> the mask."""
+        return self._call(ids, lengths, False)
+
+    def accept_node(self, draft: DraftResult, node) -> torch.Tensor:
+        """The guide adopts the state and stack behind node[b] of a draft made with states=True (-1: the root) -> the mask.  A gather of
+        the draft's state, mask and live rows; no step is run."""
+        return _guide_accept_node(self, draft, node)
+
+    def apply(self, logits: torch.Tensor, *, live_only: bool = False, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """logits [B, V] (float32, float16 or bfloat16) with -inf wherever the mask forbids the id, IN PLACE: one launch of
-        mask_apply_device.  live_only: the rows of sequences that are not constrained (`live` 0) are skipped."""
-        if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.shape[0] != self.batch_size:
-            raise ValueError("logits must have shape [batch, vocabulary]")
-        return mask_apply_device(self._tok, logits, self.mask, live=self.live if live_only else None)
+        mask_apply_device.  live_only: the rows of sequences that are not constrained (`live` 0) are skipped.  mask: a draft's mask
+        [B, 1 + K, n_words] in place of the guide's own, for logits [B * (1 + K), V]."""
+        return _guide_apply(self, logits, mask, live_only)
 
     @property
     def state(self) -> torch.Tensor:
@@ -2423,6 +2467,169 @@ class NestGuide:
 
     def __repr__(self) -> str:
         return f"NestGuide(batch_size={self.batch_size}, n_states={self.n_states}, n_dep={self.n_dep}, max_depth={self.max_depth}, n_words={self.n_words})"
+
+
+# ---------------------------------------------------------------------------------------------- draft verification: the guides behind a speculative sampler
+class DraftResult:
+    """What a draft call wrote: mask int32 [B, 1 + K, n_words] (row 0 in front of the first draft id, row 1 + i behind node i), ok uint8
+    [B, K] (1: every id of the node's path is acceptable), live uint8 [B, 1 + K], state int64 [B, 1 + K] (regex) / [B, 1 + K, 5] (nest),
+    or None where the states were not asked for."""
+
+    def __init__(self, mask, ok, live, state, tree: bool):
+        self.mask, self.ok, self.live, self.state, self.tree = mask, ok, live, state, bool(tree)
+
+    def accepted_len(self) -> torch.Tensor:
+        """int64 [B]: the leading draft ids of a CHAIN the guide accepts (ok is monotone along a chain, so this is its sum)."""
+        if self.tree:
+            raise ValueError("accepted_len is a chain's: a tree has no leading ids (read ok per node)")
+        return self.ok.sum(1)
+
+    def __repr__(self) -> str:
+        return f"DraftResult(mask={tuple(self.mask.shape)}, states={self.state is not None}, tree={self.tree})"
+
+
+def check_draft_args(ids, parent, *, keep_free: bool = False, mask=None, n_words=None, state_words: int = 1) -> None:
+    """ValueError for what a draft call refuses beyond the step's own checks (check_dfa_args / check_nest_args run on the same ids): the
+    ids must be [batch, nodes] with at most 64 nodes, the parents int32 [nodes] or [batch, nodes] on the device of the ids, the caller's
+    mask [batch, 1 + nodes, n_words]."""
+    if not isinstance(ids, torch.Tensor) or ids.dim() != 2:
+        raise ValueError("the draft ids must have rank 2 ([batch, nodes])")
+    B, K = int(ids.shape[0]), int(ids.shape[1])
+    if K > _ffi.SPL_DRAFT_MAX_NODES:
+        raise ValueError(f"a draft has at most {_ffi.SPL_DRAFT_MAX_NODES} nodes, not {K}")
+    if (1 + K) * B >= (1 << 31):
+        raise ValueError("(1 + nodes) * batch must be below 2**31")
+    if parent is not None:
+        if not isinstance(parent, torch.Tensor) or parent.dtype != torch.int32 or not parent.is_contiguous() or tuple(parent.shape) not in ((K,), (B, K)):
+            raise ValueError("parent must be a contiguous int32 tensor of shape [nodes] (one tree for all sequences) or [batch, nodes]")
+        if parent.device != ids.device:
+            raise ValueError("parent must be on the device of the ids")
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.int32 or mask.dim() != 3 or mask.shape[0] != B or mask.shape[1] != 1 + K or \
+                not mask.is_contiguous() or (n_words is not None and mask.shape[2] != int(n_words)):
+            raise ValueError("mask must be a contiguous int32 tensor of shape [batch, 1 + nodes, n_words]")
+        if mask.device != ids.device:
+            raise ValueError("mask must be on the device of the ids")
+    elif keep_free:
+        raise ValueError("keep_free needs the caller's mask (the rows of nodes that are not constrained filled with ones once)")
+
+
+def _draft_out(ids, parent, keep_free, mask, n_words, states, state_shape):
+    """the outputs of a draft call and its spl_draft_out (the tensors are returned too: they must outlive the call's arguments)"""
+    dev, B, K = ids.device, int(ids.shape[0]), int(ids.shape[1])
+    if mask is None:
+        mask = torch.empty((B, 1 + K, n_words), dtype=torch.int32, device=dev)     # (every word of every row is written by the kernel)
+    ok = torch.empty((B, K), dtype=torch.uint8, device=dev)
+    live = torch.empty((B, 1 + K), dtype=torch.uint8, device=dev)
+    state = torch.empty((B, 1 + K) + state_shape, dtype=torch.int64, device=dev) if states else None
+    per_seq = parent is not None and parent.dim() == 2
+    # (null mask and ok pointers are refused by the library: an empty batch or an empty draft passes addresses of its own, which nothing dereferences)
+    spare = torch.empty(8, dtype=torch.int64, device=dev).data_ptr() if (B == 0 or K == 0) else 0
+    d = _ffi.SplDraftOut(_ffi.SPL_DRAFT_PARENT_PER_SEQ if per_seq and parent.numel() else 0, _ptr(parent), _ptr(mask) or spare, _ptr(ok) or spare + 16,
+                         _ptr(live), _ptr(state))
+    return d, DraftResult(mask, ok, live, state, parent is not None)
+
+
+def dfa_draft_device(tok: Tokenizer, ids: torch.Tensor, lengths: Optional[torch.Tensor], state: torch.Tensor, table: torch.Tensor, index: torch.Tensor, *,
+                     end_ids, parent: Optional[torch.Tensor] = None, n_states: Optional[int] = None, keep_free: bool = False, states: bool = False,
+                     mask: Optional[torch.Tensor] = None, n_words: Optional[int] = None) -> DraftResult:
+    """The regex guide over a DRAFT (spl_dfa_draft_device), ONE launch on torch's current stream; nothing synchronises and `state` is only
+    read.  ids [B, K] int32 / int64, K <= 64: the draft's nodes (a sequence's first lengths[b] count, the others are absent); parent None:
+    a chain; int32 [K] or [B, K]: per node -1 (it hangs below the sequence's state) or the index of an earlier node.  Returns a
+    DraftResult: mask row 0 is the mask in front of the first draft id, row 1 + i the mask behind node i; ok[b, i] is 1 iff every id on
+    the way to node i is one the guide accepts; live and -- with states=True -- state hold what dfa_step_device would have written had it
+    been given the node's path.  keep_free: the rows of nodes that are not constrained are not written -- pass the mask whose rows hold
+    ones already."""
+    if n_states is None:
+        if not isinstance(table, torch.Tensor) or table.dim() != 1 or table.shape[0] % 513:
+            raise ValueError("table must be a contiguous uint8 tensor of shape [n_states * 513] (dfa_table)")
+        n_states = int(table.shape[0]) // 513
+    if mask is None and n_words is None:
+        n_words = dfa_n_words(tok)
+    check_draft_args(ids, parent, keep_free=keep_free, mask=mask, n_words=n_words)
+    n_words = int(mask.shape[2]) if mask is not None else int(n_words)
+    check_dfa_args(ids, lengths, state, table, index, n_states, end_ids=end_ids, n_words=n_words)
+    B, K = int(ids.shape[0]), int(ids.shape[1])
+    ends = _dfa_end_ids(end_ids, n_words)
+    d, res = _draft_out(ids, parent, keep_free, mask, n_words, states, ())
+    flags = (_ffi.SPL_DFA_KEEP_FREE if keep_free else 0) | (_ffi.SPL_DFA_I64 if ids.dtype == torch.int64 else 0)
+    spare = torch.empty(8, dtype=torch.int64, device=ids.device).data_ptr() if B == 0 else 0
+    si = _ffi.SplDfaIn(B, K, _ptr(ids), _ptr(lengths), _ptr(state) or spare, _ptr(table), _ptr(index), int(n_states))
+    o = _ffi.SplDfaOpts(flags, n_words, ends)
+    rc = _ffi.lib().spl_dfa_draft_device(tok.handle, ctypes.byref(si), ctypes.byref(o), ctypes.byref(d), torch.cuda.current_stream(ids.device).cuda_stream)
+    if rc != 0:
+        _raise_rc(rc, "spl_dfa_draft_device")
+    return res
+
+
+def nest_draft_device(tok: Tokenizer, ids: torch.Tensor, lengths: Optional[torch.Tensor], state: torch.Tensor, table: torch.Tensor, index: torch.Tensor, *,
+                      n_states: int, n_ret: int, dep_cap: int, end_ids, max_depth: int = 64, parent: Optional[torch.Tensor] = None, keep_free: bool = False,
+                      states: bool = False, mask: Optional[torch.Tensor] = None, n_words: Optional[int] = None) -> DraftResult:
+    """The nest guide over a DRAFT (spl_nest_draft_device): dfa_draft_device's, over configurations -- state int64 [B, 5] is only read, a
+    DraftResult's state is int64 [B, 1 + K, 5]."""
+    if mask is None and n_words is None:
+        n_words = dfa_n_words(tok)
+    check_draft_args(ids, parent, keep_free=keep_free, mask=mask, n_words=n_words)
+    n_words = int(mask.shape[2]) if mask is not None else int(n_words)
+    check_nest_args(ids, lengths, state, table, index, n_states, n_ret, dep_cap, end_ids=end_ids, max_depth=max_depth, n_words=n_words)
+    B, K = int(ids.shape[0]), int(ids.shape[1])
+    ends = _dfa_end_ids(end_ids, n_words)
+    d, res = _draft_out(ids, parent, keep_free, mask, n_words, states, (_ffi.SPL_NEST_STATE_WORDS,))
+    flags = (_ffi.SPL_NEST_KEEP_FREE if keep_free else 0) | (_ffi.SPL_NEST_I64 if ids.dtype == torch.int64 else 0)
+    spare = torch.empty(8, dtype=torch.int64, device=ids.device).data_ptr() if B == 0 else 0
+    si = _ffi.SplNestIn(B, K, _ptr(ids), _ptr(lengths), _ptr(state) or spare, _ptr(table), _ptr(index), int(n_states), int(n_ret), int(dep_cap),
+                        int(index.numel()))
+    o = _ffi.SplNestOpts(flags, n_words, ends, int(max_depth))
+    rc = _ffi.lib().spl_nest_draft_device(tok.handle, ctypes.byref(si), ctypes.byref(o), ctypes.byref(d), torch.cuda.current_stream(ids.device).cuda_stream)
+    if rc != 0:
+        _raise_rc(rc, "spl_nest_draft_device")
+    return res
+
+
+def _guide_draft_ids(guide, ids):
+    if not isinstance(ids, torch.Tensor) or ids.dim() != 2 or ids.shape[0] != guide.batch_size:
+        raise ValueError("the draft ids must have shape [batch, nodes]")
+    return ids
+
+
+def _guide_accept_node(guide, draft: DraftResult, node) -> torch.Tensor:
+    """the state, mask and live rows of node[b] (-1: the root) of a draft become the guide's: three gathers, no kernel of the library"""
+    if not isinstance(draft, DraftResult):
+        raise ValueError("draft must be what draft() returned")
+    if draft.state is None:
+        raise ValueError("accept_node needs the states behind the nodes: call draft(..., states=True)")
+    B, rows = guide.batch_size, int(draft.mask.shape[1])
+    if draft.mask.shape[0] != B or draft.mask.shape[2] != guide.n_words:
+        raise ValueError("the draft is not this guide's")
+    on_host = not (isinstance(node, torch.Tensor) and node.is_cuda)
+    node = torch.as_tensor(node)
+    if node.dtype not in (torch.int32, torch.int64) or node.shape != (B,):
+        raise ValueError("node must hold one integer per sequence: -1 (the root) or a node of the draft")
+    if on_host and B and (int(node.min()) < -1 or int(node.max()) > rows - 2):
+        raise ValueError(f"node must be in -1 .. {rows - 2}")
+    # (a tensor on the device is not read back: a value outside -1 .. nodes - 1 is clamped to that range, nothing synchronises)
+    at = (node.to(guide._state.device, torch.int64) + 1).clamp_(0, rows - 1)
+    b = torch.arange(B, device=at.device)
+    guide._state.copy_(draft.state[b, at])
+    guide.mask.copy_(draft.mask[b, at])
+    guide.live.copy_(draft.live[b, at])
+    return guide.mask
+
+
+def _guide_apply(guide, logits, mask, live_only):
+    """logits [R, V] against the guide's own mask (R = batch) or against the rows of a draft's mask ([B, 1 + K, n_words] or [R, n_words])"""
+    if mask is None:
+        if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.shape[0] != guide.batch_size:
+            raise ValueError("logits must have shape [batch, vocabulary]")
+        return mask_apply_device(guide._tok, logits, guide.mask, live=guide.live if live_only else None)
+    if live_only:
+        raise ValueError("live_only goes with the guide's own mask")
+    if not isinstance(mask, torch.Tensor) or mask.dim() not in (2, 3) or mask.shape[-1] != guide.n_words or not mask.is_contiguous():
+        raise ValueError("mask must be a contiguous tensor of shape [batch, 1 + nodes, n_words] (a draft's) or [rows, n_words]")
+    rows = mask.view(-1, guide.n_words)
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.shape[0] != rows.shape[0]:
+        raise ValueError("logits must have shape [rows of the mask, vocabulary]")
+    return mask_apply_device(guide._tok, logits, rows)
 
 
 class Comm:

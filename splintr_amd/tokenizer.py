@@ -619,7 +619,9 @@ class Tokenizer:
         follows the sampler, and `mask` -- int32 [B, n_words], the apply_token_bitmask layout -- holds the ids the automaton can walk
         on with.  end_ids: the ids (usually specials, 1 .. 8) that may follow an accepting state and end the sequence.  `done`, `broken`
         and `live` read the state on the device.  jump=True adds jump-forward: jump(ids) is step(ids) that also returns, as ids
-        (int32 [B, jump_ids] and their counts), the run the automaton forces behind them -- tokens that need no forward pass."""
+        (int32 [B, jump_ids] and their counts), the run the automaton forces behind them -- tokens that need no forward pass.
+        Behind a speculative sampler: draft(ids, lengths, parent) gives, in one launch and without moving the guide, the mask in front of
+        and behind every id of a draft chain or tree and whether each id is acceptable; accept(ids, lengths) commits."""
         from . import device as dv
         return dv.RegexGuide(self, batch_size, pattern_or_patterns, end_ids=end_ids, n_words=n_words, jump=jump, jump_ids=jump_ids)
 
@@ -628,7 +630,8 @@ class Tokenizer:
         of regular pieces inside nested brackets, given as a splintr_amd.nest.NestTable -- a byte automaton whose transitions may push
         and pop a stack of at most max_depth (1 .. 64) 4-bit symbols per sequence.  begin() writes the start state and the first masks,
         step(ids) follows the sampler, `mask` holds the ids the next step may draw.  end_ids: the ids (usually specials, 1 .. 8) that
-        may follow an accepting state with an empty stack and end the sequence.  `done`, `broken`, `live` and `depth` read the device."""
+        may follow an accepting state with an empty stack and end the sequence.  `done`, `broken`, `live` and `depth` read the device.
+        draft(ids, lengths, parent), accept and accept_node serve a speculative sampler as the regex guide's do."""
         from . import device as dv
         return dv.NestGuide(self, batch_size, table, end_ids=end_ids, max_depth=max_depth, n_words=n_words)
 
