@@ -211,7 +211,15 @@ void spl_host_free(void* p);
  *                         d_doc_off[n_docs]==n_bytes
  *   d_ids[ids_capacity]   output ids; n_bytes entries always suffice
  *   d_out_off[n_docs+1]   output offsets; d_out_off[n_docs] is the total token count
- * Tokens beyond ids_capacity are dropped (compare d_out_off[n_docs] with the capacity).
+ * What the call promises about the caller's buffers, in every execution mode and for every entry point that takes these arguments
+ * (_packed, spl_encode_chunks_device, handles with SPL_PATTERN_CUSTOM; tests/test_gpu_encode_buffers.py), T being the token count:
+ *   capacity   Tokens beyond ids_capacity are dropped (compare d_out_off[n_docs] with the capacity): d_ids[0 .. min(T, ids_capacity))
+ *              are the first ids of the result, d_out_off is complete whatever the capacity is -- d_out_off[n_docs] == T, the NEED --
+ *              and nothing is stored at or beyond d_ids[ids_capacity].  ids_capacity 0 is allowed (d_ids must still be a valid pointer).
+ *   footprint  Nothing is stored at or beyond d_ids[T] either: with ids_capacity > T the entries d_ids[T .. ids_capacity) keep what the
+ *              caller left in them.  Nothing is stored in front of d_ids[0] or outside d_out_off[0 .. n_docs].
+ *   text tail  The bytes behind d_utf8[n_bytes] (up to the next multiple of 16) are read but never looked at: the result is that of
+ *              the n_bytes bytes alone, whatever follows them -- zeros, text that would continue the last chunk, invalid UTF-8.
  * Size limits of ONE device call (SPL_EINVAL beyond them; spl_encode_batch on host buffers has none, it feeds
  * chunks of at most 5 MiB): n_bytes < 2^31 - 65536 (2047 MiB) without SPL_WITH_SPECIAL, n_bytes <= 256 MB with it and for handles with
  * SPL_PATTERN_CUSTOM (the special-token scan and the device splitter exist for the two-launch mode only).  Split a larger corpus at
@@ -277,7 +285,9 @@ int spl_gatherv_unpack(spl_tokenizer* t, const uint32_t* d_slabs, uint32_t world
 /* spl_encode_batch_device that ALSO leaves the result in slab form (the layout spl_gatherv_pack
  * makes) in d_slab[cap_words]: in tile-owned mode the last kernel writes both copies in one pass,
  * so the per-batch pack launch of a multi-GPU pipeline goes away; otherwise the pack kernel is
- * queued behind the encode. */
+ * queued behind the encode.  The slab's header and offsets are complete whatever ids_capacity is.  With ids_capacity below the token
+ * count the slab's ids at ranks >= ids_capacity are promised NOTHING: the tile-owned mode fills them from the tiles' own ids, the queued
+ * pack kernel copies min(T, slab capacity, ids_capacity) ids out of d_ids and leaves the rest of the slab as it was. */
 int spl_encode_batch_device_packed(spl_tokenizer* t, const uint8_t* d_utf8, uint64_t n_bytes, const uint64_t* d_doc_off,
                                    uint64_t n_docs, uint32_t flags, uint32_t* d_ids, uint64_t ids_capacity,
                                    uint64_t* d_out_off, uint32_t* d_slab, uint64_t cap_words, uint64_t max_docs,

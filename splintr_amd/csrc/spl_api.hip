@@ -391,7 +391,7 @@ int spl_gatherv_pack(spl_tokenizer* t, const uint32_t* d_ids, const uint64_t* d_
         return fail(SPL_EINVAL, "spl_gatherv_pack: slab too small for the document table");
     HIP_TRY(hipSetDevice(t->ctx[0]->device));
     hipLaunchKernelGGL(k_gatherv_pack, dim3(256), dim3(256), 0, (hipStream_t)hip_stream, d_ids, d_out_off, (uint32_t)n_docs,
-                       d_slab, (uint32_t)cap_words, (uint32_t)max_docs, t->slab_pack24 ? 1u : 0u);
+                       d_slab, (uint32_t)cap_words, (uint32_t)max_docs, t->slab_pack24 ? 1u : 0u, ~0ull);      // (the caller's CSR is whole)
     HIP_TRY(hipGetLastError());
     return SPL_OK;
 }

@@ -120,14 +120,17 @@ __global__ void k_ext_specials(Batch b, const uint32_t* pos, const uint32_t* id,
 // all_gather_into_tensor moves the slabs over xGMI, and every rank unpacks them into the global
 // CSR.  No host synchronisation: the token counts travel inside the slabs.
 //   slab (u32 words): [0] T  [1] N  [2 .. 2+max_docs] local out_off (N+1 used)  [2+max_docs+1 ..] ids
+//   ids_len: how many entries of ids[] exist.  Behind an encode that dropped tokens (T beyond its ids_capacity) that is the capacity, and
+//   the slab's ids at ranks >= ids_len are left as they were; for a CSR that is whole, any value >= T.
 __global__ void k_gatherv_pack(const uint32_t* ids, const uint64_t* out_off, uint32_t n_docs, uint32_t* slab,
-                               uint32_t cap_words, uint32_t max_docs, uint32_t p24) {
+                               uint32_t cap_words, uint32_t max_docs, uint32_t p24, uint64_t ids_len) {
     const uint32_t T = (uint32_t)out_off[n_docs];
     const uint32_t ids_at = 3 + max_docs, ids_cap = slab_id_cap(cap_words - ids_at, p24 != 0u);
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
     if (i == 0) { slab[0] = T; slab[1] = n_docs; }
     for (uint32_t d = i; d <= n_docs; d += stride) slab[2 + d] = (uint32_t)out_off[d];
-    const uint32_t ncopy = T < ids_cap ? T : ids_cap;        // T > ids_cap is reported by the unpacker
+    uint32_t ncopy = T < ids_cap ? T : ids_cap;              // T > ids_cap is reported by the unpacker
+    if (ncopy > ids_len) ncopy = (uint32_t)ids_len;
     for (uint32_t k = i; k < ncopy; k += stride) slab_put_id(slab + ids_at, k, ids[k], p24 != 0u);
 }
 // grid.y = source rank, grid.z = batch of the group (a rank sends `depth` slabs back to back per

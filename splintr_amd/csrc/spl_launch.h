@@ -424,9 +424,10 @@ int launch_all(spl_tokenizer* tk, Ctx* t, const LaunchReq& rq, LaunchDone* done 
         SPL_TRY(launch_owned_tiles(tk, t, rq, sh, b));
     }
     SPL_TRY(launch_error());
-    if (rq.slab && (sh.mode == TileMode::Queue || !sh.ntiles))          // the slab copy of the result, where k_tile_out did not write it
+    if (rq.slab && (sh.mode == TileMode::Queue || !sh.ntiles))          // the slab copy of the result, where k_tile_out did not write it:
+        // copied from the caller's ids, of which only ids_cap entries exist -- tokens the encode dropped are not in the slab either
         hipLaunchKernelGGL(k_gatherv_pack, dim3(256), dim3(256), 0, s, rq.ids, rq.out_off, (uint32_t)rq.n_docs, rq.slab->d_slab,
-                           (uint32_t)rq.slab->cap_words, (uint32_t)rq.slab->max_docs, tk->slab_pack24 ? 1u : 0u);
+                           (uint32_t)rq.slab->cap_words, (uint32_t)rq.slab->max_docs, tk->slab_pack24 ? 1u : 0u, rq.ids_cap);
     if (done) { done->off_host_written = b.off_out2 != nullptr; done->done_armed = b.done != nullptr; }
     if (sh.prof) SPL_TRY(read_profile(t, sh));
     return SPL_OK;
