@@ -1513,6 +1513,79 @@ typedef struct spl_draft_out {
 int spl_dfa_draft_device(spl_tokenizer* t, const spl_dfa_in* in, const spl_dfa_opts* o, const spl_draft_out* draft, void* hip_stream);
 int spl_nest_draft_device(spl_tokenizer* t, const spl_nest_in* in, const spl_nest_opts* o, const spl_draft_out* draft, void* hip_stream);
 
+/* N-GRAM DRAFTING (csrc/spl_k_ngram.h): "prompt lookup decoding", vLLM's `ngram` speculative method, on the device.  A
+ * sampler without a draft model proposes what followed the last time the sequence ended the way it ends now.  The id histories lie in
+ * HBM, where spl_pad_device, the sampler and the streaming decode leave ids; ONE call appends the ids the last step committed and writes
+ * up to SPL_NGRAM_MAX_BRANCHES draft branches per sequence -- d_ids, d_count and d_parent are what spl_dfa_draft_device /
+ * spl_nest_draft_device take as d_ids, d_len and d_parent (SPL_DRAFT_PARENT_PER_SEQ).  Nothing goes to the host.
+ *
+ * INPUT.  d_hist [n_seqs, cap], int32 or -- SPL_NGRAM_I64 -- int64; d_len int32 [n_seqs], used clamped to 0 .. cap.  Optionally the TAIL
+ * d_new [n_seqs, new_row_len] of the same type with d_new_len [n_seqs], clamped to 0 .. new_row_len (both NULL: none).
+ *   H, L        the history hist[:len] ++ new[:new_len], cut at cap, and its length.
+ *   HOLE        an element outside [0, 2^31) -- a negative int32, an int64 beyond the range.  A hole equals nothing, not even itself.
+ *   m(e)        of an END 1 <= e <= L - 1: the largest n <= min(max_n, e) with H[e - n .. e) == H[L - n .. L) element by element, no hole
+ *               among them.  H[e] always exists and may lie inside the suffix (periodic text).
+ *   CANDIDATES  the ends with m(e) >= min_n whose H[e] is no hole, by m descending, then by e descending -- SPL_NGRAM_EARLIEST: ascending.
+ *   BRANCH j    (0 <= j < branches) the j-th candidate in that order whose FIRST ID H[e] differs from the first id of every branch before
+ *               it; its ids are H[e .. min(e + depth, L)), cut in front of the first hole.
+ * OUTPUT, fully determined.  d_ids [n_seqs, branches * depth] of the input's type: branch j in columns j * depth .., missing nodes hold
+ * pad_id.  d_count, d_match, d_from int32 [n_seqs, branches]: the branch's ids (0: no branch), its m (0), its e (-1).  d_parent int32
+ * [n_seqs, branches * depth] (NULL ok for ONE branch, a chain): -1 for a branch's first node, the index in front for every other present
+ * node, -2 for a missing node -- an orphan by the draft call's rules.  THE APPEND: hist[len .. L) receives the tail, d_len[b] = L (d_len
+ * may be the input's d_len), d_full uint8 [n_seqs] (NULL ok) is 1 where len + new_len > cap; what does not fit is dropped, hist beyond L
+ * is not touched.  depth == 0 appends only and writes no draft output (those pointers may be NULL): a drafter is filled from a prompt so.
+ *
+ * SHAPE.  k_ngram: a 256-lane workgroup per (sequence, slice) streams its slice of the history in tiles of 1 024 ids, 16 bytes a lane
+ * and load, staged in LDS with the ids a run needs in front and H[e] behind; the suffix is uniform; an end is first compared with the
+ * LAST suffix id in registers, a survivor counts its run backwards through LDS and enters the lane's sorted list of the best ends with
+ * pairwise different first ids, which is max-reduced over the workgroup once per branch.  ONE pass and, with one slice, ONE launch; with
+ * S > 1 slices the slices' lists go to scratch of the handle (spl_ngram_reserve_device: 64 bytes per sequence and slice) and a second
+ * small launch, k_ngram_emit, merges them and writes the rows.  opts.slices: 0 = the library chooses from n_seqs and cap (one slice unless
+ * the batch leaves most compute units idle), else that many, at most SPL_NGRAM_MAX_SLICES (a slice is a multiple of 1 024 ids).  No
+ * global atomics, no wait between workgroups, no allocation and no synchronisation within what was reserved.  A ring buffer or sliding
+ * history, drafts across sequences, suffix automata and max_n above 8 are out of scope.
+ *
+ * SPL_EINVAL, before anything touches the device: a null handle, struct or required pointer (d_hist, both d_len, and for depth > 0 d_ids,
+ * d_count, d_match, d_from; d_parent for more than one branch; d_new without d_new_len or the reverse); a short or oversize struct_size;
+ * an unknown flag; not 1 <= min_n <= max_n <= SPL_NGRAM_MAX_N; depth above 64; branches not in 1 .. 8; branches * depth above
+ * SPL_DRAFT_MAX_NODES; slices above SPL_NGRAM_MAX_SLICES; cap above 2^24; n_seqs >= 2^31; an array not aligned to its element type; any
+ * output coinciding with an input or another output (the output d_len alone may be the input d_len); d_new overlapping d_hist. */
+#define SPL_NGRAM_I64          1u
+#define SPL_NGRAM_EARLIEST     2u   /* among ends of equal m the earliest first; default the latest */
+#define SPL_NGRAM_MAX_N        8
+#define SPL_NGRAM_MAX_DEPTH    64
+#define SPL_NGRAM_MAX_BRANCHES 8
+#define SPL_NGRAM_MAX_CAP      (1u << 24)
+#define SPL_NGRAM_MAX_SLICES   32
+
+typedef struct spl_ngram_in {
+    uint32_t struct_size, new_row_len;
+    uint64_t n_seqs;
+    void* d_hist;                         /* [n_seqs, cap]; hist[len .. L) is written */
+    const int32_t* d_len;                 /* [n_seqs] */
+    const void* d_new;                    /* [n_seqs, new_row_len]; NULL: no tail */
+    const int32_t* d_new_len;             /* [n_seqs] */
+    uint32_t cap, reserved;
+} spl_ngram_in;
+typedef struct spl_ngram_opts {
+    uint32_t struct_size, flags;          /* SPL_NGRAM_I64 | SPL_NGRAM_EARLIEST */
+    uint32_t min_n, max_n, depth, branches;
+    uint32_t pad_id, slices;              /* slices: 0 = the library chooses */
+} spl_ngram_opts;
+typedef struct spl_ngram_out {
+    uint32_t struct_size, reserved;
+    void* d_ids;                          /* [n_seqs, branches * depth] */
+    int32_t* d_count;                     /* [n_seqs, branches] */
+    int32_t* d_match;                     /* [n_seqs, branches] */
+    int32_t* d_from;                      /* [n_seqs, branches] */
+    int32_t* d_parent;                    /* [n_seqs, branches * depth]; NULL ok for one branch */
+    int32_t* d_len;                       /* [n_seqs]; may be the input's d_len */
+    uint8_t* d_full;                      /* [n_seqs]; NULL ok */
+} spl_ngram_out;
+
+int spl_ngram_reserve_device(spl_tokenizer* t, uint64_t max_seqs);
+int spl_ngram_draft_device(spl_tokenizer* t, const spl_ngram_in* in, const spl_ngram_opts* o, const spl_ngram_out* out, void* hip_stream);
+
 /* Host-side lookup of ONE id, for consumers that decode token by token on the CPU -- the streaming
  * decoders (src/core/streaming.rs, src/python/bindings.rs:465-834 take clones of Tokenizer::decoder
  * and special_tokens_decoder).  *bytes / *len = what decode_bytes emits for the id; the pointer

@@ -39,6 +39,7 @@ SYMBOLS = [
     "spl_dfa_reserve_device", "spl_dfa_index_device", "spl_dfa_step_device", "spl_dfa_jump_index_device", "spl_dfa_jump_device",
     "spl_nest_reserve_device", "spl_nest_index_device", "spl_nest_step_device",
     "spl_dfa_draft_device", "spl_nest_draft_device",
+    "spl_ngram_reserve_device", "spl_ngram_draft_device",
 ]
 SPL_PATTERN_CUSTOM = 3
 SPL_OPT_BYTE_LEVEL = 1
@@ -65,6 +66,8 @@ SPL_DFA_JUMP_MAX_BYTES, SPL_DFA_JUMP_MAX_IDS = 64, 64
 SPL_NEST_KEEP_FREE, SPL_NEST_I64, SPL_NEST_PUSH, SPL_NEST_POP = 2, 4, 0x10, 0x20
 SPL_NEST_MAX_STATES, SPL_NEST_MAX_RET, SPL_NEST_MAX_DEPTH, SPL_NEST_STATE_WORDS, SPL_NEST_MAX_END = 4096, 4096, 64, 5, 8
 SPL_DRAFT_MAX_NODES, SPL_DRAFT_PARENT_PER_SEQ = 64, 1
+SPL_NGRAM_I64, SPL_NGRAM_EARLIEST = 1, 2
+SPL_NGRAM_MAX_N, SPL_NGRAM_MAX_DEPTH, SPL_NGRAM_MAX_BRANCHES, SPL_NGRAM_MAX_CAP, SPL_NGRAM_MAX_SLICES = 8, 64, 8, 1 << 24, 32
 SPL_ECAPACITY = -3
 
 
@@ -323,6 +326,33 @@ class SplDraftOut(ctypes.Structure):
         super().__init__(ctypes.sizeof(SplDraftOut), flags, parent, mask, ok, live, state)
 
 
+class SplNgramIn(ctypes.Structure):
+    """spl_ngram_in: the histories, their lengths and the optional tail of new ids, device addresses (None: not given)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("new_row_len", ctypes.c_uint32), ("n_seqs", ctypes.c_uint64), ("d_hist", ctypes.c_void_p),
+                ("d_len", ctypes.c_void_p), ("d_new", ctypes.c_void_p), ("d_new_len", ctypes.c_void_p), ("cap", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    def __init__(self, n_seqs=0, cap=0, hist=None, lengths=None, new=None, new_len=None, new_row_len=0):
+        super().__init__(ctypes.sizeof(SplNgramIn), new_row_len, n_seqs, hist, lengths, new, new_len, cap, 0)
+
+
+class SplNgramOpts(ctypes.Structure):
+    """spl_ngram_opts (include/splintr_hip.h): flags, the n-gram lengths, the draft's shape, the pad id and the slices (0: the library chooses)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("min_n", ctypes.c_uint32), ("max_n", ctypes.c_uint32),
+                ("depth", ctypes.c_uint32), ("branches", ctypes.c_uint32), ("pad_id", ctypes.c_uint32), ("slices", ctypes.c_uint32)]
+
+    def __init__(self, flags=0, min_n=0, max_n=0, depth=0, branches=0, pad_id=0, slices=0):
+        super().__init__(ctypes.sizeof(SplNgramOpts), flags, min_n, max_n, depth, branches, pad_id, slices)
+
+
+class SplNgramOut(ctypes.Structure):
+    """spl_ngram_out: where the draft and the new lengths go, device addresses (None: not wanted)."""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("d_ids", ctypes.c_void_p), ("d_count", ctypes.c_void_p),
+                ("d_match", ctypes.c_void_p), ("d_from", ctypes.c_void_p), ("d_parent", ctypes.c_void_p), ("d_len", ctypes.c_void_p), ("d_full", ctypes.c_void_p)]
+
+    def __init__(self, ids=None, count=None, match=None, from_=None, parent=None, lengths=None, full=None):
+        super().__init__(ctypes.sizeof(SplNgramOut), 0, ids, count, match, from_, parent, lengths, full)
+
+
 _lib = None
 
 
@@ -466,6 +496,8 @@ def lib() -> ctypes.CDLL:
     L.spl_nest_step_device.argtypes = [vp, ctypes.POINTER(SplNestIn), ctypes.POINTER(SplNestOpts), ctypes.POINTER(SplNestOut), vp]
     L.spl_dfa_draft_device.argtypes = [vp, ctypes.POINTER(SplDfaIn), ctypes.POINTER(SplDfaOpts), ctypes.POINTER(SplDraftOut), vp]
     L.spl_nest_draft_device.argtypes = [vp, ctypes.POINTER(SplNestIn), ctypes.POINTER(SplNestOpts), ctypes.POINTER(SplDraftOut), vp]
+    L.spl_ngram_reserve_device.argtypes = [vp, ctypes.c_uint64]
+    L.spl_ngram_draft_device.argtypes = [vp, ctypes.POINTER(SplNgramIn), ctypes.POINTER(SplNgramOpts), ctypes.POINTER(SplNgramOut), vp]
     _lib = L
     return L
 

@@ -2616,6 +2616,175 @@ def _guide_accept_node(guide, draft: DraftResult, node) -> torch.Tensor:
     return guide.mask
 
 
+# ---------------------------------------------------------------------------------------------- n-gram drafting: prompt-lookup drafts from id histories
+class NgramDraft:
+    """What ngram_draft_device wrote: ids [B, branches * depth] (branch j in columns j * depth .., pad_id where a node is missing), count,
+    match and from_ int32 [B, branches] (the ids of a branch, the length of the n-gram it follows and the position it was copied from:
+    0, 0 and -1 where there is no branch), parent int32 [B, branches * depth] (None for one branch: a chain) -- -1 for a branch's first
+    node, the index in front for the others, -2 for a missing node.  guide.draft(d.ids, d.lengths) takes a chain, guide.draft(d.ids,
+    None, d.parent) a tree.  A depth of 0 leaves all of them None."""
+
+    def __init__(self, ids, count, match, from_, parent):
+        self.ids, self.count, self.match, self.from_, self.parent = ids, count, match, from_, parent
+
+    @property
+    def lengths(self):
+        """int32 [B]: the ids of the first branch -- the chain's length"""
+        return None if self.count is None else self.count[:, 0]
+
+    def __repr__(self) -> str:
+        return f"NgramDraft(ids={None if self.ids is None else tuple(self.ids.shape)}, tree={self.parent is not None})"
+
+
+def _ngram_int(name, v, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise ValueError(f"{name} must be an integer in {lo} .. {hi}, not {v!r}")
+    return int(v)
+
+
+def check_ngram_args(hist, lengths, new=None, new_len=None, *, min_n, max_n, depth, branches=1, pick="latest", slices=0, out=None, out_lengths=None,
+                     full=None) -> None:
+    """ValueError for a dtype, rank, shape, layout, option or device that ngram_draft_device would refuse -- before anything goes to the
+    device."""
+    if not isinstance(hist, torch.Tensor) or hist.dtype not in (torch.int32, torch.int64) or hist.dim() != 2 or not hist.is_contiguous():
+        raise ValueError("hist must be a contiguous int32 or int64 tensor of shape [batch, capacity]")
+    B, cap = int(hist.shape[0]), int(hist.shape[1])
+    if B >= (1 << 31) or cap > _ffi.SPL_NGRAM_MAX_CAP:
+        raise ValueError(f"the sequences must be fewer than 2**31 and the capacity at most {_ffi.SPL_NGRAM_MAX_CAP}")
+    max_n = _ngram_int("max_n", max_n, 1, _ffi.SPL_NGRAM_MAX_N)
+    _ngram_int("min_n", min_n, 1, max_n)
+    depth = _ngram_int("depth", depth, 0, _ffi.SPL_NGRAM_MAX_DEPTH)
+    branches = _ngram_int("branches", branches, 1, _ffi.SPL_NGRAM_MAX_BRANCHES)
+    if branches * depth > _ffi.SPL_DRAFT_MAX_NODES:
+        raise ValueError(f"branches * depth is {branches * depth}: a draft has at most {_ffi.SPL_DRAFT_MAX_NODES} nodes")
+    _ngram_int("slices", slices, 0, _ffi.SPL_NGRAM_MAX_SLICES)
+    if pick not in ("latest", "earliest"):
+        raise ValueError(f"pick must be 'latest' or 'earliest', not {pick!r}")
+    per = [_vec("lengths", lengths, B, (torch.int32,), "int32")]
+    if new is not None:
+        if not isinstance(new, torch.Tensor) or new.dtype != hist.dtype or new.dim() != 2 or new.shape[0] != B or not new.is_contiguous() or new.shape[1] >= (1 << 32):
+            raise ValueError("new must be a contiguous tensor of the history's dtype and of shape [batch, new ids]")
+        per += [("new", new)] + ([] if new_len is None else [_vec("new_len", new_len, B, (torch.int32,), "int32")])
+    elif new_len is not None:
+        raise ValueError("new_len goes with new")
+    if out_lengths is not None:
+        per.append(_vec("out_lengths", out_lengths, B, (torch.int32,), "int32"))
+    if full is not None:
+        per.append(_vec("full", full, B, (torch.uint8,), "uint8"))
+    if out is not None:
+        if not isinstance(out, NgramDraft):
+            raise ValueError("out must be an NgramDraft")
+        want = [("out.ids", out.ids, hist.dtype, branches * depth), ("out.count", out.count, torch.int32, branches), ("out.match", out.match, torch.int32, branches),
+                ("out.from_", out.from_, torch.int32, branches)] + ([("out.parent", out.parent, torch.int32, branches * depth)] if branches > 1 or out.parent is not None else [])
+        for name, t, dt, w in want if depth else []:
+            if not isinstance(t, torch.Tensor) or t.dtype != dt or tuple(t.shape) != (B, w) or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {dt} tensor of shape [{B}, {w}]")
+            per.append((name, t))
+    for name, t in per:
+        if t.device != hist.device:
+            raise ValueError(f"{name} must be on the device of hist")
+
+
+def ngram_reserve(tok: Tokenizer, max_seqs: int) -> None:
+    """spl_ngram_reserve_device: the scratch of the sliced form for up to max_seqs sequences; calls within it neither allocate nor
+    synchronise."""
+    rc = _ffi.lib().spl_ngram_reserve_device(tok.handle, int(max_seqs))
+    if rc != 0:
+        _raise_rc(rc, "spl_ngram_reserve_device")
+
+
+def ngram_draft_device(tok: Tokenizer, hist: torch.Tensor, lengths: torch.Tensor, *, new: Optional[torch.Tensor] = None, new_len: Optional[torch.Tensor] = None,
+                       min_n: int, max_n: int, depth: int, branches: int = 1, pick: str = "latest", pad_id: int = 0, slices: int = 0,
+                       out: Optional[NgramDraft] = None, out_lengths: Optional[torch.Tensor] = None, full: Optional[torch.Tensor] = None) -> NgramDraft:
+    """N-gram drafting (spl_ngram_draft_device), on torch's current stream; nothing synchronises.  hist [B, capacity] int32 / int64 and
+    lengths int32 [B] are the id histories; new [B, R] with new_len int32 [B] (None: all R) are the ids the last step committed: they are
+    appended -- hist and lengths are UPDATED IN PLACE (out_lengths: the new lengths go there instead), full uint8 [B] is set where a
+    history ran out of capacity -- and the draft is searched in the history with them.  A draft branch is what followed the latest (pick
+    "earliest": the earliest) earlier occurrence of the longest n-gram, min_n <= n <= max_n, the history ends with: up to `depth` ids;
+    `branches` > 1 asks for that many continuations with different first ids, as a tree.  An id outside [0, 2**31) is a hole: it matches
+    nothing and ends a branch.  depth 0 appends only.  slices: 0 lets the library choose, else 1 .. 32 workgroups per sequence.  out: an
+    NgramDraft of tensors to write into (default: fresh ones)."""
+    check_ngram_args(hist, lengths, new, new_len, min_n=min_n, max_n=max_n, depth=depth, branches=branches, pick=pick, slices=slices, out=out,
+                     out_lengths=out_lengths, full=full)
+    B, cap, dev = int(hist.shape[0]), int(hist.shape[1]), hist.device
+    if isinstance(pad_id, bool) or not isinstance(pad_id, (int, np.integer)) or not 0 <= int(pad_id) < (1 << 32):
+        raise ValueError(f"pad_id must be an integer in 0 .. 2**32 - 1, not {pad_id!r}")
+    if new is not None and new_len is None:
+        new_len = torch.full((B,), int(new.shape[1]), dtype=torch.int32, device=dev)
+    if depth and out is None:
+        out = NgramDraft(torch.empty((B, branches * depth), dtype=hist.dtype, device=dev), torch.empty((B, branches), dtype=torch.int32, device=dev),
+                         torch.empty((B, branches), dtype=torch.int32, device=dev), torch.empty((B, branches), dtype=torch.int32, device=dev),
+                         torch.empty((B, branches * depth), dtype=torch.int32, device=dev) if branches > 1 else None)
+    elif not depth:
+        out = NgramDraft(None, None, None, None, None)
+    flags = (_ffi.SPL_NGRAM_I64 if hist.dtype == torch.int64 else 0) | (_ffi.SPL_NGRAM_EARLIEST if pick == "earliest" else 0)
+    # (null pointers are refused by the library: an empty batch or capacity passes an address of its own, which nothing dereferences)
+    spare = torch.empty(8, dtype=torch.int64, device=dev).data_ptr() if (B == 0 or cap == 0) else 0
+
+    def at(t, k):
+        return _ptr(t) or (spare + k if spare else None)
+
+    si = _ffi.SplNgramIn(B, cap, at(hist, 0), at(lengths, 8), _ptr(new), _ptr(new_len) if _ptr(new) else None, int(new.shape[1]) if _ptr(new) else 0)
+    o = _ffi.SplNgramOpts(flags, int(min_n), int(max_n), int(depth), int(branches), int(pad_id), int(slices))
+    so = _ffi.SplNgramOut(at(out.ids, 16), at(out.count, 24), at(out.match, 32), at(out.from_, 40), at(out.parent, 48) if branches > 1 else _ptr(out.parent),
+                          at(lengths if out_lengths is None else out_lengths, 8 if out_lengths is None else 56), _ptr(full))
+    rc = _ffi.lib().spl_ngram_draft_device(tok.handle, ctypes.byref(si), ctypes.byref(o), ctypes.byref(so), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        _raise_rc(rc, "spl_ngram_draft_device")
+    return out
+
+
+class NgramDrafter:
+    """`tokenizer.ngram_drafter(batch_size, capacity)`: prompt-lookup drafts for a batch whose id histories live on the GPU -- `hist`
+    [B, capacity] and `length` int32 [B].  begin(rows, lengths) fills the histories from the prompts, step(ids) appends what a step
+    committed and proposes the next draft in the same call; `full` (uint8 [B]) tells where a history ran out of capacity (what does not
+    fit is dropped).  Nothing here synchronises."""
+
+    def __init__(self, tok: Tokenizer, batch_size: int, capacity: int, *, min_n: int = 2, max_n: int = 4, depth: int = 8, branches: int = 1,
+                 pick: str = "latest", dtype=torch.int32, pad_id: int = 0):
+        B = _ngram_int("batch_size", batch_size, 0, (1 << 31) - 1)
+        cap = _ngram_int("capacity", capacity, 1, _ffi.SPL_NGRAM_MAX_CAP)
+        if dtype not in (torch.int32, torch.int64):
+            raise ValueError("dtype must be torch.int32 or torch.int64")
+        dev = torch.device("cuda", tok._device)
+        self._tok, self.batch_size, self.capacity = tok, B, cap
+        self.opts = dict(min_n=min_n, max_n=max_n, depth=depth, branches=branches, pick=pick, pad_id=pad_id)
+        self.hist = torch.zeros((B, cap), dtype=dtype, device=dev)
+        self.length = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.full = torch.zeros(B, dtype=torch.uint8, device=dev)
+        check_ngram_args(self.hist, self.length, min_n=min_n, max_n=max_n, depth=depth, branches=branches, pick=pick)
+        ngram_reserve(tok, B)
+
+    def _tail(self, ids, lengths):
+        if not isinstance(ids, torch.Tensor) or ids.dim() not in (1, 2) or ids.shape[0] != self.batch_size:
+            raise ValueError("the ids must have shape [batch] or [batch, ids]")
+        ids = ids.view(self.batch_size, -1).to(self.hist.dtype).contiguous()
+        return ids, None if lengths is None else lengths.to(torch.int32)
+
+    def begin(self, rows: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> None:
+        """The histories start over from the prompts: rows [B, R] as encode_batch_padded leaves them, lengths [B] (None: all R)."""
+        rows, lengths = self._tail(rows, lengths)
+        self.length.zero_()
+        ngram_draft_device(self._tok, self.hist, self.length, new=rows, new_len=lengths, **{**self.opts, "depth": 0}, full=self.full)
+
+    def step(self, ids: Optional[torch.Tensor] = None, lengths: Optional[torch.Tensor] = None) -> NgramDraft:
+        """The ids a step committed, [B] or [B, K] with lengths [B] (None: nothing new), are appended and the next draft is proposed ->
+        NgramDraft."""
+        if ids is not None:
+            ids, lengths = self._tail(ids, lengths)
+        return ngram_draft_device(self._tok, self.hist, self.length, new=ids, new_len=lengths if ids is not None else None, **self.opts, full=self.full)
+
+    def reset(self, rows=None) -> None:
+        """The named sequences (indices or a bool mask; None: all) start over with an empty history."""
+        if rows is None:
+            self.length.zero_()
+            self.full.zero_()
+        else:
+            idx = torch.as_tensor(rows, device=self.hist.device)
+            self.length[idx] = 0
+            self.full[idx] = 0
+
+
 def _guide_apply(guide, logits, mask, live_only):
     """logits [R, V] against the guide's own mask (R = batch) or against the rows of a draft's mask ([B, 1 + K, n_words] or [R, n_words])"""
     if mask is None:

@@ -635,6 +635,19 @@ class Tokenizer:
         from . import device as dv
         return dv.NestGuide(self, batch_size, table, end_ids=end_ids, max_depth=max_depth, n_words=n_words)
 
+    def ngram_drafter(self, batch_size: int, capacity: int, *, min_n: int = 2, max_n: int = 4, depth: int = 8, branches: int = 1, pick: str = "latest",
+                      dtype=None):
+        """Extension: n-gram drafting ("prompt lookup decoding") on the GPU (splintr_amd.device.NgramDrafter): the id history of every
+        sequence lives in HBM, up to `capacity` ids each.  begin(rows, lengths) fills it from the prompts as encode_batch_padded leaves
+        them; step(ids) appends what the last step committed and proposes, in the same call, what followed the latest (pick
+        "earliest": the earliest) earlier occurrence of the longest n-gram of min_n .. max_n ids the history ends with: up to `depth`
+        ids, or `branches` such continuations with different first ids as a tree.  The result goes into regex_guide(...).draft(d.ids,
+        d.lengths) -- a tree: draft(d.ids, None, d.parent) -- as it is."""
+        import torch
+        from . import device as dv
+        return dv.NgramDrafter(self, batch_size, capacity, min_n=min_n, max_n=max_n, depth=depth, branches=branches, pick=pick,
+                               dtype=torch.int32 if dtype is None else dtype)
+
     def json_guide(self, batch_size: int, *, end_ids, top: str = "object", ws: str = "json", max_depth: int = 32, n_words: Optional[int] = None):
         """Extension: JSON MODE on the GPU -- the answer of every sequence is SOME valid JSON document (response_format json_object,
         guided_json without a schema): nest_guide over splintr_amd.nest.json_table(top, ws).  top: "object" (the usual contract),
