@@ -58,6 +58,32 @@ extern "C" {
 /* spl_opts.flags */
 #define SPL_OPT_BYTE_LEVEL 1u /* Tokenizer::from_bytes_byte_level (src/core/tokenizer.rs:562-569): the
                                  vocabulary's keys are ByteLevel text (src/core/byte_level.rs:46-74) */
+/* SentencePiece mode (Tokenizer::from_bytes_sentencepiece, src/core/tokenizer.rs:737-795): vocabularies whose word-boundary marker is
+ * U+2581 (Mistral V1 / V2, Llama-2, Gemma).  The split is a closed form over `[^\s]+|\s+` and runs ON THE GPU as a rewrite of the corpus in
+ * front of the tile kernel (csrc/spl_k_sp.h): every 0x20 of a whitespace run that begins with ASCII whitespace becomes E2 96 81, every
+ * other byte of such a run is a chunk of its own, the converted spaces in front of a word are that word's prefix.  spl_create takes the
+ * flag with SPL_PATTERN_CUSTOM and exactly the pattern text `[^\s]+|\s+` (any other pattern: SPL_EINVAL naming the mode; custom split
+ * patterns with the mode are out of scope), not together with SPL_OPT_BYTE_LEVEL.  On such a handle:
+ *   spl_encode_batch_device / _packed   rewrite, then the path of spl_encode_chunks_device.  The buffer contract below holds unchanged.
+ *                         One call takes at most 64 MiB of text (SPL_EINVAL beyond; the rewritten text is up to three times as long and the
+ *                         chunks path takes 256 MB) and synchronises `hip_stream` ONCE, to read the rewritten length -- as handles with
+ *                         SPL_PATTERN_CUSTOM do.  "n_bytes ids always suffice" holds when the vocabulary has the key U+2581; without
+ *                         it every converted space is three byte tokens, the need can reach 3 * n_bytes, and the capacity rule (tokens
+ *                         beyond ids_capacity are dropped, d_out_off[n_docs] reports the need) covers it.  The workspace -- 3 bytes and
+ *                         a few bits per byte of text -- comes from spl_reserve; nothing is allocated in a call once reserved.
+ *   spl_encode_batch      pieces of whole documents of at most 64 MiB, one after the other on the first device of the handle, each
+ *                         through the device call above (no latency path, no overlap of copies and kernels; a single document beyond
+ *                         64 MiB: SPL_EINVAL).
+ *   decode                spl_decode_batch, spl_decode_batch_device, the streaming decode, spans and stop strings return the vocabulary's
+ *                         own bytes, U+2581 included: turning it into a space (tokenizer.rs:913-929) is left to the caller -- the Python
+ *                         class does it for decode / decode_lossy / decode_batch / decode_batch_lossy.  Host streaming decoders for the
+ *                         mode are out of scope.
+ * Text that is not well-formed UTF-8 is never whitespace. */
+#define SPL_OPT_SENTENCEPIECE 2u
+/* load_tiktoken_bpe_with_decoder (src/core/vocab.rs:101-139): a key listed more than once ENCODES to the first id listed, and EVERY
+ * listed id decodes (spl_decode_*, spl_token_bytes).  Without the flag a later duplicate replaces the earlier one and its id decodes to
+ * nothing (vocab.rs:57-89).  Tiktoken-text vocabularies only; not with SPL_OPT_BYTE_LEVEL. */
+#define SPL_OPT_KEEP_ALL_IDS 4u
 
 /* encode flags */
 #define SPL_WITH_SPECIAL 1u /* encode_with_special semantics (src/core/tokenizer.rs:842-874) */
@@ -1595,6 +1621,8 @@ int spl_ngram_draft_device(spl_tokenizer* t, const spl_ngram_in* in, const spl_n
 int spl_token_bytes(const spl_tokenizer* t, uint32_t id, const uint8_t** bytes, uint32_t* len);
 /* 1 if the vocabulary's keys are ByteLevel text (from_bytes_byte_level / the container's flag). */
 int spl_is_byte_level(const spl_tokenizer* t);
+/* 1 for a handle created with SPL_OPT_SENTENCEPIECE. */
+int spl_is_sentencepiece(const spl_tokenizer* t);
 
 /* Per-kernel timing (HIP events on the launch stream).  While enabled every encode call records
  * events around each kernel; spl_profile_read returns the accumulated milliseconds and launch

@@ -7,8 +7,8 @@ The module exports what `splintr/__init__.py` of the reference exports (python/s
 from .agent_tokens import *  # noqa: F401,F403
 from .agent_tokens import __all__ as _agent_all
 from .streaming import ByteLevelStreamingDecoder, StreamingDecoder
-from .tokenizer import CL100K_BASE_PATTERN, LLAMA3_PATTERN, MISTRAL_V3_PATTERN, O200K_BASE_PATTERN, Tokenizer
+from .tokenizer import CL100K_BASE_PATTERN, LLAMA3_PATTERN, MISTRAL_V3_PATTERN, O200K_BASE_PATTERN, SENTENCEPIECE_PATTERN, Tokenizer
 
 __all__ = ["Tokenizer", "StreamingDecoder", "ByteLevelStreamingDecoder", "CL100K_BASE_PATTERN", "O200K_BASE_PATTERN",
-           "LLAMA3_PATTERN", "MISTRAL_V3_PATTERN"] + list(_agent_all)
+           "LLAMA3_PATTERN", "MISTRAL_V3_PATTERN", "SENTENCEPIECE_PATTERN"] + list(_agent_all)
 __version__ = "0.2.0"

@@ -25,7 +25,7 @@ SYMBOLS = [
     "spl_profile_enable", "spl_profile_reset", "spl_profile_read", "spl_kernel_name", "spl_last_queue_counts",
     "spl_debug_phases", "spl_debug_blocks", "spl_debug_rebase_offsets", "spl_gatherv_pack", "spl_gatherv_unpack", "spl_gatherv_unpack_group", "spl_encode_batch_device_packed",
     "spl_set_devices", "spl_n_devices", "spl_set_option", "spl_host_alloc", "spl_host_free",
-    "spl_token_bytes", "spl_is_byte_level",
+    "spl_token_bytes", "spl_is_byte_level", "spl_is_sentencepiece",
     "spl_comm_unique_id", "spl_comm_create", "spl_comm_destroy", "spl_comm_rank", "spl_comm_world",
     "spl_allgather_slabs", "spl_allgather_slabs_p2p", "spl_gatherv_unpack_at", "spl_allgatherv_csr", "spl_split_host", "spl_encode_chunks_device",
     "spl_split_device", "spl_device_split_fallbacks", "spl_small_path_calls", "spl_pick_stream", "spl_memo_stats", "spl_memo_seed_stats", "spl_debug_memo_entry",
@@ -43,6 +43,7 @@ SYMBOLS = [
 ]
 SPL_PATTERN_CUSTOM = 3
 SPL_OPT_BYTE_LEVEL = 1
+SPL_OPT_SENTENCEPIECE, SPL_OPT_KEEP_ALL_IDS = 2, 4
 SPL_COLLATE_I64, SPL_COLLATE_PAD_LEFT, SPL_COLLATE_KEEP_TAIL, SPL_COLLATE_BOS, SPL_COLLATE_EOS = 1, 2, 4, 8, 16
 SPL_PAIR_MAX_FIXED, SPL_PAIR_KEEP_TAIL_A, SPL_PAIR_KEEP_TAIL_B = 32, 32, 64
 SPL_PAIR_LONGEST_FIRST, SPL_PAIR_ONLY_FIRST, SPL_PAIR_ONLY_SECOND = 0, 1, 2
@@ -395,6 +396,7 @@ def lib() -> ctypes.CDLL:
     L.spl_host_free.argtypes = [vp]
     L.spl_token_bytes.argtypes = [vp, ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_uint32)]
     L.spl_is_byte_level.argtypes = [vp]
+    L.spl_is_sentencepiece.argtypes = [vp]
     L.spl_encode_batch.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(vp)]
     L.spl_result_tokens.restype = u32p
     L.spl_result_tokens.argtypes = [vp]

@@ -1,7 +1,7 @@
 // spl_api.hip -- the C ABI (include/splintr_hip.h): the root of the library's one HIP translation unit.  It includes the kernels
 // (spl_kernels.hip) and the host side, one file per concern and each building on the ones before it -- spl_host_res.h (resource owners,
 // pinned pool), spl_ctx.h (per-GPU context, handle, uploads), spl_streams.h (stream probe), spl_launch.h (memo, launch order, device
-// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_pair_host.h, spl_chat_host.h, spl_seqpack_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h, spl_seqscan_host.h, spl_stream_host.h, spl_stop_host.h, spl_heal_host.h, spl_mask_host.h, spl_choice_host.h, spl_dfa_host.h, spl_dfa_jump_host.h, spl_nest_host.h, spl_draft_host.h, spl_ngram_host.h -- and holds the entry points.
+// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_pair_host.h, spl_chat_host.h, spl_seqpack_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h, spl_sp_host.h (SentencePiece mode), spl_seqscan_host.h, spl_stream_host.h, spl_stop_host.h, spl_heal_host.h, spl_mask_host.h, spl_choice_host.h, spl_dfa_host.h, spl_dfa_jump_host.h, spl_nest_host.h, spl_draft_host.h, spl_ngram_host.h -- and holds the entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,6 +36,7 @@ using namespace spl;
 #include "spl_streams.h"
 #include "spl_launch.h"
 #include "spl_host_split.h"
+#include "spl_sp_host.h"
 #include "spl_pipeline.h"
 #include "spl_decode_host.h"
 #include "spl_collective.h"
@@ -91,16 +92,27 @@ spl_tokenizer* spl_create(const void* vocab, size_t vocab_len, const void* uclas
         std::unique_ptr<spl_tokenizer> t(new spl_tokenizer());
         std::string err;
         const bool custom = opts->pattern == SPL_PATTERN_CUSTOM;
+        const bool sp = (opts->flags & SPL_OPT_SENTENCEPIECE) != 0, keep_all = (opts->flags & SPL_OPT_KEEP_ALL_IDS) != 0;
         if (custom && (have < sizeof(spl_opts) || !opts->pattern_text || !opts->pattern_len)) {
             fail(SPL_EINVAL, "spl_create: SPL_PATTERN_CUSTOM needs spl_opts.pattern_text / pattern_len");
             return nullptr;
         }
+        if (sp) {
+            // SentencePiece mode needs no regex: its split is the closed form of spl_k_sp.h over this one pattern
+            static const char sp_pattern[] = "[^\\s]+|\\s+";
+            if (!custom || opts->pattern_len != sizeof sp_pattern - 1 || memcmp(opts->pattern_text, sp_pattern, sizeof sp_pattern - 1) != 0) {
+                fail(SPL_EINVAL, "spl_create: SentencePiece mode (SPL_OPT_SENTENCEPIECE) takes SPL_PATTERN_CUSTOM with the pattern [^\\s]+|\\s+ and no other");
+                return nullptr;
+            }
+            if (opts->flags & SPL_OPT_BYTE_LEVEL) { fail(SPL_EINVAL, "spl_create: SentencePiece mode (SPL_OPT_SENTENCEPIECE) does not go with SPL_OPT_BYTE_LEVEL"); return nullptr; }
+        }
         if (build_tables((const uint8_t*)vocab, vocab_len, (const uint8_t*)uclass_tab, uclass_len, custom ? SPL_PATTERN_CL100K : opts->pattern,
-                         (opts->flags & SPL_OPT_BYTE_LEVEL) != 0, t->ht, err)) {
+                         (opts->flags & SPL_OPT_BYTE_LEVEL) != 0, t->ht, err, keep_all)) {
             fail(SPL_EINVAL, "spl_create: " + err);
             return nullptr;
         }
-        if (custom) {
+        t->sp = sp;
+        if (custom && !sp) {
             // Tokenizer::new compiles the pattern (tokenizer.rs:426); a pattern this matcher cannot express is refused here
             t->regex = regex_compile(std::string(opts->pattern_text, (size_t)opts->pattern_len), t->ht, err);
             if (!t->regex) { fail(SPL_EINVAL, "spl_create: Regex error: " + err); return nullptr; }
@@ -248,6 +260,10 @@ void spl_destroy(spl_tokenizer* t) { delete t; }
 
 static int spl_reserve_impl(spl_tokenizer* t, uint64_t max_bytes, uint64_t max_docs) {
     if (!t) return fail(SPL_EINVAL, "spl_reserve: null handle");
+    if (t->sp) {
+        HIP_TRY(hipSetDevice(t->ctx[0]->device));
+        return sp_reserve(t, t->ctx[0].get(), std::min<uint64_t>(max_bytes, SP_MAX_BYTES), max_docs);
+    }
     return reserve(t->ctx[0].get(), max_bytes, max_docs);
 }
 
@@ -257,6 +273,7 @@ static int spl_encode_batch_device_impl(spl_tokenizer* t, const uint8_t* d_utf8,
     if (!t || !d_doc_off || !d_out_off || (n_bytes && (!d_utf8 || !d_ids)))
         return fail(SPL_EINVAL, "spl_encode_batch_device: null argument");
     HIP_TRY(hipSetDevice(t->ctx[0]->device));
+    if (t->sp) return encode_device_sp(t, t->ctx[0].get(), d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_capacity, d_out_off, (hipStream_t)hip_stream, nullptr);
     if (t->regex) return encode_device_custom(t, t->ctx[0].get(), d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_capacity, d_out_off, (hipStream_t)hip_stream, nullptr);
     return launch_all(t, t->ctx[0].get(), {.text = d_utf8, .n_bytes = n_bytes, .doc_off = d_doc_off, .n_docs = n_docs, .flags = flags,
                                            .ids = d_ids, .ids_cap = ids_capacity, .out_off = d_out_off, .stream = (hipStream_t)hip_stream});
@@ -273,6 +290,7 @@ static int spl_encode_batch_device_packed_impl(spl_tokenizer* t, const uint8_t* 
     HIP_TRY(hipSetDevice(t->ctx[0]->device));
     SlabOut so;
     so.d_slab = d_slab; so.cap_words = cap_words; so.max_docs = max_docs;
+    if (t->sp) return encode_device_sp(t, t->ctx[0].get(), d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_capacity, d_out_off, (hipStream_t)hip_stream, &so);
     if (t->regex) return encode_device_custom(t, t->ctx[0].get(), d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_capacity, d_out_off, (hipStream_t)hip_stream, &so);
     return launch_all(t, t->ctx[0].get(), {.text = d_utf8, .n_bytes = n_bytes, .doc_off = d_doc_off, .n_docs = n_docs, .flags = flags,
                                            .ids = d_ids, .ids_cap = ids_capacity, .out_off = d_out_off, .stream = (hipStream_t)hip_stream, .slab = &so});
@@ -288,6 +306,12 @@ int spl_encode_batch(spl_tokenizer* t, const uint8_t* utf8, const uint64_t* doc_
     if (doc_off[n_docs] && !utf8) return fail(SPL_EINVAL, "spl_encode_batch: null text");
     try {
         std::unique_ptr<spl_result> r(new spl_result());
+        if (t->sp) {                                        // (no latency path, no pipeline: the rewrite, piece by piece)
+            int rcp = encode_host_sp(t, utf8, doc_off, n_docs, flags, r.get());
+            if (rcp) return rcp;
+            *out = r.release();
+            return SPL_OK;
+        }
         if (t->small_path && !t->regex && doc_off[n_docs] > 0 && doc_off[n_docs] <= SMALL_MAX_BYTES && n_docs <= SMALL_MAX_DOCS) {
             int rcs = encode_small(t, utf8, doc_off, n_docs, flags, r.get());
             if (rcs) return rcs;
@@ -365,6 +389,7 @@ int spl_token_bytes(const spl_tokenizer* t, uint32_t id, const uint8_t** bytes, 
     return 0;
 }
 int spl_is_byte_level(const spl_tokenizer* t) { return t && t->ht.byte_level ? 1 : 0; }
+int spl_is_sentencepiece(const spl_tokenizer* t) { return t && t->sp ? 1 : 0; }
 
 int spl_profile_enable(spl_tokenizer* t, int on) {
     if (!t) return fail(SPL_EINVAL, "null handle");
@@ -383,7 +408,10 @@ int spl_profile_read(spl_tokenizer* t, double ms_out[SPL_MAX_KERNELS], uint64_t 
     memcpy(launches_out, t->ctx[0]->prof_n, sizeof t->ctx[0]->prof_n);
     return SPL_OK;
 }
-const char* spl_kernel_name(int index) { return (index >= 0 && index < KI_N) ? k_names[index] : nullptr; }
+const char* spl_kernel_name(int index) {
+    if (index >= KI_SP_COUNT && index <= KI_SP_WRITE) return k_sp_names[index - KI_SP_COUNT];
+    return (index >= 0 && index < KI_N) ? k_names[index] : nullptr;
+}
 
 int spl_gatherv_pack(spl_tokenizer* t, const uint32_t* d_ids, const uint64_t* d_out_off, uint64_t n_docs, uint32_t* d_slab,
                      uint64_t cap_words, uint64_t max_docs, void* hip_stream) {

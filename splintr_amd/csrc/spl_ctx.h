@@ -139,6 +139,12 @@ struct Ctx {
     DevBuf<uint32_t> d_rx_patch; uint64_t rx_patch_cap = 0;        // per-document fallback: the patch of one split (grow-only)
     DevBuf<uint32_t> d_rx_bad;                                      // [0] count, [1 .. RX_BAD_CAP] blocks the matcher gave up on (device list of one split)
     HostMapped<uint32_t> h_rx_bad;                                  // ... where k_rx_mark leaves it for the host (pinned)
+    // SentencePiece mode (spl_sp_host.h): the rewritten text, the tiles' counts, the rewritten document offsets, starts | gaps over the
+    // rewritten text; with SPL_WITH_SPECIAL the literal scan's four bitmaps and ids over the CALLER's text; spl_encode_batch's staging
+    DevBuf<uint8_t> d_sp_text; DevBuf<uint64_t> d_sp_cnt, d_sp_off; DevBuf<uint32_t> d_sp_bits, d_sp_scan;
+    uint64_t sp_cap_bytes = 0, sp_cap_docs = 0, sp_scan_cap = 0;
+    DevBuf<uint8_t> d_sph_text; DevBuf<uint64_t> d_sph_off, d_sph_oo; DevBuf<uint32_t> d_sph_ids;
+    uint64_t sph_text_cap = 0, sph_off_cap = 0, sph_oo_cap = 0, sph_ids_cap = 0;
     Event ev_split;                                                 // host pipeline: a chunk's split is through (the producer waits for it: per-document fallback)
     Event ev_h2d[NSLOT], ev_cmp[NSLOT];
     std::vector<Event> ev_chunk;
@@ -205,6 +211,7 @@ struct spl_tokenizer {
     mutable uint32_t max_tok_bytes = 0;       // spl_max_token_bytes, computed at its first call (0: not yet; spl_add_special resets it)
     bool special_newline = false;             // a literal contains '\n': no sub-document cuts with SPL_WITH_SPECIAL
     bool special_general = false;             // occurrences can overlap, or a literal exceeds SP_MAXLEN: the two-launch general matcher
+    bool sp = false;                          // SPL_OPT_SENTENCEPIECE: the split is the rewrite of spl_k_sp.h (no regex)
     RegexPtr regex;                           // SPL_PATTERN_CUSTOM: the host splitter's program (null: one of the GPU scanner's patterns)
     std::vector<uint32_t> rx_image;           // ... and its image for the device splitter (empty: the program does not fit, the split stays on the host)
     int rx_device = 1;                        // spl_set_option("device_split"): 0 keeps a custom pattern's split on the host cores

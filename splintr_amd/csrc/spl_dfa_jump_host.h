@@ -62,7 +62,8 @@ int dfa_jump_index_device(spl_tokenizer* t, const uint8_t* d_table, uint32_t n_s
     if (total > scr.text_cap()) return fail(SPL_EDEVICE, who + ": the runs hold more bytes than 64 a state");
     if (t->jump_phase == 2) return SPL_OK;
     if (total) {
-        if (t->regex) SPL_TRY(encode_device_custom(t, c, scr.text(), total, scr.doc_off(), S, 0u, scr.ids(), scr.text_cap(), scr.out_off(), st, nullptr));
+        if (t->sp) SPL_TRY(encode_device_sp(t, c, scr.text(), total, scr.doc_off(), S, 0u, scr.ids(), scr.text_cap(), scr.out_off(), st, nullptr));
+        else if (t->regex) SPL_TRY(encode_device_custom(t, c, scr.text(), total, scr.doc_off(), S, 0u, scr.ids(), scr.text_cap(), scr.out_off(), st, nullptr));
         else SPL_TRY(launch_all(t, c, {.text = scr.text(), .n_bytes = total, .doc_off = scr.doc_off(), .n_docs = S, .flags = 0u,
                                        .ids = scr.ids(), .ids_cap = scr.text_cap(), .out_off = scr.out_off(), .stream = st}));
     } else HIP_TRY(hipMemsetAsync(scr.out_off(), 0, (S + 1) * 8, st));           // (no run at all: S empty rows)

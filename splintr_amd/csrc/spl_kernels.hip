@@ -39,6 +39,7 @@
 //   spl_k_nest.h       k_nest_index / k_nest_count / k_nest_scan / k_nest_write / k_nest_step: nested languages (JSON mode) -- a byte automaton with push and pop ops and a 64-level stack per sequence; the stack-free part of a mask row is a row copy, the few ids that touch the stack are walked against it and merged in LDS before the copy (and their host-testable first half)
 //   spl_k_draft.h      k_dfa_draft / k_nest_draft: draft verification for the regex and nest guides -- from one state row per sequence and a draft chain or tree of up to 64 ids, the mask in front of the draft and behind every draft id, and whether each id is acceptable; a wavefront per (sequence, row) walks the node's path and takes the step's settle and row write (and their host-testable first half)
 //   spl_k_ngram.h      k_ngram / k_ngram_emit: n-gram drafting (prompt lookup) -- per-sequence id histories in HBM to draft chains or trees of up to 64 ids: a workgroup per (sequence, slice) streams the history through LDS, every end compared with the last suffix id in registers, the survivors' runs counted backwards, a top-W distinct list per lane, max-reduced over the workgroup; the ids a step committed appended on the way
+//   spl_k_sp.h         k_sp_rewrite<count> / <write>: SentencePiece mode -- the corpus rewritten (spaces of ASCII-led whitespace runs to U+2581) and its chunk starts, bit vectors of 4 096 bytes a workgroup, the run flags by an add-carry and one wavefront scan (and its host-testable per-word logic)
 //   (spl_rx_split.h, included by spl_api.hip: the device splitter for custom split patterns; its host half is in spl_launch.h)
 // (The multi-pass pipeline of rounds 1-3 -- k_bpe_lanes64, k_count, k_scan, k_compact_docs and the k_pretok
 //  instantiations without tile records -- was removed in round 4: no BASELINE configuration reached it.)
@@ -217,3 +218,4 @@ __device__ __forceinline__ uint32_t tidx() {
 #include "spl_k_nest.h"
 #include "spl_k_draft.h"
 #include "spl_k_ngram.h"
+#include "spl_k_sp.h"

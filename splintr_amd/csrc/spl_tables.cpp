@@ -117,7 +117,7 @@ uint32_t host_cp_category(const HostTables& t, uint32_t cp) {
 }
 
 int build_tables(const uint8_t* splv, size_t splv_len, const uint8_t* ucls, size_t ucls_len, int pattern,
-                 bool force_byte_level, HostTables& out, std::string& err) {
+                 bool force_byte_level, HostTables& out, std::string& err, bool keep_all_ids) {
     // ---- class table -------------------------------------------------------------------
     if (ucls_len < 32 || memcmp(ucls, "SPLU", 4) != 0 || rd32(ucls + 4) < 1 || rd32(ucls + 4) > 3) { err = "bad unicode class table"; return 1; }
     const uint32_t ucls_version = rd32(ucls + 4);
@@ -176,7 +176,13 @@ int build_tables(const uint8_t* splv, size_t splv_len, const uint8_t* ucls, size
 
     // ---- vocabulary (reference src/core/vocab.rs:57-89: later duplicate wins) ---------------
     std::unordered_map<std::string, uint32_t> enc;
+    // keep_all_ids (load_tiktoken_bpe_with_decoder, vocab.rs:101-139): the encoder keeps the FIRST id of a key, the decoder every id listed
+    std::vector<std::pair<uint32_t, std::string>> listed;
     uint32_t max_rank_seen = 0;
+    if (keep_all_ids && (force_byte_level || (splv_len >= 4 && memcmp(splv, "SPLV", 4) == 0))) {
+        err = "keeping every id of a duplicated key (SPL_OPT_KEEP_ALL_IDS) takes a tiktoken-text vocabulary without ByteLevel keys";
+        return 1;
+    }
     if (splv_len >= 4 && memcmp(splv, "SPLV", 4) == 0) {
         // this repo's packed container (tools/pack_vocab.py); the ByteLevel flag travels inside
         if (splv_len < 20 || rd32(splv + 4) != 1) { err = "bad vocabulary container"; return 1; }
@@ -273,10 +279,12 @@ int build_tables(const uint8_t* splv, size_t splv_len, const uint8_t* ucls, size
                 if (rank > 0xFFFFFFFFull) ok = false;
             }
             if (!ok) { err = "Invalid line format: Invalid rank: " + std::string((const char*)line + sp, n - sp); return 1; }
-            enc[key] = (uint32_t)rank;
+            if (keep_all_ids) { listed.emplace_back((uint32_t)rank, key); enc.emplace(key, (uint32_t)rank); }
+            else enc[key] = (uint32_t)rank;
         }
     }
     for (const auto& kv : enc) max_rank_seen = std::max(max_rank_seen, kv.second);   // vocab_size: max id of the map as loaded
+    for (const auto& kv : listed) max_rank_seen = std::max(max_rank_seen, kv.first);
     if (max_rank_seen > SPL_ID_MASK) { err = "token id does not fit 21 bits"; return 1; }
     // The id 2^21 - 1 stays free: the pair (2^21 - 1, 2^21 - 1) has a 42-bit key of all ones, which is what an EMPTY pair slot holds
     // (SPL_PAIR_EMPTY) -- pair_rank would "find" it there and return the slot's upper 22 bits, 4194303, as the merged id.
@@ -289,6 +297,7 @@ int build_tables(const uint8_t* splv, size_t splv_len, const uint8_t* ucls, size
     std::vector<uint32_t> verbatim;               // ByteLevel: ids whose key is emitted as it is
     dec.reserve(enc.size() * 2);
     if (!out.byte_level) for (const auto& kv : enc) dec[kv.second] = kv.first;
+    for (const auto& kv : listed) if (!kv.second.empty()) dec[kv.first] = kv.second;      // (an id listed twice: the later line, as a map insert)
     if (out.byte_level) {
         // Re-key into raw-byte space.  The reference merges over the UTF-8 bytes of the ByteLevel
         // text, where a byte whose alphabet char is U+0080 or above starts out as TWO nodes that only

@@ -35,6 +35,8 @@ MISTRAL_V3_PATTERN = (
     r"|[^\r\n\p{L}\p{N}]?[\p{Lu}\p{Lt}\p{Lm}\p{Lo}\p{M}]+[\p{Ll}\p{Lm}\p{Lo}\p{M}]*"
     r"|\p{N}| ?[^\s\p{L}\p{N}]+[\r\n/]*|\s*[\r\n]+|\s+(?!\S)|\s+"
 )
+# SentencePiece mode (src/core/tokenizer.rs:56): the one pattern the mode takes; its split is a closed form on the GPU (csrc/spl_k_sp.h).
+SENTENCEPIECE_PATTERN = r"[^\s]+|\s+"
 # The GPU scanner implements exactly these patterns; any other pattern is SPL_PATTERN_CUSTOM: its split runs on the
 # host cores (csrc/spl_regex.cpp) and feeds the same probe / merge kernels.
 _PATTERN_ID = {CL100K_BASE_PATTERN: 0, O200K_BASE_PATTERN: 1, MISTRAL_V3_PATTERN: 2}
@@ -51,6 +53,16 @@ _PRETRAINED = {
     "deepseek-v3": ("deepseek_v3.splv", LLAMA3_PATTERN, "deepseek_v3"),
     "mistral_v3": ("mistral_v3.splv", MISTRAL_V3_PATTERN, "mistral_v3"),
 }
+# SentencePiece vocabularies (src/core/pretrained.rs:143-151): name -> (the reference's vocabulary file, which the USER puts into
+# splintr_amd/data/ -- none is shipped --, every id decodes, native special tokens, first agent-token id)
+_V2_CONTROL = {"[INST]": 3, "[/INST]": 4, "[TOOL_CALLS]": 5, "[AVAILABLE_TOOLS]": 6, "[/AVAILABLE_TOOLS]": 7, "[TOOL_RESULTS]": 8,
+               "[/TOOL_RESULTS]": 9}
+_PRETRAINED_SP = {
+    "mistral": ("mistral.tiktoken", False, {"<unk>": 0, "<s>": 1, "</s>": 2}, 32000),
+    "mistral_v1": ("mistral.tiktoken", False, {"<unk>": 0, "<s>": 1, "</s>": 2}, 32000),
+    "mistral_v2": ("mistral_v2.tiktoken", True, _V2_CONTROL, 32768),
+}
+_AGENT_BASE_V3 = 131072                 # where special_tokens.json's mistral_v3 table has the 54 agent literals (pretrained.rs:391)
 
 
 def _byte_level_alphabet() -> List[str]:
@@ -132,23 +144,25 @@ class Tokenizer:
     """
 
     def __init__(self, vocab_path: str, pattern: str, special_tokens: Optional[Dict[str, int]] = None, *,
-                 device: int = 0, byte_level: bool = False, unicode_tables: str = "pcre2"):
+                 device: int = 0, byte_level: bool = False, unicode_tables: str = "pcre2", sentencepiece: bool = False):
         # src/python/bindings.rs:70-83: every failure of from_file surfaces as IOError
         try:
             blob = _read(vocab_path)
-            self._init_from_blob(blob, pattern, special_tokens or {}, device, byte_level, unicode_tables)
+            self._init_from_blob(blob, pattern, special_tokens or {}, device, byte_level, unicode_tables, sentencepiece)
         except (OSError, ValueError) as e:
             raise IOError(str(e)) from None
 
     # ------------------------------------------------------------------ construction
     def _init_from_blob(self, blob: bytes, pattern: str, special_tokens: Dict[str, int], device: int,
-                        byte_level: bool = False, unicode_tables: str = "pcre2"):
+                        byte_level: bool = False, unicode_tables: str = "pcre2", sentencepiece: bool = False, keep_all_ids: bool = False):
         if not isinstance(pattern, str):
             raise TypeError("argument 'pattern': object cannot be converted to 'PyString'")
         L = _ffi.lib()
         ucls = _read(_unicode_table_path(unicode_tables))
         flags = _ffi.SPL_OPT_BYTE_LEVEL if byte_level else 0
-        if pattern in _PATTERN_ID:
+        flags |= (_ffi.SPL_OPT_SENTENCEPIECE if sentencepiece else 0) | (_ffi.SPL_OPT_KEEP_ALL_IDS if keep_all_ids else 0)
+        self._sentencepiece = bool(sentencepiece)
+        if pattern in _PATTERN_ID and not sentencepiece:
             opts = _ffi.SplOpts(_PATTERN_ID[pattern], device, flags)
         else:                                   # src/core/tokenizer.rs:426: any pattern is compiled
             self._pattern_bytes = pattern.encode("utf-8")
@@ -166,9 +180,10 @@ class Tokenizer:
 
     @classmethod
     def _from_blob(cls, blob: bytes, pattern: str, special_tokens: Dict[str, int], device: int = 0,
-                   byte_level: bool = False, unicode_tables: str = "pcre2") -> "Tokenizer":
+                   byte_level: bool = False, unicode_tables: str = "pcre2", sentencepiece: bool = False,
+                   keep_all_ids: bool = False) -> "Tokenizer":
         self = cls.__new__(cls)
-        self._init_from_blob(blob, pattern, special_tokens, device, byte_level, unicode_tables)
+        self._init_from_blob(blob, pattern, special_tokens, device, byte_level, unicode_tables, sentencepiece, keep_all_ids)
         return self
 
     @staticmethod
@@ -177,6 +192,18 @@ class Tokenizer:
         deepseek_v3 / deepseek-v3)."""
         if not isinstance(name, str):
             raise TypeError("argument 'name': object cannot be converted to 'PyString'")
+        if name in _PRETRAINED_SP:
+            fn, keep_all, special, agent_base = _PRETRAINED_SP[name]
+            with open(os.path.join(_DATA, "special_tokens.json"), encoding="utf-8") as f:
+                v3 = json.load(f)["mistral_v3"]
+            special = dict(special)
+            special.update({lit: tid - _AGENT_BASE_V3 + agent_base for lit, tid in v3.items() if tid >= _AGENT_BASE_V3})
+            path = os.path.join(_DATA, fn)
+            if not os.path.exists(path):
+                raise FileNotFoundError(
+                    f"{name}: this package ships no SentencePiece vocabulary; put the reference's {fn} into {_DATA}, or load "
+                    "the vocabulary yourself with Tokenizer.from_bytes_sentencepiece(vocab_data, SENTENCEPIECE_PATTERN, special_tokens)")
+            return Tokenizer._from_blob(_read(path), SENTENCEPIECE_PATTERN, special, device, False, unicode_tables, True, keep_all)
         ent = _PRETRAINED.get(name)
         if ent is None:
             raise ValueError(
@@ -199,6 +226,23 @@ class Tokenizer:
         """src/core/tokenizer.rs:562-569 (not exposed by the reference's Python class; used by its
         from_pretrained for deepseek_v3 and mistral_v3)."""
         return Tokenizer._from_blob(bytes(vocab_data), pattern, special_tokens or {}, device, True, unicode_tables)
+
+    @staticmethod
+    def from_bytes_sentencepiece(vocab_data: bytes, pattern: str = SENTENCEPIECE_PATTERN, special_tokens: Optional[Dict[str, int]] = None,
+                                 device: int = 0, unicode_tables: str = "pcre2") -> "Tokenizer":
+        """src/core/tokenizer.rs:571-580: a vocabulary whose word-boundary marker is U+2581 (Mistral V1 / V2, Llama-2, Gemma).  Spaces
+        of whitespace runs that begin with ASCII whitespace are encoded as U+2581 and join the word behind them; decode turns U+2581
+        back into a space.  pattern must be SENTENCEPIECE_PATTERN (the split runs as a closed form on the GPU); a key listed twice
+        keeps its later id."""
+        return Tokenizer._from_blob(bytes(vocab_data), pattern, special_tokens or {}, device, False, unicode_tables, True)
+
+    @staticmethod
+    def from_bytes_sentencepiece_with_decoder(vocab_data: bytes, pattern: str = SENTENCEPIECE_PATTERN,
+                                              special_tokens: Optional[Dict[str, int]] = None, device: int = 0,
+                                              unicode_tables: str = "pcre2") -> "Tokenizer":
+        """src/core/tokenizer.rs:582-600 with load_tiktoken_bpe_with_decoder (vocab.rs:101-139): as from_bytes_sentencepiece, but a key
+        listed twice encodes to its FIRST id and every listed id decodes."""
+        return Tokenizer._from_blob(bytes(vocab_data), pattern, special_tokens or {}, device, False, unicode_tables, True, True)
 
     def set_devices(self, devices: Sequence[int]) -> "Tokenizer":
         """Extension: spread `encode_batch` over several GPUs from this one process
@@ -517,24 +561,28 @@ class Tokenizer:
             L.spl_free(oo)
         return [raw[o[i]:o[i + 1]] for i in range(len(token_lists))]
 
+    def _post(self, text: str) -> str:
+        """postprocess_decode (src/core/tokenizer.rs:913-929): SentencePiece mode turns every U+2581 into a space."""
+        return text.replace("\u2581", " ") if self._sentencepiece else text
+
     def decode(self, tokens: Sequence[int]) -> str:
         """src/python/bindings.rs:300-304 (ValueError on invalid UTF-8)."""
         try:
-            return self.decode_bytes(tokens).decode("utf-8")
+            return self._post(self.decode_bytes(tokens).decode("utf-8"))
         except UnicodeDecodeError:
             raise ValueError("Decoding error: invalid UTF-8") from None
 
     def decode_lossy(self, tokens: Sequence[int]) -> str:
-        return self.decode_bytes(tokens).decode("utf-8", "replace")
+        return self._post(self.decode_bytes(tokens).decode("utf-8", "replace"))
 
     def decode_batch(self, token_lists: Sequence[Sequence[int]]) -> List[str]:
         try:
-            return [b.decode("utf-8") for b in self._decode_batch_bytes(token_lists)]
+            return [self._post(b.decode("utf-8")) for b in self._decode_batch_bytes(token_lists)]
         except UnicodeDecodeError:
             raise ValueError("Decoding error: invalid UTF-8") from None
 
     def decode_batch_lossy(self, token_lists: Sequence[Sequence[int]]) -> List[str]:
-        return [b.decode("utf-8", "replace") for b in self._decode_batch_bytes(token_lists)]
+        return [self._post(b.decode("utf-8", "replace")) for b in self._decode_batch_bytes(token_lists)]
 
     def decode_tensor(self, input_ids, lengths=None, *, padding_side: str = "right", skip_special_tokens: bool = False,
                       errors: str = "strict") -> List[str]:
@@ -713,7 +761,12 @@ class Tokenizer:
         """Extension: True when the split pattern is not one of the three the GPU scanner implements (its split then
         runs as a matcher program -- on the GPU, or on the host cores for what the device matcher gives up on --, and no context-free cut position is
         known for it: splintr_amd.distributed keeps such a tokenizer's documents whole)."""
-        return self._pattern not in _PATTERN_ID
+        return self._pattern not in _PATTERN_ID and not self._sentencepiece
+
+    @property
+    def is_sentencepiece(self) -> bool:
+        """Extension: True for a SentencePiece handle (from_bytes_sentencepiece*, from_pretrained("mistral" / "mistral_v1" / "mistral_v2"))."""
+        return self._sentencepiece
 
     def pcre2(self, use_pcre2: bool = True) -> "Tokenizer":
         """Backend switches (src/python/bindings.rs:207-242) select between regex engines that
