@@ -84,6 +84,33 @@ extern "C" {
  * listed id decodes (spl_decode_*, spl_token_bytes).  Without the flag a later duplicate replaces the earlier one and its id decodes to
  * nothing (vocab.rs:57-89).  Tiktoken-text vocabularies only; not with SPL_OPT_BYTE_LEVEL. */
 #define SPL_OPT_KEEP_ALL_IDS 4u
+/* WordPiece mode (BERT, MiniLM, the bge-*-en and e5 embedders, the ms-marco cross-encoders): Hugging Face's BertNormalizer ->
+ * BertPreTokenizer -> WordPiece, restated per code point and run ON THE GPU by kernels of its own (csrc/spl_k_wp.h): a
+ * normaliser (two-stage table lookup per code point: clean-up, CJK isolation, NFD with accents stripped, lowercasing; text that is not
+ * well-formed UTF-8 is dropped) and a matcher (greedy longest match first over a trie of word-initial and continuation keys).  spl_create
+ * takes the flag with `vocab` = vocab.txt text -- one token per line, id = line number, a carriage return in front of the line feed is
+ * not part of the token -- and spl_opts.unk_id, max_word_chars (0: 100; at most 255), wp_prefix (NULL: "##") and norm_table (built by
+ * splintr_amd/wordpiece.py build_norm_table from Python's unicodedata; checked entry by entry).  SPL_EINVAL, naming the mode: a key listed
+ * twice, an empty line inside the file, a key of more than 255 bytes; the flag together with SPL_OPT_BYTE_LEVEL, SPL_OPT_SENTENCEPIECE,
+ * SPL_OPT_KEEP_ALL_IDS or SPL_PATTERN_CUSTOM (spl_opts.pattern is not read).  The id limit is unchanged.  On such a handle:
+ *   spl_encode_batch_device / _packed   the mode's four launches and two scans.  The buffer contract below holds unchanged, and n_bytes ids
+ *                         always suffice (no code point yields more words than it has bytes: the table check refuses one that does).
+ *                         One call takes at most 64 MiB of text (SPL_EINVAL beyond) and synchronises `hip_stream` ONCE, to read the
+ *                         normalised length.  The workspace -- 3 bytes and a few bits per byte of text -- comes from spl_reserve;
+ *                         nothing is allocated in a call once reserved.  SPL_WITH_SPECIAL on a handle that has special tokens:
+ *                         SPL_EINVAL (literals in the text are not looked for; [CLS] and [SEP] come from spl_pair_device / spl_chat_device).
+ *   spl_encode_batch      pieces of whole documents of at most 64 MiB, one after the other on the first device of the handle, each
+ *                         through the device call above, as in SentencePiece mode.
+ *   spl_token_bytes, spl_decode_batch   the vocabulary's own bytes, "##" included; joining pieces into text is left to the caller.
+ *   every call that only moves ids (pad, pack, pair, chat, seqpack, window, gatherv, ngram, mask apply) works unchanged.
+ *   REFUSED (SPL_EINVAL): spl_split_host, spl_split_device, spl_encode_chunks_device.  UNDEFINED (they run the byte-pair tables built from
+ *   the keys, or read ids as byte strings that concatenate to the text, which WordPiece ids do not): the chunk memo's statistics, the
+ *   byte-oriented guides (heal, choice, DFA, jump, nest, draft, UTF-8 masks) and the device decode family that turns ids into text
+ *   (spl_decode_batch_device, spans, the streaming decode, stop strings).
+ * Not pinned: code points whose category or decomposition differs between the Unicode version of the table's builder and the one inside
+ * Hugging Face's tokenizers; runs of two or more non-Mn combining marks of different combining classes (a whole-string NFD would reorder
+ * them); CJK compatibility ideographs, which stay themselves here. */
+#define SPL_OPT_WORDPIECE 8u
 
 /* encode flags */
 #define SPL_WITH_SPECIAL 1u /* encode_with_special semantics (src/core/tokenizer.rs:842-874) */
@@ -101,6 +128,13 @@ typedef struct spl_opts {
     uint32_t flags;       /* SPL_OPT_* */
     const char* pattern_text; /* SPL_PATTERN_CUSTOM: the split pattern, UTF-8, pattern_len bytes (no terminator needed) */
     uint64_t pattern_len;
+    /* SPL_OPT_WORDPIECE (fields behind struct_size of an older caller read as 0) */
+    uint32_t unk_id;          /* the id a word without a match becomes */
+    uint32_t max_word_chars;  /* words of more code points are unk_id (0: 100; at most 255) */
+    const char* wp_prefix;    /* the continuing-subword prefix, wp_prefix_len bytes (NULL: "##") */
+    uint64_t wp_prefix_len;
+    const void* norm_table;   /* the normalisation table, norm_table_len bytes; read during spl_create only */
+    uint64_t norm_table_len;
 } spl_opts;
 
 /* Thread-local text of the last failure in this thread. */
@@ -1623,6 +1657,8 @@ int spl_token_bytes(const spl_tokenizer* t, uint32_t id, const uint8_t** bytes, 
 int spl_is_byte_level(const spl_tokenizer* t);
 /* 1 for a handle created with SPL_OPT_SENTENCEPIECE. */
 int spl_is_sentencepiece(const spl_tokenizer* t);
+/* 1 for a handle created with SPL_OPT_WORDPIECE. */
+int spl_is_wordpiece(const spl_tokenizer* t);
 
 /* Per-kernel timing (HIP events on the launch stream).  While enabled every encode call records
  * events around each kernel; spl_profile_read returns the accumulated milliseconds and launch

@@ -70,9 +70,10 @@ void memo_seed_plan(const HostTables& t, uint32_t bits, uint32_t long_bits, Memo
 // Returns 0 on success; on failure fills err.
 // `vocab` is either this repo's SPLV container or the reference's tiktoken text (autodetected by the
 // magic); force_byte_level = the reference's from_bytes_byte_level (tokenizer.rs:562-569); keep_all_ids = load_tiktoken_bpe_with_decoder
-// (vocab.rs:101-139): a duplicated key encodes to its first id and every listed id decodes.
+// (vocab.rs:101-139): a duplicated key encodes to its first id and every listed id decodes; wordpiece = `vocab` is vocab.txt text, one key
+// per line, id = line number (WordPiece mode: the decoder side serves it, the encode tables are built but never probed).
 int build_tables(const uint8_t* vocab, size_t vocab_len, const uint8_t* ucls, size_t ucls_len, int pattern,
-                 bool force_byte_level, HostTables& out, std::string& err, bool keep_all_ids = false);
+                 bool force_byte_level, HostTables& out, std::string& err, bool keep_all_ids = false, bool wordpiece = false);
 
 // Host mirror of the device two-stage lookup (used by build checks and tests/hostsim).
 uint32_t host_cp_class(const HostTables& t, uint32_t cp);

@@ -162,6 +162,7 @@ class Tokenizer:
         flags = _ffi.SPL_OPT_BYTE_LEVEL if byte_level else 0
         flags |= (_ffi.SPL_OPT_SENTENCEPIECE if sentencepiece else 0) | (_ffi.SPL_OPT_KEEP_ALL_IDS if keep_all_ids else 0)
         self._sentencepiece = bool(sentencepiece)
+        self._wordpiece = False
         if pattern in _PATTERN_ID and not sentencepiece:
             opts = _ffi.SplOpts(_PATTERN_ID[pattern], device, flags)
         else:                                   # src/core/tokenizer.rs:426: any pattern is compiled
@@ -243,6 +244,56 @@ class Tokenizer:
         """src/core/tokenizer.rs:582-600 with load_tiktoken_bpe_with_decoder (vocab.rs:101-139): as from_bytes_sentencepiece, but a key
         listed twice encodes to its FIRST id and every listed id decodes."""
         return Tokenizer._from_blob(bytes(vocab_data), pattern, special_tokens or {}, device, False, unicode_tables, True, True)
+
+    @staticmethod
+    def from_bytes_wordpiece(vocab_data: bytes, *, lowercase: bool = True, strip_accents: Optional[bool] = None,
+                             handle_chinese_chars: bool = True, clean_text: bool = True, unk_token: str = "[UNK]",
+                             max_input_chars_per_word: int = 100, continuing_prefix: str = "##",
+                             special_tokens: Optional[Dict[str, int]] = None, device: int = 0) -> "Tokenizer":
+        """Extension: a WordPiece vocabulary (BERT, MiniLM, the bge-*-en and e5 embedders, the ms-marco cross-encoders) -- vocab.txt
+        text, one token per line, id = line number; the options are Hugging Face's BertNormalizer / WordPiece options and
+        strip_accents=None follows lowercase.  Normaliser and matcher run ON THE GPU (csrc/spl_k_wp.h); every encode_*
+        method works, [CLS] / [SEP] come from encode_batch_pairs' prefix / middle / suffix, and special-token literals in the text are
+        not looked for (the *_with_special methods refuse on a handle with special_tokens).  decode* raise: joining pieces is not
+        part of this mode yet; token_bytes / decode_bytes return the vocabulary's own bytes."""
+        from . import wordpiece
+        keys = wordpiece.parse_vocab_txt(vocab_data)
+        unk = unk_token.encode("utf-8")
+        if unk not in keys:
+            raise ValueError(f"WordPiece mode: unk_token {unk_token!r} is not in the vocabulary")
+        if not 1 <= int(max_input_chars_per_word) <= 255:
+            raise ValueError("WordPiece mode: max_input_chars_per_word must be in 1 .. 255")
+        table = wordpiece.build_norm_table(lowercase, strip_accents, handle_chinese_chars, clean_text)
+        self = Tokenizer.__new__(Tokenizer)
+        L = _ffi.lib()
+        blob = b"\n".join(keys) + b"\n"
+        ucls = _read(_unicode_table_path("pcre2"))
+        self._wp_prefix = continuing_prefix.encode("utf-8")
+        opts = _ffi.SplOpts(0, device, _ffi.SPL_OPT_WORDPIECE, None, keys.index(unk), int(max_input_chars_per_word), self._wp_prefix, table)
+        self._h = L.spl_create(blob, len(blob), ucls, len(ucls), ctypes.byref(opts))
+        if not self._h:
+            raise ValueError(_ffi.last_error())
+        self._device, self._pattern, self._sentencepiece, self._wordpiece = device, CL100K_BASE_PATTERN, False, True
+        self._special = dict(special_tokens or {})
+        for lit, tid in self._special.items():
+            b = lit.encode("utf-8")
+            if L.spl_add_special(self._h, b, len(b), int(tid)) != 0:
+                raise ValueError(_ffi.last_error())
+        return self
+
+    @staticmethod
+    def from_vocab_txt(path: str, **options) -> "Tokenizer":
+        """Extension: from_bytes_wordpiece on a vocab.txt file."""
+        return Tokenizer.from_bytes_wordpiece(_read(path), **options)
+
+    def is_wordpiece(self) -> bool:
+        """Extension: True for a WordPiece handle (from_bytes_wordpiece, from_vocab_txt)."""
+        return self._wordpiece
+
+    def _no_wordpiece_decode(self):
+        if self._wordpiece:
+            raise NotImplementedError("WordPiece mode: decoding ids to text (joining pieces, stripping the continuing prefix) is not "
+                                      "implemented; decode_bytes returns the vocabulary's own bytes")
 
     def set_devices(self, devices: Sequence[int]) -> "Tokenizer":
         """Extension: spread `encode_batch` over several GPUs from this one process
@@ -527,6 +578,7 @@ class Tokenizer:
         """tiktoken's decode_with_offsets: (text, the character index at which each token starts); a token that begins inside a
         character starts at that character.  Strict as decode (ValueError on invalid UTF-8); an id of neither map contributes nothing
         and starts where the next token does.  The starts come from the device (splintr_amd.device.spans_rows_device, one row)."""
+        self._no_wordpiece_decode()
         text = self.decode(tokens)
         if not len(tokens):
             return text, []
@@ -567,21 +619,25 @@ class Tokenizer:
 
     def decode(self, tokens: Sequence[int]) -> str:
         """src/python/bindings.rs:300-304 (ValueError on invalid UTF-8)."""
+        self._no_wordpiece_decode()
         try:
             return self._post(self.decode_bytes(tokens).decode("utf-8"))
         except UnicodeDecodeError:
             raise ValueError("Decoding error: invalid UTF-8") from None
 
     def decode_lossy(self, tokens: Sequence[int]) -> str:
+        self._no_wordpiece_decode()
         return self._post(self.decode_bytes(tokens).decode("utf-8", "replace"))
 
     def decode_batch(self, token_lists: Sequence[Sequence[int]]) -> List[str]:
+        self._no_wordpiece_decode()
         try:
             return [self._post(b.decode("utf-8")) for b in self._decode_batch_bytes(token_lists)]
         except UnicodeDecodeError:
             raise ValueError("Decoding error: invalid UTF-8") from None
 
     def decode_batch_lossy(self, token_lists: Sequence[Sequence[int]]) -> List[str]:
+        self._no_wordpiece_decode()
         return [self._post(b.decode("utf-8", "replace")) for b in self._decode_batch_bytes(token_lists)]
 
     def decode_tensor(self, input_ids, lengths=None, *, padding_side: str = "right", skip_special_tokens: bool = False,
@@ -625,6 +681,7 @@ class Tokenizer:
 
     def streaming_decoder(self):
         """src/python/bindings.rs:386-405."""
+        self._no_wordpiece_decode()
         from .streaming import StreamingDecoder
         return StreamingDecoder(lambda t: self._token_bytes(t, False))
 
