@@ -111,6 +111,35 @@ extern "C" {
  * Hugging Face's tokenizers; runs of two or more non-Mn combining marks of different combining classes (a whole-string NFD would reorder
  * them); CJK compatibility ideographs, which stay themselves here. */
 #define SPL_OPT_WORDPIECE 8u
+/* Unigram mode (XLM-RoBERTa and what is built on it -- bge-m3, multilingual-e5-*, the bge-reranker-v2-m3 cross-encoders --, T5, mT5, ALBERT):
+ * Hugging Face's pre_tokenizers.Metaspace -> models.Unigram.encode_optimized with byte_fallback off and fuse_unk on, restated in DESIGN.md
+ * 4.25 and run ON THE GPU by kernels of its own (csrc/spl_k_uni.h).  Every 0x20 stands for U+2581 and a U+2581 in the text counts the same;
+ * with uni_flags bit 0 (prepend "always") a non-empty document that begins with neither gets one U+2581 in front; a word starts at a
+ * document start and at every U+2581; tab, newline and every other character are word characters; a byte that is not part of a
+ * well-formed UTF-8 character is a character by itself without a key.  Per word the path of highest score wins: best[0] = 0.0, starts in
+ * ascending order, every key equal to word[s:e] proposes best[s] + score for e -- ONE IEEE-754 f64 add --, a character without a key of its
+ * own proposes unk_id at min_score - 10.0, a proposal replaces the incumbent only when STRICTLY greater, and a run of unk on the chosen
+ * path is one id.  A word of any length is exact.  spl_create takes the flag with `vocab` = one key per line, id = line number (as
+ * WordPiece mode parses it), spl_opts.scores / n_scores (one f64 per line; read during spl_create only), unk_id and uni_flags.
+ * SPL_EINVAL, naming the mode: n_scores that is not the number of lines, a key listed twice, an empty line, a key of more than 255 bytes or
+ * one that is not well-formed UTF-8, a score that is not finite, min_score - 10.0 >= 0, an unk_id beyond the lines; the flag together with
+ * SPL_OPT_BYTE_LEVEL, SPL_OPT_SENTENCEPIECE, SPL_OPT_KEEP_ALL_IDS, SPL_OPT_WORDPIECE or SPL_PATTERN_CUSTOM.  On such a handle:
+ *   spl_encode_batch_device / _packed   five launches on `hip_stream` and NO synchronisation: the kernels read the caller's text.  The
+ *                         buffer contract below holds; the need is at most n_bytes + n_docs ids (a prepended marker can be a token of
+ *                         its own).  One call takes at most 64 MiB of text (SPL_EINVAL beyond).  The workspace -- 16 bytes per byte of
+ *                         text for words longer than 128 bytes, a few bytes per 512-byte tile -- comes from spl_reserve; nothing is
+ *                         allocated in a call once reserved.  SPL_WITH_SPECIAL on a handle that has special tokens: SPL_EINVAL (literals in
+ *                         the text are not looked for; <s> and </s> come from spl_pair_device / spl_chat_device).
+ *   spl_encode_batch      pieces of whole documents of at most 64 MiB through the device call above, as in SentencePiece mode.
+ *   spl_token_bytes, spl_decode_batch   the vocabulary's own bytes, U+2581 included.
+ *   every call that only moves ids (pad, pack, pair, chat, seqpack, window, gatherv, ngram, mask apply) works unchanged.
+ *   spl_profile_read      a handle is of one mode: slots 11 .. 14 hold k_uni_match<count>, k_uni_long<count> + k_decode_scan,
+ *                         k_uni_match<write>, k_uni_long<write> (spl_kernel_name gives WordPiece mode's names for these slots).
+ *   REFUSED (SPL_EINVAL): spl_split_host, spl_split_device, spl_encode_chunks_device.  UNDEFINED, as in WordPiece mode: the chunk memo's
+ *   statistics, the byte-oriented guides and the device decode family that turns ids into text.
+ * Out of scope: byte_fallback; the normaliser (the Precompiled charsmap / NFKC and XLM-R's Replace(" {2,}", " ")) -- the text is taken as
+ * already normalised; prepend_scheme "first"; sampling and n-best. */
+#define SPL_OPT_UNIGRAM 16u
 
 /* encode flags */
 #define SPL_WITH_SPECIAL 1u /* encode_with_special semantics (src/core/tokenizer.rs:842-874) */
@@ -135,6 +164,10 @@ typedef struct spl_opts {
     uint64_t wp_prefix_len;
     const void* norm_table;   /* the normalisation table, norm_table_len bytes; read during spl_create only */
     uint64_t norm_table_len;
+    /* SPL_OPT_UNIGRAM (unk_id above is shared) */
+    const double* scores;     /* one score per line of `vocab`, n_scores of them; read during spl_create only */
+    uint64_t n_scores;
+    uint32_t uni_flags;       /* bit 0: prepend_scheme "always" (0: "never") */
 } spl_opts;
 
 /* Thread-local text of the last failure in this thread. */
@@ -1659,6 +1692,8 @@ int spl_is_byte_level(const spl_tokenizer* t);
 int spl_is_sentencepiece(const spl_tokenizer* t);
 /* 1 for a handle created with SPL_OPT_WORDPIECE. */
 int spl_is_wordpiece(const spl_tokenizer* t);
+/* 1 for a handle created with SPL_OPT_UNIGRAM. */
+int spl_is_unigram(const spl_tokenizer* t);
 
 /* Per-kernel timing (HIP events on the launch stream).  While enabled every encode call records
  * events around each kernel; spl_profile_read returns the accumulated milliseconds and launch

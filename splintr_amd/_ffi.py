@@ -25,7 +25,7 @@ SYMBOLS = [
     "spl_profile_enable", "spl_profile_reset", "spl_profile_read", "spl_kernel_name", "spl_last_queue_counts",
     "spl_debug_phases", "spl_debug_blocks", "spl_debug_rebase_offsets", "spl_gatherv_pack", "spl_gatherv_unpack", "spl_gatherv_unpack_group", "spl_encode_batch_device_packed",
     "spl_set_devices", "spl_n_devices", "spl_set_option", "spl_host_alloc", "spl_host_free",
-    "spl_token_bytes", "spl_is_byte_level", "spl_is_sentencepiece", "spl_is_wordpiece",
+    "spl_token_bytes", "spl_is_byte_level", "spl_is_sentencepiece", "spl_is_wordpiece", "spl_is_unigram",
     "spl_comm_unique_id", "spl_comm_create", "spl_comm_destroy", "spl_comm_rank", "spl_comm_world",
     "spl_allgather_slabs", "spl_allgather_slabs_p2p", "spl_gatherv_unpack_at", "spl_allgatherv_csr", "spl_split_host", "spl_encode_chunks_device",
     "spl_split_device", "spl_device_split_fallbacks", "spl_small_path_calls", "spl_pick_stream", "spl_memo_stats", "spl_memo_seed_stats", "spl_debug_memo_entry",
@@ -43,7 +43,7 @@ SYMBOLS = [
 ]
 SPL_PATTERN_CUSTOM = 3
 SPL_OPT_BYTE_LEVEL = 1
-SPL_OPT_SENTENCEPIECE, SPL_OPT_KEEP_ALL_IDS, SPL_OPT_WORDPIECE = 2, 4, 8
+SPL_OPT_SENTENCEPIECE, SPL_OPT_KEEP_ALL_IDS, SPL_OPT_WORDPIECE, SPL_OPT_UNIGRAM = 2, 4, 8, 16
 SPL_COLLATE_I64, SPL_COLLATE_PAD_LEFT, SPL_COLLATE_KEEP_TAIL, SPL_COLLATE_BOS, SPL_COLLATE_EOS = 1, 2, 4, 8, 16
 SPL_PAIR_MAX_FIXED, SPL_PAIR_KEEP_TAIL_A, SPL_PAIR_KEEP_TAIL_B = 32, 32, 64
 SPL_PAIR_LONGEST_FIRST, SPL_PAIR_ONLY_FIRST, SPL_PAIR_ONLY_SECOND = 0, 1, 2
@@ -96,12 +96,17 @@ class SplOpts(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("pattern", ctypes.c_int32), ("device", ctypes.c_int32),
                 ("flags", ctypes.c_uint32), ("pattern_text", ctypes.c_char_p), ("pattern_len", ctypes.c_uint64),
                 ("unk_id", ctypes.c_uint32), ("max_word_chars", ctypes.c_uint32), ("wp_prefix", ctypes.c_char_p),
-                ("wp_prefix_len", ctypes.c_uint64), ("norm_table", ctypes.c_char_p), ("norm_table_len", ctypes.c_uint64)]
+                ("wp_prefix_len", ctypes.c_uint64), ("norm_table", ctypes.c_char_p), ("norm_table_len", ctypes.c_uint64),
+                ("scores", ctypes.POINTER(ctypes.c_double)), ("n_scores", ctypes.c_uint64), ("uni_flags", ctypes.c_uint32)]
 
-    def __init__(self, pattern=0, device=0, flags=0, pattern_text=None, unk_id=0, max_word_chars=0, wp_prefix=None, norm_table=None):
+    def __init__(self, pattern=0, device=0, flags=0, pattern_text=None, unk_id=0, max_word_chars=0, wp_prefix=None, norm_table=None,
+                 scores=None, uni_flags=0):
+        """scores: a ctypes array of c_double (Unigram mode), kept alive by the caller through spl_create."""
         super().__init__(ctypes.sizeof(SplOpts), pattern, device, flags, pattern_text, len(pattern_text) if pattern_text else 0,
                          unk_id, max_word_chars, wp_prefix, len(wp_prefix) if wp_prefix else 0, norm_table,
-                         len(norm_table) if norm_table else 0)
+                         len(norm_table) if norm_table else 0,
+                         ctypes.cast(scores, ctypes.POINTER(ctypes.c_double)) if scores is not None else None,
+                         len(scores) if scores is not None else 0, uni_flags)
 
 
 class SplCollateOpts(ctypes.Structure):
@@ -402,6 +407,7 @@ def lib() -> ctypes.CDLL:
     L.spl_is_byte_level.argtypes = [vp]
     L.spl_is_sentencepiece.argtypes = [vp]
     L.spl_is_wordpiece.argtypes = [vp]
+    L.spl_is_unigram.argtypes = [vp]
     L.spl_encode_batch.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(vp)]
     L.spl_result_tokens.restype = u32p
     L.spl_result_tokens.argtypes = [vp]

@@ -1,7 +1,7 @@
 // spl_api.hip -- the C ABI (include/splintr_hip.h): the root of the library's one HIP translation unit.  It includes the kernels
 // (spl_kernels.hip) and the host side, one file per concern and each building on the ones before it -- spl_host_res.h (resource owners,
 // pinned pool), spl_ctx.h (per-GPU context, handle, uploads), spl_streams.h (stream probe), spl_launch.h (memo, launch order, device
-// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_pair_host.h, spl_chat_host.h, spl_seqpack_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h, spl_wp_host.h (WordPiece mode), spl_sp_host.h (SentencePiece mode), spl_seqscan_host.h, spl_stream_host.h, spl_stop_host.h, spl_heal_host.h, spl_mask_host.h, spl_choice_host.h, spl_dfa_host.h, spl_dfa_jump_host.h, spl_nest_host.h, spl_draft_host.h, spl_ngram_host.h -- and holds the entry points.
+// splitter), spl_host_split.h, spl_pipeline.h (spl_encode_batch), spl_decode_host.h, spl_collective.h, spl_collate_host.h, spl_pair_host.h, spl_chat_host.h, spl_seqpack_host.h, spl_window_host.h, spl_decode_dev_host.h, spl_spans_host.h, spl_wp_host.h (WordPiece mode), spl_uni_host.h (Unigram mode), spl_sp_host.h (SentencePiece mode), spl_seqscan_host.h, spl_stream_host.h, spl_stop_host.h, spl_heal_host.h, spl_mask_host.h, spl_choice_host.h, spl_dfa_host.h, spl_dfa_jump_host.h, spl_nest_host.h, spl_draft_host.h, spl_ngram_host.h -- and holds the entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -9,6 +9,8 @@
 #include <cstddef>
 #include <cstdio>
 #include <cstdlib>
+#include <cmath>
+#include <limits>
 #include <condition_variable>
 #include <cstring>
 #include <functional>
@@ -38,6 +40,7 @@ using namespace spl;
 #include "spl_launch.h"
 #include "spl_host_split.h"
 #include "spl_wp_host.h"
+#include "spl_uni_host.h"
 #include "spl_sp_host.h"
 #include "spl_pipeline.h"
 #include "spl_decode_host.h"
@@ -99,6 +102,14 @@ spl_tokenizer* spl_create(const void* vocab, size_t vocab_len, const void* uclas
             fail(SPL_EINVAL, "spl_create: SPL_PATTERN_CUSTOM needs spl_opts.pattern_text / pattern_len");
             return nullptr;
         }
+        const bool uni = (opts->flags & SPL_OPT_UNIGRAM) != 0;
+        if (uni) {
+            if ((opts->flags & (SPL_OPT_BYTE_LEVEL | SPL_OPT_SENTENCEPIECE | SPL_OPT_KEEP_ALL_IDS | SPL_OPT_WORDPIECE)) || custom) {
+                fail(SPL_EINVAL, "spl_create: Unigram mode (SPL_OPT_UNIGRAM) does not go with SPL_OPT_BYTE_LEVEL, SPL_OPT_SENTENCEPIECE, SPL_OPT_KEEP_ALL_IDS, SPL_OPT_WORDPIECE or a custom pattern");
+                return nullptr;
+            }
+            if (have < sizeof(spl_opts)) { fail(SPL_EINVAL, "spl_create: Unigram mode (SPL_OPT_UNIGRAM) needs spl_opts.scores / n_scores"); return nullptr; }
+        }
         if (sp) {
             // SentencePiece mode needs no regex: its split is the closed form of spl_k_sp.h over this one pattern
             static const char sp_pattern[] = "[^\\s]+|\\s+";
@@ -115,7 +126,7 @@ spl_tokenizer* spl_create(const void* vocab, size_t vocab_len, const void* uclas
                 fail(SPL_EINVAL, "spl_create: WordPiece mode (SPL_OPT_WORDPIECE) does not go with SPL_OPT_BYTE_LEVEL, SPL_OPT_SENTENCEPIECE, SPL_OPT_KEEP_ALL_IDS or a custom pattern");
                 return nullptr;
             }
-            if (have < sizeof(spl_opts) || !opts->norm_table) { fail(SPL_EINVAL, "spl_create: WordPiece mode (SPL_OPT_WORDPIECE) needs spl_opts.norm_table / norm_table_len"); return nullptr; }
+            if (have < offsetof(spl_opts, scores) || !opts->norm_table) { fail(SPL_EINVAL, "spl_create: WordPiece mode (SPL_OPT_WORDPIECE) needs spl_opts.norm_table / norm_table_len"); return nullptr; }
             if (opts->max_word_chars > (uint32_t)WP_MAX_WORD_CHARS) { fail(SPL_EINVAL, "spl_create: WordPiece mode: max_word_chars is at most 255"); return nullptr; }
             if (opts->wp_prefix) wp_prefix.assign(opts->wp_prefix, (size_t)opts->wp_prefix_len);
             t->wp = std::make_shared<WpHost>();
@@ -124,9 +135,13 @@ spl_tokenizer* spl_create(const void* vocab, size_t vocab_len, const void* uclas
             t->wp->max_chars = opts->max_word_chars ? opts->max_word_chars : 100u;
         }
         if (build_tables((const uint8_t*)vocab, vocab_len, (const uint8_t*)uclass_tab, uclass_len, custom ? SPL_PATTERN_CL100K : opts->pattern,
-                         (opts->flags & SPL_OPT_BYTE_LEVEL) != 0, t->ht, err, keep_all, wp)) {
+                         (opts->flags & SPL_OPT_BYTE_LEVEL) != 0, t->ht, err, keep_all, wp || uni, uni ? "Unigram" : "WordPiece")) {
             fail(SPL_EINVAL, "spl_create: " + err);
             return nullptr;
+        }
+        if (uni) {
+            t->uni = std::make_shared<UniHost>();
+            if (uni_build(t->ht, opts->scores, opts->n_scores, opts->unk_id, opts->uni_flags, *t->uni, err)) { fail(SPL_EINVAL, "spl_create: " + err); return nullptr; }
         }
         if (wp && wp_build_trie(t->ht, wp_prefix, *t->wp, err)) { fail(SPL_EINVAL, "spl_create: " + err); return nullptr; }
         t->sp = sp;
@@ -278,6 +293,10 @@ void spl_destroy(spl_tokenizer* t) { delete t; }
 
 static int spl_reserve_impl(spl_tokenizer* t, uint64_t max_bytes, uint64_t max_docs) {
     if (!t) return fail(SPL_EINVAL, "spl_reserve: null handle");
+    if (t->uni) {
+        HIP_TRY(hipSetDevice(t->ctx[0]->device));
+        return uni_reserve(t, t->ctx[0].get(), std::min<uint64_t>(max_bytes, UNI_MAX_BYTES), max_docs);
+    }
     if (t->wp) {
         HIP_TRY(hipSetDevice(t->ctx[0]->device));
         return wp_reserve(t, t->ctx[0].get(), std::min<uint64_t>(max_bytes, WP_MAX_BYTES), max_docs);
@@ -295,6 +314,7 @@ static int spl_encode_batch_device_impl(spl_tokenizer* t, const uint8_t* d_utf8,
     if (!t || !d_doc_off || !d_out_off || (n_bytes && (!d_utf8 || !d_ids)))
         return fail(SPL_EINVAL, "spl_encode_batch_device: null argument");
     HIP_TRY(hipSetDevice(t->ctx[0]->device));
+    if (t->uni) return encode_device_uni(t, t->ctx[0].get(), d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_capacity, d_out_off, (hipStream_t)hip_stream, nullptr);
     if (t->wp) return encode_device_wp(t, t->ctx[0].get(), d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_capacity, d_out_off, (hipStream_t)hip_stream, nullptr);
     if (t->sp) return encode_device_sp(t, t->ctx[0].get(), d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_capacity, d_out_off, (hipStream_t)hip_stream, nullptr);
     if (t->regex) return encode_device_custom(t, t->ctx[0].get(), d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_capacity, d_out_off, (hipStream_t)hip_stream, nullptr);
@@ -313,6 +333,7 @@ static int spl_encode_batch_device_packed_impl(spl_tokenizer* t, const uint8_t* 
     HIP_TRY(hipSetDevice(t->ctx[0]->device));
     SlabOut so;
     so.d_slab = d_slab; so.cap_words = cap_words; so.max_docs = max_docs;
+    if (t->uni) return encode_device_uni(t, t->ctx[0].get(), d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_capacity, d_out_off, (hipStream_t)hip_stream, &so);
     if (t->wp) return encode_device_wp(t, t->ctx[0].get(), d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_capacity, d_out_off, (hipStream_t)hip_stream, &so);
     if (t->sp) return encode_device_sp(t, t->ctx[0].get(), d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_capacity, d_out_off, (hipStream_t)hip_stream, &so);
     if (t->regex) return encode_device_custom(t, t->ctx[0].get(), d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_capacity, d_out_off, (hipStream_t)hip_stream, &so);
@@ -330,7 +351,7 @@ int spl_encode_batch(spl_tokenizer* t, const uint8_t* utf8, const uint64_t* doc_
     if (doc_off[n_docs] && !utf8) return fail(SPL_EINVAL, "spl_encode_batch: null text");
     try {
         std::unique_ptr<spl_result> r(new spl_result());
-        if (t->sp || t->wp) {                               // (no latency path, no pipeline: the mode's device call, piece by piece)
+        if (t->sp || t->wp || t->uni) {                               // (no latency path, no pipeline: the mode's device call, piece by piece)
             int rcp = encode_host_sp(t, utf8, doc_off, n_docs, flags, r.get());
             if (rcp) return rcp;
             *out = r.release();
@@ -415,6 +436,7 @@ int spl_token_bytes(const spl_tokenizer* t, uint32_t id, const uint8_t** bytes, 
 int spl_is_byte_level(const spl_tokenizer* t) { return t && t->ht.byte_level ? 1 : 0; }
 int spl_is_sentencepiece(const spl_tokenizer* t) { return t && t->sp ? 1 : 0; }
 int spl_is_wordpiece(const spl_tokenizer* t) { return t && t->wp ? 1 : 0; }
+int spl_is_unigram(const spl_tokenizer* t) { return t && t->uni ? 1 : 0; }
 
 int spl_profile_enable(spl_tokenizer* t, int on) {
     if (!t) return fail(SPL_EINVAL, "null handle");
@@ -915,6 +937,7 @@ int spl_encode_chunks_device(spl_tokenizer* t, const uint8_t* d_utf8, uint64_t n
     if (!t || !d_doc_off || !d_out_off || !d_start_bits || !d_gap_bits || (n_bytes && (!d_utf8 || !d_ids)))
         return fail(SPL_EINVAL, "spl_encode_chunks_device: null argument");
     if (t->wp) return fail(SPL_EINVAL, "spl_encode_chunks_device: WordPiece mode has no chunks path (its words come from the normaliser)");
+    if (t->uni) return fail(SPL_EINVAL, "spl_encode_chunks_device: Unigram mode has no chunks path (its words are cut at U+2581 by its own kernels)");
     return guarded("spl_encode_chunks_device", [&] {
         HIP_TRY(hipSetDevice(t->ctx[0]->device));
         ExtIn ext;

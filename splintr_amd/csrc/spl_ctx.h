@@ -55,6 +55,7 @@ struct Memo {
 // staging.  A handle has one context per device of spl_set_devices (one by default).  Every GPU resource is a member that
 // frees itself (spl_host_res.h); the destructor only makes sure the device is idle and the twin goes first.
 struct WpCtx; struct WpHost;                                  // WordPiece mode (spl_wp_host.h)
+struct UniCtx; struct UniHost;                                // Unigram mode (spl_uni_host.h)
 struct Ctx {
     int device = 0;
     std::shared_ptr<const TableSet> tables;
@@ -146,6 +147,7 @@ struct Ctx {
     uint64_t sp_cap_bytes = 0, sp_cap_docs = 0, sp_scan_cap = 0;
     DevBuf<uint8_t> d_sph_text; DevBuf<uint64_t> d_sph_off, d_sph_oo; DevBuf<uint32_t> d_sph_ids;
     uint64_t sph_text_cap = 0, sph_off_cap = 0, sph_oo_cap = 0, sph_ids_cap = 0;
+    std::shared_ptr<UniCtx> uni;                                    // Unigram mode: this GPU's tables and workspace (made at the first call)
     std::shared_ptr<WpCtx> wp;                                      // WordPiece mode: this GPU's tables and workspace (made at the first call)
     Event ev_split;                                                 // host pipeline: a chunk's split is through (the producer waits for it: per-document fallback)
     Event ev_h2d[NSLOT], ev_cmp[NSLOT];
@@ -214,6 +216,7 @@ struct spl_tokenizer {
     bool special_newline = false;             // a literal contains '\n': no sub-document cuts with SPL_WITH_SPECIAL
     bool special_general = false;             // occurrences can overlap, or a literal exceeds SP_MAXLEN: the two-launch general matcher
     bool sp = false;                          // SPL_OPT_SENTENCEPIECE: the split is the rewrite of spl_k_sp.h (no regex)
+    std::shared_ptr<UniHost> uni;             // SPL_OPT_UNIGRAM: the trie, the scores and the options (spl_uni_host.h); the encode path is that file's
     std::shared_ptr<WpHost> wp;               // SPL_OPT_WORDPIECE: the normalisation table, the trie and the options (spl_wp_host.h); the encode path is that file's
     RegexPtr regex;                           // SPL_PATTERN_CUSTOM: the host splitter's program (null: one of the GPU scanner's patterns)
     std::vector<uint32_t> rx_image;           // ... and its image for the device splitter (empty: the program does not fit, the split stays on the host)

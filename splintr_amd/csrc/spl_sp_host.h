@@ -119,7 +119,7 @@ int encode_device_sp(spl_tokenizer* tk, Ctx* c, const uint8_t* d_utf8, uint64_t 
     return SPL_OK;
 }
 
-// spl_encode_batch on a SentencePiece or WordPiece handle (the latter through encode_device_wp, spl_wp_host.h: the same limit): pieces of whole documents of at most SP_MAX_BYTES, one after the other -- text and offsets
+// spl_encode_batch on a SentencePiece, WordPiece or Unigram handle (the latter two through encode_device_wp, spl_wp_host.h, and encode_device_uni, spl_uni_host.h: the same limit): pieces of whole documents of at most SP_MAX_BYTES, one after the other -- text and offsets
 // to the device, the device call above with n_bytes ids of room, once more with the need it reported if that was short, the ids back.
 int encode_host_sp(spl_tokenizer* tk, const uint8_t* utf8, const uint64_t* doc_off, uint64_t n_docs, uint32_t flags, spl_result* r) {
     Ctx* c = tk->ctx[0].get();
@@ -136,7 +136,7 @@ int encode_host_sp(spl_tokenizer* tk, const uint8_t* utf8, const uint64_t* doc_o
     for (uint64_t d = 0; d < n_docs;) {
         uint64_t e = d + 1;
         const uint64_t lo = doc_off[d];
-        if (doc_off[e] - lo > SP_MAX_BYTES) return fail(SPL_EINVAL, std::string("spl_encode_batch: ") + (tk->wp ? "WordPiece" : "SentencePiece") + " mode takes documents of at most 64 MiB");
+        if (doc_off[e] - lo > SP_MAX_BYTES) return fail(SPL_EINVAL, std::string("spl_encode_batch: ") + (tk->uni ? "Unigram" : tk->wp ? "WordPiece" : "SentencePiece") + " mode takes documents of at most 64 MiB");
         while (e < n_docs && doc_off[e + 1] - lo <= SP_MAX_BYTES) e++;
         const uint64_t nb = doc_off[e] - lo, nd = e - d;
         rel.resize(nd + 1);
@@ -150,7 +150,7 @@ int encode_host_sp(spl_tokenizer* tk, const uint8_t* utf8, const uint64_t* doc_o
         HIP_TRY(hipStreamSynchronize(s));                        // (rel is reused by the next piece)
         uint64_t need = 0;
         for (int pass = 0; pass < 2; pass++) {
-            SPL_TRY((tk->wp ? encode_device_wp : encode_device_sp)(tk, c, c->d_sph_text.get(), nb, c->d_sph_off.get(), nd, flags, c->d_sph_ids.get(), c->sph_ids_cap, c->d_sph_oo.get(), s, nullptr));
+            SPL_TRY((tk->uni ? encode_device_uni : tk->wp ? encode_device_wp : encode_device_sp)(tk, c, c->d_sph_text.get(), nb, c->d_sph_off.get(), nd, flags, c->d_sph_ids.get(), c->sph_ids_cap, c->d_sph_oo.get(), s, nullptr));
             HIP_TRY(hipMemcpyAsync(&need, c->d_sph_oo.get() + nd, 8, hipMemcpyDeviceToHost, s));
             HIP_TRY(hipStreamSynchronize(s));
             if (need <= c->sph_ids_cap) break;

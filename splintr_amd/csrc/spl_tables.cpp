@@ -117,7 +117,7 @@ uint32_t host_cp_category(const HostTables& t, uint32_t cp) {
 }
 
 int build_tables(const uint8_t* splv, size_t splv_len, const uint8_t* ucls, size_t ucls_len, int pattern,
-                 bool force_byte_level, HostTables& out, std::string& err, bool keep_all_ids, bool wordpiece) {
+                 bool force_byte_level, HostTables& out, std::string& err, bool keep_all_ids, bool wordpiece, const char* mode) {
     // ---- class table -------------------------------------------------------------------
     if (ucls_len < 32 || memcmp(ucls, "SPLU", 4) != 0 || rd32(ucls + 4) < 1 || rd32(ucls + 4) > 3) { err = "bad unicode class table"; return 1; }
     const uint32_t ucls_version = rd32(ucls + 4);
@@ -193,9 +193,9 @@ int build_tables(const uint8_t* splv, size_t splv_len, const uint8_t* ucls, size
             size_t n = e - a;
             if (n && splv[a + n - 1] == '\r') n--;
             const std::string where = " (vocab.txt line " + std::to_string(ln + 1) + ")";
-            if (!n) { err = "WordPiece mode: an empty line inside the vocabulary" + where; return 1; }
-            if (n > 255) { err = "WordPiece mode: a key of more than 255 bytes" + where; return 1; }
-            if (!enc.emplace(std::string((const char*)splv + a, n), ln).second) { err = "WordPiece mode: a key is listed twice" + where; return 1; }
+            if (!n) { err = std::string(mode) + " mode: an empty line inside the vocabulary" + where; return 1; }
+            if (n > 255) { err = std::string(mode) + " mode: a key of more than 255 bytes" + where; return 1; }
+            if (!enc.emplace(std::string((const char*)splv + a, n), ln).second) { err = std::string(mode) + " mode: a key is listed twice" + where; return 1; }
             a = e + 1;
         }
     } else if (splv_len >= 4 && memcmp(splv, "SPLV", 4) == 0) {

@@ -71,9 +71,11 @@ void memo_seed_plan(const HostTables& t, uint32_t bits, uint32_t long_bits, Memo
 // `vocab` is either this repo's SPLV container or the reference's tiktoken text (autodetected by the
 // magic); force_byte_level = the reference's from_bytes_byte_level (tokenizer.rs:562-569); keep_all_ids = load_tiktoken_bpe_with_decoder
 // (vocab.rs:101-139): a duplicated key encodes to its first id and every listed id decodes; wordpiece = `vocab` is vocab.txt text, one key
-// per line, id = line number (WordPiece mode: the decoder side serves it, the encode tables are built but never probed).
+// per line, id = line number (WordPiece and Unigram mode: the decoder side serves it, the encode tables are built but never probed);
+// mode names the mode in the messages about such a file.
 int build_tables(const uint8_t* vocab, size_t vocab_len, const uint8_t* ucls, size_t ucls_len, int pattern,
-                 bool force_byte_level, HostTables& out, std::string& err, bool keep_all_ids = false, bool wordpiece = false);
+                 bool force_byte_level, HostTables& out, std::string& err, bool keep_all_ids = false, bool wordpiece = false,
+                 const char* mode = "WordPiece");
 
 // Host mirror of the device two-stage lookup (used by build checks and tests/hostsim).
 uint32_t host_cp_class(const HostTables& t, uint32_t cp);

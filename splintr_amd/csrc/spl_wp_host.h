@@ -43,41 +43,56 @@ int wp_load_table(const uint8_t* tab, uint64_t len, WpHost& w, std::string& err)
     return 0;
 }
 
-// The trie over the vocabulary's keys (id -> bytes: the handle's decoder table).  Node 0: the root of word-initial keys, every key as it
-// is; node 1: the root of continuation keys, every key that begins with the prefix and goes on, without the prefix.
-int wp_build_trie(const HostTables& ht, const std::string& prefix, WpHost& w, std::string& err) {
+// A trie over byte strings in the layout the matchers probe (WpTrie, spl_k_wp.h): an open-addressing hash of (node << 8 | byte) -> child
+// whose probe bound is measured at build, and node -> id.  WordPiece mode and Unigram mode (spl_uni_host.h) build theirs with it.
+struct TrieBuilder {
     std::unordered_map<uint32_t, uint32_t> child;
-    w.node_id.assign(2, WP_NONE);
-    auto insert = [&](uint32_t node, const uint8_t* k, uint32_t n, uint32_t id) {
+    std::vector<uint32_t> node_id;
+    explicit TrieBuilder(uint32_t roots) : node_id(roots, WP_NONE) {}
+    void insert(uint32_t node, const uint8_t* k, uint32_t n, uint32_t id) {
         for (uint32_t i = 0; i < n; i++) {
             auto it = child.find(node << 8 | k[i]);
             if (it == child.end()) {
-                it = child.emplace(node << 8 | k[i], (uint32_t)w.node_id.size()).first;
-                w.node_id.push_back(WP_NONE);
+                it = child.emplace(node << 8 | k[i], (uint32_t)node_id.size()).first;
+                node_id.push_back(WP_NONE);
             }
             node = it->second;
         }
-        w.node_id[node] = id;
-    };
+        node_id[node] = id;
+    }
+    uint32_t find(uint32_t node, const uint8_t* k, uint32_t n) const {
+        for (uint32_t i = 0; i < n && node != WP_NONE; i++) { auto it = child.find(node << 8 | k[i]); node = it == child.end() ? WP_NONE : it->second; }
+        return node;
+    }
+    void table(std::vector<uint2>& edges, uint32_t& bits, uint32_t& max_probe) const {
+        bits = 6;
+        while ((1ull << bits) < 2 * child.size() + 2) bits++;
+        edges.assign((size_t)1 << bits, make_uint2(WP_NONE, WP_NONE));
+        max_probe = 0;
+        const uint32_t mask = (1u << bits) - 1u;
+        for (const auto& kv : child) {
+            uint32_t h = (kv.first * 0x9E3779B1u) >> (32 - bits), k = 0;
+            while (edges[(h + k) & mask].x != WP_NONE) k++;
+            edges[(h + k) & mask] = make_uint2(kv.first, kv.second);
+            max_probe = std::max(max_probe, k);
+        }
+    }
+};
+
+// The trie over the vocabulary's keys (id -> bytes: the handle's decoder table).  Node 0: the root of word-initial keys, every key as it
+// is; node 1: the root of continuation keys, every key that begins with the prefix and goes on, without the prefix.
+int wp_build_trie(const HostTables& ht, const std::string& prefix, WpHost& w, std::string& err) {
+    TrieBuilder tb(2);
     for (uint32_t id = 0; id <= ht.max_id; id++) {
         if (!ht.tok_present[id]) continue;
         const uint8_t* k = ht.tok_bytes.data() + ht.tok_off[id];
         const uint32_t n = ht.tok_off[id + 1] - ht.tok_off[id];
-        insert(0u, k, n, id);
-        if (n > prefix.size() && memcmp(k, prefix.data(), prefix.size()) == 0) insert(1u, k + prefix.size(), n - (uint32_t)prefix.size(), id);
-        if (w.node_id.size() >= (1u << 24)) { err = "WordPiece mode: the vocabulary's trie has 2^24 nodes or more"; return 1; }
+        tb.insert(0u, k, n, id);
+        if (n > prefix.size() && memcmp(k, prefix.data(), prefix.size()) == 0) tb.insert(1u, k + prefix.size(), n - (uint32_t)prefix.size(), id);
+        if (tb.node_id.size() >= (1u << 24)) { err = "WordPiece mode: the vocabulary's trie has 2^24 nodes or more"; return 1; }
     }
-    w.bits = 6;
-    while ((1ull << w.bits) < 2 * child.size() + 2) w.bits++;
-    w.edges.assign((size_t)1 << w.bits, make_uint2(WP_NONE, WP_NONE));
-    w.max_probe = 0;
-    const uint32_t mask = (1u << w.bits) - 1u;
-    for (const auto& kv : child) {
-        uint32_t h = (kv.first * 0x9E3779B1u) >> (32 - w.bits), k = 0;
-        while (w.edges[(h + k) & mask].x != WP_NONE) k++;
-        w.edges[(h + k) & mask] = make_uint2(kv.first, kv.second);
-        w.max_probe = std::max(w.max_probe, k);
-    }
+    tb.table(w.edges, w.bits, w.max_probe);
+    w.node_id = std::move(tb.node_id);
     return 0;
 }
 

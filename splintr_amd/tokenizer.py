@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes
 import json
 import os
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -285,6 +285,68 @@ class Tokenizer:
     def from_vocab_txt(path: str, **options) -> "Tokenizer":
         """Extension: from_bytes_wordpiece on a vocab.txt file."""
         return Tokenizer.from_bytes_wordpiece(_read(path), **options)
+
+    @staticmethod
+    def from_bytes_unigram(pieces: Sequence[Tuple[str, float]], unk_id: int, *, prepend_scheme: str = "always",
+                           special_tokens: Optional[Dict[str, int]] = None, device: int = 0) -> "Tokenizer":
+        """Extension: a Unigram vocabulary (XLM-RoBERTa, bge-m3, multilingual-e5-*, T5, mT5, ALBERT) -- (piece, score) pairs, id =
+        index -- under Hugging Face's Metaspace pre-tokeniser with prepend_scheme "always" or "never" and models.Unigram with
+        byte_fallback off.  The Viterbi runs ON THE GPU (csrc/spl_k_uni.h) on text taken as already normalised; every
+        encode_* method works, <s> / </s> come from encode_batch_pairs' prefix / middle / suffix, and special-token literals in the text
+        are not looked for (the *_with_special methods refuse on a handle with special_tokens).  decode turns U+2581 into a space and
+        drops the one leading space "always" added; decode_bytes returns the vocabulary's own bytes."""
+        if prepend_scheme not in ("always", "never"):
+            raise ValueError(f"Unigram mode: prepend_scheme {prepend_scheme!r} is not supported (\"always\" or \"never\")")
+        keys = [p.encode("utf-8") for p, _ in pieces]
+        for i, k in enumerate(keys):
+            if b"\n" in k or k.endswith(b"\r"):
+                raise ValueError(f"Unigram mode: piece {i} contains a line feed or ends in a carriage return (the vocabulary travels one key per line)")
+        self = Tokenizer.__new__(Tokenizer)
+        L = _ffi.lib()
+        blob = b"\n".join(keys) + b"\n" if keys else b""
+        ucls = _read(_unicode_table_path("pcre2"))
+        scores = (ctypes.c_double * len(keys))(*[float(s) for _, s in pieces])
+        opts = _ffi.SplOpts(0, device, _ffi.SPL_OPT_UNIGRAM, unk_id=int(unk_id), scores=scores, uni_flags=1 if prepend_scheme == "always" else 0)
+        self._h = L.spl_create(blob, len(blob), ucls, len(ucls), ctypes.byref(opts))
+        if not self._h:
+            raise ValueError(_ffi.last_error())
+        self._device, self._pattern, self._sentencepiece, self._wordpiece = device, CL100K_BASE_PATTERN, False, False
+        self._unigram = prepend_scheme
+        self._special = dict(special_tokens or {})
+        for lit, tid in self._special.items():
+            b = lit.encode("utf-8")
+            if L.spl_add_special(self._h, b, len(b), int(tid)) != 0:
+                raise ValueError(_ffi.last_error())
+        return self
+
+    @staticmethod
+    def from_tokenizer_json(path: str, *, ignore_normalizer: bool = False, device: int = 0) -> "Tokenizer":
+        """Extension: from_bytes_unigram on a Hugging Face tokenizer.json whose model is Unigram (byte_fallback off) and whose
+        pre-tokeniser is Metaspace; anything else is refused by name.  A normaliser is refused too unless ignore_normalizer=True:
+        the text is then taken as already normalised.  Added tokens marked special become special_tokens."""
+        cfg = json.loads(_read(path).decode("utf-8"))
+        model, pre, norm = cfg.get("model") or {}, cfg.get("pre_tokenizer") or {}, cfg.get("normalizer")
+        if model.get("type") != "Unigram":
+            raise ValueError(f"from_tokenizer_json: model {model.get('type')!r} is not supported (Unigram)")
+        if model.get("byte_fallback"):
+            raise ValueError("from_tokenizer_json: Unigram with byte_fallback is not supported")
+        if pre.get("type") != "Metaspace":
+            raise ValueError(f"from_tokenizer_json: pre_tokenizer {pre.get('type')!r} is not supported (Metaspace)")
+        if pre.get("replacement", "▁") != "▁" or pre.get("split", True) is not True:
+            raise ValueError("from_tokenizer_json: Metaspace with another replacement than U+2581, or with split=false, is not supported")
+        scheme = pre.get("prepend_scheme") or ("always" if pre.get("add_prefix_space", True) else "never")
+        if norm is not None and not ignore_normalizer:
+            raise ValueError(f"from_tokenizer_json: the normalizer ({norm.get('type')!r}) does not run on the device; normalise the text "
+                             "yourself and pass ignore_normalizer=True")
+        if model.get("unk_id") is None:
+            raise ValueError("from_tokenizer_json: Unigram without unk_id is not supported")
+        special = {t["content"]: int(t["id"]) for t in cfg.get("added_tokens") or [] if t.get("special")}
+        return Tokenizer.from_bytes_unigram([(p, s) for p, s in model["vocab"]], int(model["unk_id"]), prepend_scheme=scheme,
+                                            special_tokens=special, device=device)
+
+    def is_unigram(self) -> bool:
+        """Extension: True for a Unigram handle (from_bytes_unigram, from_tokenizer_json)."""
+        return getattr(self, "_unigram", None) is not None
 
     def is_wordpiece(self) -> bool:
         """Extension: True for a WordPiece handle (from_bytes_wordpiece, from_vocab_txt)."""
@@ -615,6 +677,9 @@ class Tokenizer:
 
     def _post(self, text: str) -> str:
         """postprocess_decode (src/core/tokenizer.rs:913-929): SentencePiece mode turns every U+2581 into a space."""
+        if getattr(self, "_unigram", None) is not None:      # Hugging Face's Metaspace decoder
+            text = text.replace("\u2581", " ")
+            return text[1:] if self._unigram == "always" and text.startswith(" ") else text
         return text.replace("\u2581", " ") if self._sentencepiece else text
 
     def decode(self, tokens: Sequence[int]) -> str:
