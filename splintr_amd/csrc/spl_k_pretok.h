@@ -340,10 +340,25 @@ void k_pretok(const uint8_t* e_text, const uint64_t* e_doc_off, uint32_t e_n_byt
             const uint32_t tw = s_txt32[wi];
             const uint32_t ts4 = (s_ts[i0 >> 5] >> (i0 & 31)) & 0xFu;
             const uint32_t sk4 = (s_sk[i0 >> 5] >> (i0 & 31)) & 0xFu;
+#if SPL_WORD_INSIDE
+            // The word that holds one whole two-byte character (word_inside: arithmetic on tw) stays in the ASCII branch: the
+            // table reads are the wavefront's, the lane mends its character's two bytes with one lookup -- no neighbouring
+            // word, no text-start bits beyond ts4, no guard for the 63 lanes to wait for (profiles/word_inside.txt).
+            const bool mid = sk4 == 0u && i0 + 3 < iB && w0 + i0 >= 0;
+            const bool beyond = (tw & 0x80808080u) != 0u;
+            uint32_t kin = 0u;
+            const bool ins = mid && beyond && word_inside(tw, ts4, kin);
+            if ((mid && !beyond) || ins) {
+                const KindEnt e[4] = {s_aent[tw & 0x7Fu], s_aent[(tw >> 8) & 0x7Fu], s_aent[(tw >> 16) & 0x7Fu], s_aent[(tw >> 24) & 0x7Fu]};
+                wk = classify_word_ascii(e, ts4);
+                if (ins) wk = classify_word_inside(T, KPAT, tw, kin, wk, [&](uint32_t c) { return s_kent[c]; });
+            } else {
+#else
             if (!(tw & 0x80808080u) && sk4 == 0u && i0 + 3 < iB && w0 + i0 >= 0) {
                 const KindEnt e[4] = {s_aent[tw & 0xFFu], s_aent[(tw >> 8) & 0xFFu], s_aent[(tw >> 16) & 0xFFu], s_aent[tw >> 24]};
                 wk = classify_word_ascii(e, ts4);
             } else {
+#endif
                 // A word with a byte beyond ASCII (or at an edge of the text): the neighbouring words and the text-start bits
                 // of [i0 - 4, i0 + 12) go into registers once; the look-back / look-ahead (at most 3 bytes either way, plus
                 // the decode) is arithmetic on them.  (Bytes before window index 0 do not exist for the look-back: that

@@ -5,8 +5,9 @@
 // with a dozen ballots per 64-byte row: a fifth of the kernel's vector instructions for the two steps
 // (profiles/r04_phase_instruction_mix.txt).  Here a lane turns its four bytes into the records AND into two words of
 // NIBBLES, one nibble per kind: bit k of nibble j = "byte k of this lane's word is of kind j".  For ASCII -- nearly every
-// word of English / code -- that is four reads of a 128-entry LDS table and a few shifts.  A word with a byte beyond
-// ASCII, away from every text edge, goes through classify_word_text: first the two-byte form (classify_word_two: accented
+// word of English / code -- that is four reads of a 128-entry LDS table and a few shifts.  A word that holds one whole
+// two-byte character and two ASCII bytes takes the same four reads and mends two bytes (word_inside).  Any other word with
+// a byte beyond ASCII, away from every text edge, goes through classify_word_text: first the two-byte form (classify_word_two: accented
 // Latin, Greek, Cyrillic, Hebrew, Arabic), then the three-character form for well-formed text of any length (a dash, CJK);
 // what both decline -- malformed text, a text edge within three bytes, a special-literal span -- takes the general path
 // classify_word.  Eight neighbouring lanes then transpose their 8 x 8 nibbles
@@ -297,6 +298,56 @@ SPL_HD bool classify_word_two(const DeviceTables& T, int pattern, uint32_t wp, u
         }
     }
     return true;
+}
+
+#ifndef SPL_WORD_INSIDE
+#define SPL_WORD_INSIDE 1        /* 0: no form of its own for the word that holds one whole two-byte character (A/B; profiles/word_inside.txt) */
+#endif
+
+// The word that holds ONE WHOLE two-byte character and two ASCII bytes -- three alignments in four of an accented letter in
+// English, Spanish or German text: a lead 110xxxxx in byte 0, 1 or 2, its continuation byte 10xxxxxx right behind it, no
+// other byte beyond ASCII.  Such a word needs nothing outside itself: no neighbouring word (no character reaches into it
+// or out of it), no text-start bit but its own four, no edge but the caller's (below) -- so the lane that holds it stays
+// with the ASCII lanes of its wavefront, shares their four table reads, and only mends the two bytes of the character.
+// word_inside is the test, word arithmetic on tw alone; k: the lead's byte.  A text start ON the continuation byte cuts
+// the character in two (the general path: a lead without its continuation and a stray continuation byte, each "other"):
+// declined.  A text start anywhere else in the word -- on the lead, on an ASCII byte -- does not touch the character and is
+// what classify_word_ascii makes of ts4.
+//   precondition (caller, the ASCII branch's own): no special-literal span in the word, i0 + 3 < iB, i0 >= lo
+SPL_HD bool word_inside(uint32_t tw, uint32_t ts4, uint32_t& k) {
+    const uint32_t hi = tw & 0x80808080u, t1 = tw << 1;
+    const uint32_t ld = hi & t1, C = hi ^ ld;                  // bit 7 of a byte: 11xxxxxx / 10xxxxxx
+    // two bytes beyond ASCII, a continuation behind every lead (so: one lead in byte 0..2, its continuation), no lead 111xxxxx
+    // (one expression without a branch: a lane that tests keeps its wavefront for a dozen instructions, not for three jumps)
+    const bool shape = (C != 0u) & (C == (ld << 8)) & ((hi & (hi - 1u)) == C) & ((ld & (t1 << 1)) == 0u);
+    k = (uint32_t)ctz32(ld | 0x80000000u) >> 3;
+#if SPL_WORDS_SIM_BREAK == 4
+    return shape;
+#else
+    return shape & !((ts4 >> (k + 1u)) & 1u);
+#endif
+}
+// a: classify_word_ascii of the word's table entries, the two bytes of the character looked up as (byte & 0x7F) -- their
+// entries are masked out here; what stays of them is ts4's: V1_TS, and CB_TSTART | CB_SYNC on the lead's record.  The
+// character as classify_word_two's one-character sub-case makes it: one lookup, one kind entry, CS on the lead alone.
+template <class KENT>
+SPL_HD WordKinds classify_word_inside(const DeviceTables& T, int pattern, uint32_t tw, uint32_t k, const WordKinds& a, const KENT& kent) {
+    const uint32_t w = tw >> (8u * k), cp1 = ((w & 0x1Fu) << 6) | ((w >> 8) & 0x3Fu);
+    const uint32_t sh = T.ucls_shift, lowm = (1u << sh) - 1u;
+    const uint32_t c = T.ucls_stage2[((uint32_t)T.ucls_stage1[cp1 >> sh] << sh) | (cp1 & lowm)];
+    const KindEnt e = kent(c);
+    const bool bad = !(SPL_BIT(c) & (M_L | M_OTHER)) || (pattern != PAT_CL100K && c == C_M);
+    const uint32_t m = 3u << k, ascn = (~m & 0xFu) * 0x11111111u;
+#if SPL_WORDS_SIM_BREAK == 3
+    const uint32_t cs = (V1_CS * 3u) << k;
+#else
+    const uint32_t cs = V1_CS << k;                             // CS on the lead byte alone
+#endif
+    WordKinds o;
+    o.v0 = (a.v0 & ascn) | e.x * m;
+    o.v1 = (a.v1 & (ascn | (V1_TS * 0xFu))) | (e.y | (bad ? V1_BAD : 0u)) * m | cs;
+    o.rec = (a.rec & ~((CB_CLASS * 0x0101u) << (8u * k))) | (((1u << CB_LEN_SHIFT) | c | ((uint32_t)C_CONT << 8)) << (8u * k));
+    return o;
 }
 
 // The COMMON word beyond ASCII: well-formed UTF-8, away from every edge -- an accented letter, a dash, a run of CJK.  The
