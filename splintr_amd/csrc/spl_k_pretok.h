@@ -348,10 +348,27 @@ void k_pretok(const uint8_t* e_text, const uint64_t* e_doc_off, uint32_t e_n_byt
             const bool beyond = (tw & 0x80808080u) != 0u;
             uint32_t kin = 0u;
             const bool ins = mid && beyond && word_inside(tw, ts4, kin);
+#if SPL_WORD_STRADDLE
+            // The two words that one two-byte character straddles (lead in byte 3 / continuation in byte 0) stay as well: the
+            // lanes of the shape read the ONE neighbouring word and the two bits of the neighbouring byte
+            // (profiles/word_straddle.txt); whatever word_straddle declines goes on to the branch below.
+            uint32_t side = (mid && beyond && !ins) ? straddle_shape(tw) : 0u, nb = 0u;
+            if (side) {
+                const int q = side == 1u ? i0 + 4 : i0 > 0 ? i0 - 1 : 0;         // (i0 + 4 <= Wv: staged, and a bit of s_ts / s_sk)
+                nb = s_txt32[q >> 2];
+                side = word_straddle(side, nb, ts4, (s_ts[q >> 5] >> (q & 31)) & 1u, (s_sk[q >> 5] >> (q & 31)) & 1u, i0, iB,
+                                     w0 < 0 ? (int)-w0 : 0);
+            }
+            if ((mid && !beyond) || ins || side) {
+#else
             if ((mid && !beyond) || ins) {
+#endif
                 const KindEnt e[4] = {s_aent[tw & 0x7Fu], s_aent[(tw >> 8) & 0x7Fu], s_aent[(tw >> 16) & 0x7Fu], s_aent[(tw >> 24) & 0x7Fu]};
                 wk = classify_word_ascii(e, ts4);
                 if (ins) wk = classify_word_inside(T, KPAT, tw, kin, wk, [&](uint32_t c) { return s_kent[c]; });
+#if SPL_WORD_STRADDLE
+                if (side) wk = classify_word_straddle(T, KPAT, tw, nb, side, wk, [&](uint32_t c) { return s_kent[c]; });
+#endif
             } else {
 #else
             if (!(tw & 0x80808080u) && sk4 == 0u && i0 + 3 < iB && w0 + i0 >= 0) {

@@ -6,7 +6,8 @@
 // (profiles/r04_phase_instruction_mix.txt).  Here a lane turns its four bytes into the records AND into two words of
 // NIBBLES, one nibble per kind: bit k of nibble j = "byte k of this lane's word is of kind j".  For ASCII -- nearly every
 // word of English / code -- that is four reads of a 128-entry LDS table and a few shifts.  A word that holds one whole
-// two-byte character and two ASCII bytes takes the same four reads and mends two bytes (word_inside).  Any other word with
+// two-byte character and two ASCII bytes takes the same four reads and mends two bytes (word_inside); the two words that
+// one such character straddles take them and mend one byte each (word_straddle).  Any other word with
 // a byte beyond ASCII, away from every text edge, goes through classify_word_text: first the two-byte form (classify_word_two: accented
 // Latin, Greek, Cyrillic, Hebrew, Arabic), then the three-character form for well-formed text of any length (a dash, CJK);
 // what both decline -- malformed text, a text edge within three bytes, a special-literal span -- takes the general path
@@ -347,6 +348,61 @@ SPL_HD WordKinds classify_word_inside(const DeviceTables& T, int pattern, uint32
     o.v0 = (a.v0 & ascn) | e.x * m;
     o.v1 = (a.v1 & (ascn | (V1_TS * 0xFu))) | (e.y | (bad ? V1_BAD : 0u)) * m | cs;
     o.rec = (a.rec & ~((CB_CLASS * 0x0101u) << (8u * k))) | (((1u << CB_LEN_SHIFT) | c | ((uint32_t)C_CONT << 8)) << (8u * k));
+    return o;
+}
+
+#ifndef SPL_WORD_STRADDLE
+#define SPL_WORD_STRADDLE 1      /* 0: no form of its own for the two words a two-byte character straddles (A/B; profiles/word_straddle.txt) */
+#endif
+
+// The two words that ONE two-byte character STRADDLES -- the fourth alignment of an accented letter: the lead 110xxxxx in
+// byte 3 of a word (the "lead word", side 1), its continuation byte 10xxxxxx in byte 0 of the next (the "continuation word",
+// side 2), no other byte of either beyond ASCII.  Each needs one byte outside itself -- byte 0 of the word behind / byte 3
+// of the word in front -- and that byte's text-start and special-literal bits: not both neighbouring words, sixteen
+// text-start bits and classify_word_text's guard.  The lanes stay in the ASCII branch as the "inside" lanes do.
+// straddle_shape is the part of the test that is arithmetic on tw alone (every lane with a byte beyond ASCII runs it:
+// two comparisons, no branch); word_straddle finishes it for the lanes of the shape with the neighbouring word nb (the
+// one behind for side 1, in front for side 2) and the bits of the neighbouring byte.  Declined, for the paths they had:
+// a text start ON the continuation byte (it cuts the character: tsq for side 1, bit 0 of ts4 for side 2), a special-literal
+// span on the neighbouring byte, a continuation byte that is not text of this window (i0 + 4 >= iB), a lead before the
+// first byte that exists (i0 - 1 < lo; that covers the window's first word), both alignments in one word.  A text start on
+// the lead does not touch the character.  (The overlong leads 0xC0 / 0xC1 are taken, as classify_word_two takes them.)
+//   precondition (caller, the ASCII branch's own): no special-literal span in the word, i0 + 3 < iB, i0 >= lo
+SPL_HD uint32_t straddle_shape(uint32_t tw) {
+    return (tw & 0xE0808080u) == 0xC0000000u ? 1u : (tw & 0x808080C0u) == 0x00000080u ? 2u : 0u;
+}
+SPL_HD uint32_t word_straddle(uint32_t side, uint32_t nb, uint32_t ts4, uint32_t tsq, uint32_t skq, int i0, int iB, int lo) {
+#if SPL_WORDS_SIM_BREAK == 6
+    const bool cut1 = false, cut2 = false;
+#else
+    const bool cut1 = tsq != 0u, cut2 = (ts4 & 1u) != 0u;
+#endif
+    const bool lead = (side == 1u) & ((nb & 0xC0u) == 0x80u) & !cut1 & (skq == 0u) & (i0 + 4 < iB);
+    const bool cont = (side == 2u) & ((nb & 0xE0000000u) == 0xC0000000u) & !cut2 & (skq == 0u) & (i0 - 1 >= lo);
+    return lead ? 1u : cont ? 2u : 0u;
+}
+// a: classify_word_ascii of the word's table entries, the odd byte looked up as (byte & 0x7F) and masked out here, ts4's part
+// of it kept.  The character as classify_word_two's one-character sub-case makes it (hasB with k1 = 3 / hasA): one lookup,
+// one kind entry; the lead word gets CS, class and length on byte 3, the continuation word C_CONT and no CS on byte 0.
+template <class KENT>
+SPL_HD WordKinds classify_word_straddle(const DeviceTables& T, int pattern, uint32_t tw, uint32_t nb, uint32_t side, const WordKinds& a,
+                                        const KENT& kent) {
+    const bool ld = side == 1u;
+    const uint32_t cp1 = ld ? (((tw >> 24) & 0x1Fu) << 6) | (nb & 0x3Fu) : (((nb >> 24) & 0x1Fu) << 6) | (tw & 0x3Fu);
+    const uint32_t sh = T.ucls_shift, lowm = (1u << sh) - 1u;
+    const uint32_t c = T.ucls_stage2[((uint32_t)T.ucls_stage1[cp1 >> sh] << sh) | (cp1 & lowm)];
+    const KindEnt e = kent(c);
+    const bool bad = !(SPL_BIT(c) & (M_L | M_OTHER)) || (pattern != PAT_CL100K && c == C_M);
+    const uint32_t m = ld ? 8u : 1u, ascn = (~m & 0xFu) * 0x11111111u;
+#if SPL_WORDS_SIM_BREAK == 5
+    const uint32_t cs = ld ? V1_CS << 3 : V1_CS;
+#else
+    const uint32_t cs = ld ? V1_CS << 3 : 0u;                   // CS on the lead byte alone
+#endif
+    WordKinds o;
+    o.v0 = (a.v0 & ascn) | e.x * m;
+    o.v1 = (a.v1 & (ascn | (V1_TS * 0xFu))) | (e.y | (bad ? V1_BAD : 0u)) * m | cs;
+    o.rec = ld ? (a.rec & ~(CB_CLASS << 24)) | (((1u << CB_LEN_SHIFT) | c) << 24) : (a.rec & ~CB_CLASS) | (uint32_t)C_CONT;
     return o;
 }
 
