@@ -326,6 +326,25 @@ int spl_encode_batch_device(spl_tokenizer* t, const uint8_t* d_utf8, uint64_t n_
                             uint64_t n_docs, uint32_t flags, uint32_t* d_ids, uint64_t ids_capacity,
                             uint64_t* d_out_off, void* hip_stream);
 
+/* WordPiece and Unigram handles: spl_encode_batch_device plus WHERE every id lies in the caller's text, from the encode kernels
+ * themselves (these modes' ids do not decode to the text, so spl_token_spans_device cannot say).  Ids and offsets are
+ * spl_encode_batch_device's, with everything promised there (capacity, footprint, text tail); row i of a span buffer is stored exactly
+ * when d_ids[i] is -- nothing at or beyond row min(T, ids_capacity).
+ *   d_byte_span[ids_capacity][2]  (start, end) in bytes of the token's document: from the first byte of the input character its first
+ *                         character came from to the end of the input character its last came from.  WordPiece: characters the
+ *                         normaliser drops, spaces and ill-formed bytes belong to no token, "##" has no source, a word that becomes
+ *                         unk_id spans the word.  Unigram: a space matched as U+2581 is its one byte; the marker prepended to a
+ *                         document has the document's first character as its source; a fused run of unk is one span.
+ *   d_char_span[ids_capacity][2]  the same in characters: offset p becomes the number of bytes b with (b & 0xC0) != 0x80 in front of it
+ *                         (Python str indices for valid text; Hugging Face's Encoding.offsets).
+ * Either may be NULL (both: SPL_EINVAL); both 8-byte aligned.  SPL_EINVAL for a handle of another mode.  Workspace beyond the mode's,
+ * reserved by the first such call: WordPiece 12 bytes per byte of text (the normaliser's source map), character spans 8 bytes per 64.
+ * Synchronises as spl_encode_batch_device does on the same handle (WordPiece once, Unigram never); the per-kernel profile counts these
+ * calls in the mode's slots. */
+int spl_encode_batch_spans_device(spl_tokenizer* t, const uint8_t* d_utf8, uint64_t n_bytes, const uint64_t* d_doc_off,
+                                  uint64_t n_docs, uint32_t flags, uint32_t* d_ids, uint64_t ids_capacity, uint64_t* d_out_off,
+                                  int32_t* d_byte_span, int32_t* d_char_span, void* hip_stream);
+
 /* Handles with SPL_PATTERN_CUSTOM: spl_encode_batch / spl_decode_batch work as for every other handle (the split of each pipeline chunk
  * runs on the device splitter, csrc/spl_rx_split.h, behind the GPU's special-token scan with SPL_WITH_SPECIAL).  What the device matcher
  * gives up on is handled per DOCUMENT: the 256-byte blocks of such positions come back in a small pinned list, the documents they lie in

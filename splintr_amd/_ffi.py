@@ -30,7 +30,7 @@ SYMBOLS = [
     "spl_allgather_slabs", "spl_allgather_slabs_p2p", "spl_gatherv_unpack_at", "spl_allgatherv_csr", "spl_split_host", "spl_encode_chunks_device",
     "spl_split_device", "spl_device_split_fallbacks", "spl_small_path_calls", "spl_pick_stream", "spl_memo_stats", "spl_memo_seed_stats", "spl_debug_memo_entry",
     "spl_pad_device", "spl_pack_device", "spl_pair_device", "spl_chat_work_bytes", "spl_chat_device", "spl_seqpack_work_bytes", "spl_seqpack_device", "spl_window_work_bytes", "spl_window_device",
-    "spl_decode_reserve_device", "spl_decode_batch_device", "spl_max_token_bytes", "spl_token_spans_device",
+    "spl_decode_reserve_device", "spl_decode_batch_device", "spl_max_token_bytes", "spl_token_spans_device", "spl_encode_batch_spans_device",
     "spl_stream_reserve_device", "spl_stream_decode_device",
     "spl_get_option", "spl_stop_reserve_device", "spl_stop_match_device",
     "spl_heal_reserve_device", "spl_heal_begin_device", "spl_heal_step_device",
@@ -421,6 +421,8 @@ def lib() -> ctypes.CDLL:
     L.spl_result_free.restype = None
     L.spl_encode_batch_device.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_uint32, vp,
                                           ctypes.c_uint64, vp, vp]
+    L.spl_encode_batch_spans_device.argtypes = [vp, vp, ctypes.c_uint64, vp, ctypes.c_uint64, ctypes.c_uint32, vp,
+                                                ctypes.c_uint64, vp, vp, vp, vp]
     L.spl_decode_batch.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.POINTER(u8p), ctypes.POINTER(u64p)]
     L.spl_free.argtypes = [vp]
     L.spl_free.restype = None

@@ -322,6 +322,21 @@ static int spl_encode_batch_device_impl(spl_tokenizer* t, const uint8_t* d_utf8,
                                            .ids = d_ids, .ids_cap = ids_capacity, .out_off = d_out_off, .stream = (hipStream_t)hip_stream});
 }
 
+static int spl_encode_batch_spans_device_impl(spl_tokenizer* t, const uint8_t* d_utf8, uint64_t n_bytes, const uint64_t* d_doc_off,
+                                              uint64_t n_docs, uint32_t flags, uint32_t* d_ids, uint64_t ids_capacity, uint64_t* d_out_off,
+                                              int32_t* d_byte_span, int32_t* d_char_span, void* hip_stream) {
+    const std::string who = "spl_encode_batch_spans_device";
+    if (!t || !d_doc_off || !d_out_off || (n_bytes && (!d_utf8 || !d_ids))) return fail(SPL_EINVAL, who + ": null argument");
+    if (!d_byte_span && !d_char_span) return fail(SPL_EINVAL, who + ": d_byte_span and d_char_span are both null -- spl_encode_batch_device is the call without spans");
+    if (!t->wp && !t->uni)
+        return fail(SPL_EINVAL, who + ": the handle is neither WordPiece nor Unigram mode -- the spans of a byte-pair handle's ids are spl_token_spans_device's");
+    if (((uintptr_t)d_byte_span & 7) || ((uintptr_t)d_char_span & 7)) return fail(SPL_EINVAL, who + ": a span buffer is not 8-byte aligned");
+    HIP_TRY(hipSetDevice(t->ctx[0]->device));
+    const SpanReq sr{d_byte_span, d_char_span};
+    return (t->uni ? encode_device_uni_spans : encode_device_wp_spans)(t, t->ctx[0].get(), d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_capacity,
+                                                                       d_out_off, (hipStream_t)hip_stream, nullptr, &sr);
+}
+
 static int spl_encode_batch_device_packed_impl(spl_tokenizer* t, const uint8_t* d_utf8, uint64_t n_bytes, const uint64_t* d_doc_off,
                                    uint64_t n_docs, uint32_t flags, uint32_t* d_ids, uint64_t ids_capacity,
                                    uint64_t* d_out_off, uint32_t* d_slab, uint64_t cap_words, uint64_t max_docs,
@@ -815,6 +830,14 @@ int spl_encode_batch_device(spl_tokenizer* t, const uint8_t* d_utf8, uint64_t n_
     return guarded("spl_encode_batch_device", [&] {
         return spl_encode_batch_device_impl(t, d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_capacity, d_out_off, hip_stream); });
 }
+int spl_encode_batch_spans_device(spl_tokenizer* t, const uint8_t* d_utf8, uint64_t n_bytes, const uint64_t* d_doc_off,
+                                  uint64_t n_docs, uint32_t flags, uint32_t* d_ids, uint64_t ids_capacity, uint64_t* d_out_off,
+                                  int32_t* d_byte_span, int32_t* d_char_span, void* hip_stream) {
+    return guarded("spl_encode_batch_spans_device", [&] {
+        return spl_encode_batch_spans_device_impl(t, d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_capacity, d_out_off, d_byte_span,
+                                                  d_char_span, hip_stream); });
+}
+
 int spl_encode_batch_device_packed(spl_tokenizer* t, const uint8_t* d_utf8, uint64_t n_bytes, const uint64_t* d_doc_off,
                                    uint64_t n_docs, uint32_t flags, uint32_t* d_ids, uint64_t ids_capacity,
                                    uint64_t* d_out_off, uint32_t* d_slab, uint64_t cap_words, uint64_t max_docs,

@@ -26,6 +26,7 @@
 // and tells it where they are.
 #pragma once
 #include "spl_common.h"
+#include "spl_k_textspans.h"
 #include "spl_k_wp.h"
 
 namespace spl {
@@ -55,6 +56,7 @@ struct UniArgs {
     uint32_t* lr_n; uint32_t* lr_start; uint32_t* lr_cnt; uint64_t* lr_slot;   // long words: [tiles], [tiles * UNI_LREC] x 3
     UniNodes g;                                              // [n_bytes + 1] each: the long path's nodes
     uint32_t* ids; uint64_t ids_cap; uint64_t* out_off;
+    TextSpanOut so;                                          // the <write, span> kernels only: where the spans go
 };
 
 // ---- the per-word logic, plain C++ ---------------------------------------------------------------------------------------------------
@@ -92,9 +94,11 @@ SPL_HD void uni_relax(const UniNodes& n, uint32_t e, double v, uint32_t id, uint
 }
 // The chosen path from `we` back to the word's first node b; with a source (has_vm) node b is reached from it by id_b.  A run of unk is
 // one id.  Returns the tokens; WRITE stores them backwards from ids[at] (only below cap).  Every back pointer is checked to lie in
-// [b, e): a node without a proposal ends the walk instead of leading it astray.
-template <bool WRITE> SPL_HD uint32_t uni_backtrack(const UniNodes& n, uint32_t b, uint32_t we, bool has_vm, uint32_t id_b, uint32_t unk_id,
-                                                    uint32_t* ids, uint64_t at, uint64_t cap) {
+// [b, e): a node without a proposal ends the walk instead of leading it astray.  span(slot, from, e, fused): the edge (from, e] --
+// from UNI_FROM_S: the source's -- belongs to the id in `slot`; fused: as one more unk at the front of the run that slot holds.
+struct UniNoSpan { SPL_HD void operator()(uint64_t, uint32_t, uint32_t, bool) const {} };
+template <bool WRITE, class SPAN = UniNoSpan> SPL_HD uint32_t uni_backtrack(const UniNodes& n, uint32_t b, uint32_t we, bool has_vm, uint32_t id_b, uint32_t unk_id,
+                                                    uint32_t* ids, uint64_t at, uint64_t cap, SPAN&& span = SPAN()) {
     uint32_t cnt = 0, e = we;
     bool prev_unk = false;
     for (;;) {
@@ -103,9 +107,9 @@ template <bool WRITE> SPL_HD uint32_t uni_backtrack(const UniNodes& n, uint32_t 
         else { id = n.bid[e]; from = n.bfrom[e]; if (from != UNI_FROM_S && (from < b || from >= e)) break; }
         const bool unk = id == unk_id;
         if (!(unk && prev_unk)) {
-            if (WRITE) { if (at < cap) ids[at] = id; at--; }
+            if (WRITE) { if (at < cap) { ids[at] = id; span(at, from, e, false); } at--; }
             cnt++;
-        }
+        } else if (WRITE) { if (at + 1u < cap) span(at + 1u, from, e, true); }
         prev_unk = unk;
         if (from == UNI_FROM_S) break;
         e = from;
@@ -155,7 +159,20 @@ __device__ __forceinline__ void uni_step_source(const UniArgs& a, const UniNodes
     });
 }
 
-template <bool WRITE> __global__ __launch_bounds__(UNI_NT) void k_uni_match(UniArgs a) {
+// The span of one edge of a word's chosen path, for uni_backtrack (the <write, span> kernels): raw positions are the kernel's positions
+// less `shift`; the word's first key byte is at b, its document starts at raw ds with c0 characters in front of it.  An edge from the
+// source begins at the space the marker stands for, or -- the virtual marker -- at the document's first character, and covers it whole.
+struct UniSpanPut {
+    const TextSpanOut& so; uint32_t shift, b, ds, c0, first_end; bool sp;
+    __device__ __forceinline__ void operator()(uint64_t slot, uint32_t from, uint32_t e, bool fused) const {
+        const uint32_t rs = (from == UNI_FROM_S ? (sp ? b - 1u : b) : from) - shift;
+        const uint32_t re = (from == UNI_FROM_S && !sp ? max(e, first_end) : e) - shift;
+        ts_store(so, slot, ds, c0, rs, re, fused);
+    }
+};
+
+template <bool WRITE, bool SPAN = false> __global__ __launch_bounds__(UNI_NT) void k_uni_match(UniArgs a) {
+    static_assert(WRITE || !SPAN, "the spans are the write pass's");
     static_assert(UNI_NT == 256 && UNI_TB == 2 * UNI_NT && UNI_S / 16 <= UNI_NT && UNI_S < 0xFFFE, "two positions a lane in phase B; one 16-byte group a lane; wp_block_excl");
     __shared__ __attribute__((aligned(16))) uint8_t s_txt[UNI_S];
     __shared__ uint32_t s_brk[UNI_BW + 1], s_bd[UNI_BW + 1], s_lit[UNI_BW + 1];       // document starts; word bounds; literal U+2581
@@ -281,6 +298,12 @@ template <bool WRITE> __global__ __launch_bounds__(UNI_NT) void k_uni_match(UniA
                     const uint32_t mid = a.marker_node != WP_NONE ? a.trie.node_id[a.marker_node] : WP_NONE;
                     if (mid != WP_NONE) id_b = mid;
                 }
+                if constexpr (SPAN) {
+                    const uint32_t shift = (uint32_t)UNI_PAD - base;           // (modulo 2^32: raw = P - UNI_PAD + base)
+                    const uint32_t ds = ts_doc_start(a.so, a.n_docs, P - shift);
+                    (void)uni_backtrack<true>(n, b, we, has_vm, id_b, a.unk_id, a.ids, tb + pre + nt - 1u, a.ids_cap,
+                                              UniSpanPut{a.so, shift, b, ds, ts_doc_chars(a.so, ds), b + uni_clen(s_txt + b, we - b, 0u), sp});
+                } else
                 (void)uni_backtrack<true>(n, b, we, has_vm, id_b, a.unk_id, a.ids, tb + pre + nt - 1u, a.ids_cap);
             }
             pre += nt;
@@ -300,7 +323,8 @@ template <bool WRITE> __global__ __launch_bounds__(UNI_NT) void k_uni_match(UniA
 }
 
 // ---- long words ----------------------------------------------------------------------------------------------------------------------
-template <bool WRITE> __global__ __launch_bounds__(UNI_LB) void k_uni_long(UniArgs a, uint32_t ntiles) {
+template <bool WRITE, bool SPAN = false> __global__ __launch_bounds__(UNI_LB) void k_uni_long(UniArgs a, uint32_t ntiles) {
+    static_assert(WRITE || !SPAN, "the spans are the write pass's");
     static_assert(UNI_LB == 64, "one wavefront: the ballot covers a block");
     __shared__ __attribute__((aligned(16))) UniEdge s_pool[UNI_LPOOL];
     __shared__ uint16_t s_head[UNI_LB];
@@ -361,6 +385,11 @@ template <bool WRITE> __global__ __launch_bounds__(UNI_LB) void k_uni_long(UniAr
             }
         } else if (lane == 0u) {
             const uint32_t cnt = a.lr_cnt[r];
+            if constexpr (SPAN) {
+                const uint32_t ds = ts_doc_start(a.so, a.n_docs, s0);
+                if (cnt) (void)uni_backtrack<true>(a.g, b, we, has_vm, id_b, a.unk_id, a.ids, a.lr_slot[r] + cnt - 1u, a.ids_cap,
+                                                   UniSpanPut{a.so, 0u, b, ds, ts_doc_chars(a.so, ds), b + uni_clen(a.text + b, we - b, 0u), sp});
+            } else
             if (cnt) (void)uni_backtrack<true>(a.g, b, we, has_vm, id_b, a.unk_id, a.ids, a.lr_slot[r] + cnt - 1u, a.ids_cap);
         }
         __syncthreads();

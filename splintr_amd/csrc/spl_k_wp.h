@@ -24,6 +24,7 @@
 // leaves the tile's tokens, k_decode_scan the bases, the write pass stores ids and the documents' offsets.  No atomics on the result.
 #pragma once
 #include "spl_common.h"
+#include "spl_k_textspans.h"
 
 namespace spl {
 
@@ -45,6 +46,7 @@ struct WpNormArgs {
     uint8_t* tstate;                     // [tiles]: the state a tile ends in (count pass)
     uint8_t* out; uint32_t* starts;      // write pass: the normalised text; word-start bits over it (zero-filled by the host)
     uint64_t* out_doc_off;               // [n_docs + 1]
+    uint32_t* map;                       // k_wp_norm<write, map> only: per normalised character start, its source (wp_map_entry)
 };
 // The trie.  edges: {node << 8 | byte, child}, key WP_NONE for an empty slot; a probe ends at the key, an empty slot or max_probe steps.
 struct WpTrie { const uint2* edges; uint32_t mask, hshift, max_probe; const uint32_t* node_id; };
@@ -54,7 +56,13 @@ struct WpMatchArgs {
     WpTrie trie; uint32_t unk_id, max_chars, halo;
     uint64_t* cnt;                       // [tiles + 1]: tokens per tile; exclusive sums and the total
     uint32_t* ids; uint64_t ids_cap; uint64_t* out_off;
+    const uint32_t* map; TextSpanOut so; // k_wp_match<write, span> only: the normaliser's source map; where the spans go
 };
+// The source map: the input character a normalised character came from, as the offset of its lead byte in the caller's text (26 bits:
+// WP_MAX_BYTES) and its length in bytes above them.  All outputs of one input share it; a position that starts no character holds 0.
+SPL_HD uint32_t wp_map_entry(uint32_t off, uint32_t len) { return off | len << 26; }
+SPL_HD uint32_t wp_map_off(uint32_t e) { return e & 0x3FFFFFFu; }
+SPL_HD uint32_t wp_map_end(uint32_t e) { return (e & 0x3FFFFFFu) + (e >> 26); }
 
 // One well-formed UTF-8 character at p[0 .. avail): its length and code point; 0 for a byte that starts none (it is dropped).  brk: bit k
 // set if a document starts at p + k -- a character does not reach across a document boundary.
@@ -109,16 +117,18 @@ constexpr int WPN_OUT = 3 * WPN_TB + 32;                    // staged output byt
 constexpr int WPN_OBW = (3 * WPN_TB + 31) / 32 + 2;         // words of the staged word-start bitmap
 
 // One lane's bytes [l0, l1) of the tile: the bytes they emit and the state behind them, from state st in front.  WRITE: the bytes go to
-// s_out + o, the word-start bits to s_sb at bit bb + o, the output position of every document start to s_opos.
-template <bool WRITE> __device__ __forceinline__ uint32_t wp_norm_lane(const WpNormTab& tab, const uint8_t* s_in, const uint32_t* s_brk, uint32_t l0,
+// s_out + o, the word-start bits to s_sb at bit bb + o, the output position of every document start to s_opos.  MAP: s_map + o takes the
+// source of every character written, as its position in the tile (12 bits) and its length above them.
+template <bool WRITE, bool MAP = false> __device__ __forceinline__ uint32_t wp_norm_lane(const WpNormTab& tab, const uint8_t* s_in, const uint32_t* s_brk, uint32_t l0,
                                                                        uint32_t l1, uint32_t avail, uint32_t& st, uint8_t* s_out, uint32_t o,
-                                                                       uint32_t* s_sb, uint32_t bb, uint16_t* s_opos) {
+                                                                       uint32_t* s_sb, uint32_t bb, uint16_t* s_opos, uint16_t* s_map = nullptr) {
     const uint32_t o0 = o;
     for (uint32_t li = l0; li < l1; li++) {
         if (wp_bit(s_brk, li)) { st = WPS_BOUND; if (WRITE) s_opos[li] = (uint16_t)o; }
         const uint32_t brk = (wp_bit(s_brk, li + 1u) ? 2u : 0u) | (wp_bit(s_brk, li + 2u) ? 4u : 0u) | (wp_bit(s_brk, li + 3u) ? 8u : 0u);
         uint32_t cp = 0;
-        if (!wp_decode(s_in + li, avail - li, brk, cp)) continue;
+        const uint32_t slen = wp_decode(s_in + li, avail - li, brk, cp);
+        if (!slen) continue;
         const uint32_t e = wp_norm_entry(tab, cp), n = e & 3u;
         for (uint32_t k = 0; k < n; k++) {
             const uint32_t v = wp_norm_out(tab, e, cp, k), oc = v & 0x1FFFFFu, len = wp_utf8_len(oc);
@@ -126,6 +136,7 @@ template <bool WRITE> __device__ __forceinline__ uint32_t wp_norm_lane(const WpN
             if (WRITE) {
                 if (!space && (iso || st != WPS_PLAIN)) atomicOr(&s_sb[(bb + o) >> 5], 1u << ((bb + o) & 31u));
                 wp_utf8_put(s_out + o, oc);
+                if constexpr (MAP) s_map[o] = (uint16_t)(li | slen << 12);
             }
             st = (space || iso) ? WPS_BOUND : WPS_PLAIN;
             o += len;
@@ -134,7 +145,9 @@ template <bool WRITE> __device__ __forceinline__ uint32_t wp_norm_lane(const WpN
     return o - o0;
 }
 
-template <bool WRITE> __global__ __launch_bounds__(WPN_NT) void k_wp_norm(WpNormArgs a) {
+template <bool WRITE, bool MAP = false> __global__ __launch_bounds__(WPN_NT) void k_wp_norm(WpNormArgs a) {
+    static_assert(WRITE || !MAP, "the map is the write pass's");
+    static_assert(WPN_TB <= 4096, "a source's position in the tile is 12 bits of the staged map");
     static_assert(WPN_NT == 256, "wp_block_excl and the state scan are written for four wavefronts");
     __shared__ __attribute__((aligned(16))) uint8_t s_in[WPN_TB + 16];
     __shared__ uint32_t s_brk[WPN_TB / 32 + 2];
@@ -187,8 +200,28 @@ template <bool WRITE> __global__ __launch_bounds__(WPN_NT) void k_wp_norm(WpNorm
         const uint64_t obase = a.cnt[tile];
         const uint32_t ba = (uint32_t)(obase & 15u), bb = (uint32_t)(obase & 31u);
         __syncthreads();
-        if (l0 < nv) (void)wp_norm_lane<true>(a.tab, s_in, s_brk, l0, l1, avail, sin, s_out + ba, o_lane, s_sb, bb, s_opos);
-        __syncthreads();
+        if constexpr (MAP) {
+            // the source map, staged beside the bytes at the same place modulo 16 and stored as they are: four entries -- 16 bytes -- a
+            // group, whole groups by one store, the groups the tile shares with its neighbours entry by entry
+            __shared__ uint16_t s_map[WPN_OUT];
+            if (l0 < nv) (void)wp_norm_lane<true, true>(a.tab, s_in, s_brk, l0, l1, avail, sin, s_out + ba, o_lane, s_sb, bb, s_opos, s_map + ba);
+            __syncthreads();
+            uint32_t* const m4 = a.map + (obase - ba);
+            for (uint32_t j = tid; j * 4u < ba + total; j += WPN_NT) {
+                const uint32_t lo = j * 4u;
+                uint32_t v[4];
+                for (uint32_t k = 0; k < 4u; k++) {
+                    const uint32_t q = lo + k;
+                    const bool cs = q >= ba && q < ba + total && (s_out[q] & 0xC0u) != 0x80u;
+                    v[k] = cs ? wp_map_entry(base + (s_map[q] & 0xFFFu), (uint32_t)s_map[q] >> 12) : 0u;
+                }
+                if (lo >= ba && lo + 4u <= ba + total) *reinterpret_cast<uint4*>(m4 + lo) = make_uint4(v[0], v[1], v[2], v[3]);
+                else for (uint32_t k = 0; k < 4u; k++) if (lo + k >= ba && lo + k < ba + total) m4[lo + k] = v[k];
+            }
+        } else {
+            if (l0 < nv) (void)wp_norm_lane<true>(a.tab, s_in, s_brk, l0, l1, avail, sin, s_out + ba, o_lane, s_sb, bb, s_opos);
+            __syncthreads();
+        }
         // the documents' offsets in the normalised text; the last tile also closes the table (documents that start at the text's end)
         for (uint32_t d = d0 + tid; d < a.n_docs; d += WPN_NT) {
             const uint64_t p = a.doc_off[d];
@@ -228,7 +261,8 @@ __device__ __forceinline__ uint32_t wp_child(const WpTrie& t, uint32_t node, uin
     return WP_NONE;
 }
 
-template <bool WRITE> __global__ __launch_bounds__(WPM_NT) void k_wp_match(WpMatchArgs a) {
+template <bool WRITE, bool SPAN = false> __global__ __launch_bounds__(WPM_NT) void k_wp_match(WpMatchArgs a) {
+    static_assert(WRITE || !SPAN, "the spans are the write pass's");
     static_assert(WPM_NT == 256 && WPM_TB == 8 * WPM_NT, "eight positions a lane in the chain phase; wp_block_excl");
     __shared__ __attribute__((aligned(16))) uint8_t s_txt[WPM_R + 16];
     __shared__ uint32_t s_st[WPM_R / 32 + 2];
@@ -301,6 +335,25 @@ template <bool WRITE> __global__ __launch_bounds__(WPM_NT) void k_wp_match(WpMat
             uint64_t at = tb + pre;
             if (tc & 0x8000u) { if (at < a.ids_cap) a.ids[at] = a.unk_id; }
             else for (uint32_t q = p, k = 0; k < tc; k++, at++) { const uint32_t li = s_li[q]; if (at < a.ids_cap) a.ids[at] = li & 0xFFFFFFu; q += li >> 24; }
+            if constexpr (SPAN) {
+                // a piece spans from the source of its first character to the end of the source of its last, an unk word from its first
+                // character's to its last's: that word may end beyond the halo, so its end is looked for in the text itself
+                at = tb + pre;
+                if (tc && at < a.ids_cap) {
+                    auto byte_at = [&](uint32_t g) { return g < nvr ? (uint32_t)s_txt[g] : (uint32_t)a.text[base + g]; };
+                    auto last_char = [&](uint32_t e) { uint32_t l = e - 1u; while ((byte_at(l) & 0xC0u) == 0x80u) l--; return a.map[base + l]; };
+                    const uint32_t m0 = a.map[base + p], ds = ts_doc_start(a.so, a.n_docs, wp_map_off(m0)), c0 = ts_doc_chars(a.so, ds);
+                    if (tc & 0x8000u) {
+                        uint32_t we = p + 1u;
+                        while (base + we < a.n_bytes && !(we < nvr ? is_b(we) : (a.text[base + we] == 0x20u || wp_bit(a.starts, base + we)))) we++;
+                        ts_store(a.so, at, ds, c0, wp_map_off(m0), wp_map_end(last_char(we)), false);
+                    } else for (uint32_t q = p, k = 0; k < tc && at < a.ids_cap; k++, at++) {
+                        const uint32_t l = s_li[q] >> 24;
+                        ts_store(a.so, at, ds, c0, wp_map_off(a.map[base + q]), wp_map_end(last_char(q + l)), false);
+                        q += l;
+                    }
+                }
+            }
             pre += tc & 0x7FFFu;
         }
         __syncthreads();

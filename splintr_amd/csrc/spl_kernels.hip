@@ -42,6 +42,7 @@
 //   spl_k_sp.h         k_sp_rewrite<count> / <write>: SentencePiece mode -- the corpus rewritten (spaces of ASCII-led whitespace runs to U+2581) and its chunk starts, bit vectors of 4 096 bytes a workgroup, the run flags by an add-carry and one wavefront scan (and its host-testable per-word logic)
 //   spl_k_wp.h         k_wp_norm<count> / <write>, k_wp_match<count> / <write>: WordPiece mode -- the BERT normaliser as a two-stage table lookup per code point with the word-start state scanned across lanes and tiles, and greedy longest-match-first over a hashed trie: a lane per character start walks it, a lane per word follows the chain (and their host-testable decode and table lookup)
 //   spl_k_uni.h        k_uni_match<count> / <write>, k_uni_long<count> / <write>: Unigram mode -- Viterbi over a hashed trie of all keys on the caller's text (0x20 and document starts feed U+2581 virtually): a lane per character start walks the trie and chains {f64 score, id, end} edges in LDS, a lane per word start runs the f64 dynamic program and the back-track with unk fusing; words longer than the halo go to a wavefront of their own with nodes in HBM (and their host-testable relax, back-track and character-start logic)
+//   spl_k_textspans.h  k_text_cstarts, ts_store: what the <write, span> variants of the two modes above share (spl_encode_batch_spans_device) -- character starts per 64 bytes of the caller's text, and a token's first and last source as a document-relative byte and character span; the variants themselves (k_wp_norm<write, map>, k_wp_match<write, span>, k_uni_match<write, span>, k_uni_long<write, span>) are in the modes' files
 //   (spl_rx_split.h, included by spl_api.hip: the device splitter for custom split patterns; its host half is in spl_launch.h)
 // (The multi-pass pipeline of rounds 1-3 -- k_bpe_lanes64, k_count, k_scan, k_compact_docs and the k_pretok
 //  instantiations without tile records -- was removed in round 4: no BASELINE configuration reached it.)
@@ -221,5 +222,6 @@ __device__ __forceinline__ uint32_t tidx() {
 #include "spl_k_draft.h"
 #include "spl_k_ngram.h"
 #include "spl_k_sp.h"
+#include "spl_k_textspans.h"
 #include "spl_k_wp.h"
 #include "spl_k_uni.h"

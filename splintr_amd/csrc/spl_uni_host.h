@@ -57,6 +57,7 @@ struct UniCtx {                                              // one GPU's share:
     bool uploaded = false;
     DevBuf<uint64_t> cnt, lr_slot; DevBuf<uint32_t> lr_n, lr_start, lr_cnt, g_bid, g_bfrom; DevBuf<double> g_best;
     uint64_t cap_bytes = 0;
+    DevBuf<uint64_t> cblk; uint64_t cblk_cap = 0;            // character spans only (spans_reserve, spl_wp_host.h)
 };
 
 // The workspace of calls of up to max_bytes of text: a count per tile, the long words' records (UNI_LREC a tile), and the long path's
@@ -81,8 +82,9 @@ int uni_reserve(spl_tokenizer* tk, Ctx* c, uint64_t max_bytes, uint64_t /*max_do
     return SPL_OK;
 }
 
-int encode_device_uni(spl_tokenizer* tk, Ctx* c, const uint8_t* d_utf8, uint64_t n_bytes, const uint64_t* d_doc_off, uint64_t n_docs,
-                      uint32_t flags, uint32_t* d_ids, uint64_t ids_cap, uint64_t* d_out_off, hipStream_t s, const SlabOut* so) {
+// sr: the spans beside the ids (spl_encode_batch_spans_device) -- the two write kernels store a span per id; still no synchronisation.
+int encode_device_uni_spans(spl_tokenizer* tk, Ctx* c, const uint8_t* d_utf8, uint64_t n_bytes, const uint64_t* d_doc_off, uint64_t n_docs,
+                            uint32_t flags, uint32_t* d_ids, uint64_t ids_cap, uint64_t* d_out_off, hipStream_t s, const SlabOut* so, const SpanReq* sr) {
     if ((flags & SPL_WITH_SPECIAL) && !tk->specials.empty())
         return fail(SPL_EINVAL, "Unigram mode: SPL_WITH_SPECIAL is refused on a handle with special tokens -- literals in the text are not looked for; <s> and </s> come from the pair and chat collation");
     if (n_bytes > UNI_MAX_BYTES) return fail(SPL_EINVAL, "Unigram mode: a device call takes at most 64 MiB of text (split the corpus at document boundaries -- spl_encode_batch does that by itself)");
@@ -92,6 +94,7 @@ int encode_device_uni(spl_tokenizer* tk, Ctx* c, const uint8_t* d_utf8, uint64_t
     SPL_TRY(uni_reserve(tk, c, n_bytes, n_docs));
     UniCtx& x = *c->uni;
     const UniHost& u = *tk->uni;
+    if (sr) SPL_TRY(spans_reserve(x.cblk, &x.cblk_cap, nullptr, nullptr, x.cap_bytes, sr->cspan != nullptr));
     Event ev[5];
     if (c->prof) for (auto& e : ev) SPL_TRY(e.create(hipEventDefault));
     if (!n_bytes) {                                          // (nothing to match: n_docs empty rows)
@@ -112,9 +115,14 @@ int encode_device_uni(spl_tokenizer* tk, Ctx* c, const uint8_t* d_utf8, uint64_t
         hipLaunchKernelGGL(k_uni_long<false>, dim3(nlong), dim3(UNI_LB), 0, s, a, ntiles);
         hipLaunchKernelGGL(k_decode_scan, dim3(1), dim3(1024), 0, s, a.cnt, (uint64_t)ntiles);
         if (c->prof) HIP_TRY(hipEventRecord(ev[2].get(), s));
-        hipLaunchKernelGGL(k_uni_match<true>, dim3(ntiles), dim3(UNI_NT), 0, s, a);
+        if (sr) {
+            if (sr->cspan) text_char_blocks(d_utf8, n_bytes, x.cblk.get(), s);
+            a.so = TextSpanOut{d_utf8, d_doc_off, x.cblk.get(), sr->bspan, sr->cspan};
+            hipLaunchKernelGGL((k_uni_match<true, true>), dim3(ntiles), dim3(UNI_NT), 0, s, a);
+        } else hipLaunchKernelGGL(k_uni_match<true>, dim3(ntiles), dim3(UNI_NT), 0, s, a);
         if (c->prof) HIP_TRY(hipEventRecord(ev[3].get(), s));
-        hipLaunchKernelGGL(k_uni_long<true>, dim3(nlong), dim3(UNI_LB), 0, s, a, ntiles);
+        if (sr) hipLaunchKernelGGL((k_uni_long<true, true>), dim3(nlong), dim3(UNI_LB), 0, s, a, ntiles);
+        else hipLaunchKernelGGL(k_uni_long<true>, dim3(nlong), dim3(UNI_LB), 0, s, a, ntiles);
         if (c->prof) HIP_TRY(hipEventRecord(ev[4].get(), s));
         HIP_TRY(hipGetLastError());
     }
@@ -130,5 +138,9 @@ int encode_device_uni(spl_tokenizer* tk, Ctx* c, const uint8_t* d_utf8, uint64_t
         }
     }
     return SPL_OK;
+}
+int encode_device_uni(spl_tokenizer* tk, Ctx* c, const uint8_t* d_utf8, uint64_t n_bytes, const uint64_t* d_doc_off, uint64_t n_docs,
+                      uint32_t flags, uint32_t* d_ids, uint64_t ids_cap, uint64_t* d_out_off, hipStream_t s, const SlabOut* so) {
+    return encode_device_uni_spans(tk, c, d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_cap, d_out_off, s, so, nullptr);
 }
 }  // namespace

@@ -1,6 +1,10 @@
 // spl_wp_host.h -- WordPiece mode, host side (the kernels: spl_k_wp.h): the check of the normalisation table and the trie (wp_build, at
 // spl_create), their upload and the workspace (wp_reserve), and one device call -- count pass of the normaliser, scan, ONE synchronisation
 // for the normalised length, write pass, then the matcher's count pass, scan and write pass.  Needs ensure_streams (spl_ctx.h).
+// A span call (spl_encode_batch_spans_device) is the same call with the <write, map> / <write, span> variants of the two write passes and,
+// for character spans, the character count of the caller's text in front of the matcher's (spans_reserve, text_char_blocks: Unigram
+// mode's span call, spl_uni_host.h, uses them too).  Workspace of a span call beyond the mode's: 12 bytes per byte of text (the source
+// map) and 8 bytes per 64 (the character count).
 #pragma once
 namespace {
 
@@ -101,7 +105,26 @@ struct WpCtx {                                               // one GPU's share:
     bool uploaded = false;
     DevBuf<uint8_t> text, tstate; DevBuf<uint64_t> cnt, off; DevBuf<uint32_t> bits;
     uint64_t cap_bytes = 0, cap_docs = 0;
+    DevBuf<uint32_t> map; DevBuf<uint64_t> cblk; uint64_t map_cap = 0, cblk_cap = 0;      // span calls only (spans_reserve)
 };
+
+// What spl_encode_batch_spans_device asks of a mode's device call beyond the encode: [ids_cap, 2] each, either may be null.
+struct SpanReq { int32_t* bspan; int32_t* cspan; };
+
+// The workspace of a span call on top of the mode's own, reserved by the first span call (and grown with the mode's): the character
+// starts in front of every TS_BLK bytes of the text for character spans (8 bytes per 64 of text) and, WordPiece mode, the source map
+// -- a word per byte of normalised text, 12 bytes per byte of text.
+int spans_reserve(DevBuf<uint64_t>& cblk, uint64_t* cblk_cap, DevBuf<uint32_t>* map, uint64_t* map_cap, uint64_t cap_bytes, bool chars) {
+    if (chars) SPL_TRY(cblk.grow(cblk_cap, cap_bytes / TS_BLK + 2, cap_bytes / TS_BLK + 2));
+    if (map) SPL_TRY(map->grow(map_cap, 3 * cap_bytes + 64, 3 * cap_bytes + 64));
+    return SPL_OK;
+}
+// cblk[i]: the character starts in text[0, TS_BLK * i), for every i up to the block that holds n_bytes.
+void text_char_blocks(const uint8_t* d_utf8, uint64_t n_bytes, uint64_t* cblk, hipStream_t s) {
+    const uint64_t n_blk = (n_bytes + TS_BLK - 1) / TS_BLK;
+    hipLaunchKernelGGL(k_text_cstarts, dim3((uint32_t)((n_bytes + 16 * TS_NT - 1) / (16 * TS_NT))), dim3(TS_NT), 0, s, d_utf8, (uint32_t)n_bytes, cblk);
+    hipLaunchKernelGGL(k_decode_scan, dim3(1), dim3(1024), 0, s, cblk, n_blk);
+}
 
 // The workspace of calls of up to max_bytes of text and max_docs documents: the normalised text (three times the bytes), its word-start
 // bits, a count per tile of either kernel (one array serves both, the normaliser's first), a state per tile, the normalised offsets.
@@ -134,8 +157,10 @@ int wp_reserve(spl_tokenizer* tk, Ctx* c, uint64_t max_bytes, uint64_t max_docs)
     return SPL_OK;
 }
 
-int encode_device_wp(spl_tokenizer* tk, Ctx* c, const uint8_t* d_utf8, uint64_t n_bytes, const uint64_t* d_doc_off, uint64_t n_docs,
-                     uint32_t flags, uint32_t* d_ids, uint64_t ids_cap, uint64_t* d_out_off, hipStream_t s, const SlabOut* so) {
+// sr: the spans beside the ids (spl_encode_batch_spans_device) -- the normaliser's write pass leaves its source map, the matcher's stores
+// a span per id; their time counts in the same profile slots.
+int encode_device_wp_spans(spl_tokenizer* tk, Ctx* c, const uint8_t* d_utf8, uint64_t n_bytes, const uint64_t* d_doc_off, uint64_t n_docs,
+                           uint32_t flags, uint32_t* d_ids, uint64_t ids_cap, uint64_t* d_out_off, hipStream_t s, const SlabOut* so, const SpanReq* sr) {
     if ((flags & SPL_WITH_SPECIAL) && !tk->specials.empty())
         return fail(SPL_EINVAL, "WordPiece mode: SPL_WITH_SPECIAL is refused on a handle with special tokens -- literals in the text are not looked for; [CLS] and [SEP] come from the pair and chat collation");
     if (n_bytes > WP_MAX_BYTES) return fail(SPL_EINVAL, "WordPiece mode: a device call takes at most 64 MiB of text (split the corpus at document boundaries -- spl_encode_batch does that by itself)");
@@ -145,6 +170,7 @@ int encode_device_wp(spl_tokenizer* tk, Ctx* c, const uint8_t* d_utf8, uint64_t 
     SPL_TRY(wp_reserve(tk, c, n_bytes, n_docs));
     WpCtx& x = *c->wp;
     const WpHost& w = *tk->wp;
+    if (sr) SPL_TRY(spans_reserve(x.cblk, &x.cblk_cap, &x.map, &x.map_cap, x.cap_bytes, sr->cspan != nullptr));
     Event ev[5];
     if (c->prof) for (auto& e : ev) SPL_TRY(e.create(hipEventDefault));
     uint64_t n_out = 0;
@@ -153,7 +179,7 @@ int encode_device_wp(spl_tokenizer* tk, Ctx* c, const uint8_t* d_utf8, uint64_t 
         a.text = d_utf8; a.n_bytes = (uint32_t)n_bytes; a.doc_off = d_doc_off; a.n_docs = (uint32_t)n_docs;
         a.tab = WpNormTab{x.s1.get(), x.s2.get(), x.multi.get(), w.shift};
         a.cnt = x.cnt.get(); a.tstate = x.tstate.get();
-        a.out = x.text.get(); a.starts = x.bits.get(); a.out_doc_off = x.off.get();
+        a.out = x.text.get(); a.starts = x.bits.get(); a.out_doc_off = x.off.get(); a.map = sr ? x.map.get() : nullptr;
         const uint32_t ntiles = (uint32_t)((n_bytes + WPN_TB - 1) / WPN_TB);
         if (c->prof) HIP_TRY(hipEventRecord(ev[0].get(), s));
         hipLaunchKernelGGL(k_wp_norm<false>, dim3(ntiles), dim3(WPN_NT), 0, s, a);
@@ -165,7 +191,8 @@ int encode_device_wp(spl_tokenizer* tk, Ctx* c, const uint8_t* d_utf8, uint64_t 
         HIP_TRY(hipStreamSynchronize(s));
         if (n_out > 3 * n_bytes) return fail(SPL_EDEVICE, "WordPiece mode: the count pass reports more than three times the bytes");
         HIP_TRY(hipMemsetAsync(x.bits.get(), 0, (n_out / 32 + 4) * 4, s));
-        hipLaunchKernelGGL(k_wp_norm<true>, dim3(ntiles), dim3(WPN_NT), 0, s, a);
+        if (sr) hipLaunchKernelGGL((k_wp_norm<true, true>), dim3(ntiles), dim3(WPN_NT), 0, s, a);
+        else hipLaunchKernelGGL(k_wp_norm<true>, dim3(ntiles), dim3(WPN_NT), 0, s, a);
         if (c->prof) HIP_TRY(hipEventRecord(ev[2].get(), s));
         HIP_TRY(hipGetLastError());
     }
@@ -181,7 +208,11 @@ int encode_device_wp(spl_tokenizer* tk, Ctx* c, const uint8_t* d_utf8, uint64_t 
         hipLaunchKernelGGL(k_wp_match<false>, dim3(mtiles), dim3(WPM_NT), 0, s, m);
         hipLaunchKernelGGL(k_decode_scan, dim3(1), dim3(1024), 0, s, m.cnt, (uint64_t)mtiles);
         if (c->prof) HIP_TRY(hipEventRecord(ev[3].get(), s));
-        hipLaunchKernelGGL(k_wp_match<true>, dim3(mtiles), dim3(WPM_NT), 0, s, m);
+        if (sr) {
+            if (sr->cspan) text_char_blocks(d_utf8, n_bytes, x.cblk.get(), s);
+            m.map = x.map.get(); m.so = TextSpanOut{d_utf8, d_doc_off, x.cblk.get(), sr->bspan, sr->cspan};
+            hipLaunchKernelGGL((k_wp_match<true, true>), dim3(mtiles), dim3(WPM_NT), 0, s, m);
+        } else hipLaunchKernelGGL(k_wp_match<true>, dim3(mtiles), dim3(WPM_NT), 0, s, m);
         if (c->prof) HIP_TRY(hipEventRecord(ev[4].get(), s));
         HIP_TRY(hipGetLastError());
     }
@@ -197,5 +228,9 @@ int encode_device_wp(spl_tokenizer* tk, Ctx* c, const uint8_t* d_utf8, uint64_t 
         }
     }
     return SPL_OK;
+}
+int encode_device_wp(spl_tokenizer* tk, Ctx* c, const uint8_t* d_utf8, uint64_t n_bytes, const uint64_t* d_doc_off, uint64_t n_docs,
+                     uint32_t flags, uint32_t* d_ids, uint64_t ids_cap, uint64_t* d_out_off, hipStream_t s, const SlabOut* so) {
+    return encode_device_wp_spans(tk, c, d_utf8, n_bytes, d_doc_off, n_docs, flags, d_ids, ids_cap, d_out_off, s, so, nullptr);
 }
 }  // namespace

@@ -61,6 +61,25 @@ def encode_device(tok: Tokenizer, batch: DeviceBatch, with_special: bool = False
         raise RuntimeError(f"spl_encode_batch_device failed ({rc}): {_ffi.last_error()}")
 
 
+def encode_spans_device(tok: Tokenizer, batch: DeviceBatch, *, chars: bool = True, bytes: bool = True, with_special: bool = False):
+    """encode_device on a WordPiece or Unigram handle plus where every id lies in its document, from the encode kernels themselves
+    (spl_encode_batch_spans_device), asynchronous on torch's current stream.  Returns (byte_span, char_span): int32 [batch.ids.numel(),
+    2] each, or None for the one not asked for; row i is written where batch.ids[i] is.  ValueError for a handle of another mode
+    (spans_device serves those)."""
+    if not (chars or bytes):
+        raise ValueError("encode_spans_device: neither chars nor bytes asked for")
+    dev = batch.text.device
+    byte_span = torch.empty((batch.ids.numel(), 2), dtype=torch.int32, device=dev) if bytes else None
+    char_span = torch.empty((batch.ids.numel(), 2), dtype=torch.int32, device=dev) if chars else None
+    rc = _ffi.lib().spl_encode_batch_spans_device(tok.handle, batch.text.data_ptr(), batch.n_bytes, batch.doc_off.data_ptr(), batch.n_docs,
+                                                  _ffi.SPL_WITH_SPECIAL if with_special else 0, batch.ids.data_ptr(), batch.ids.numel(),
+                                                  batch.out_off.data_ptr(), _ptr(byte_span), _ptr(char_span),
+                                                  torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        _raise_rc(rc, "spl_encode_batch_spans_device")
+    return byte_span, char_span
+
+
 def reserve(tok: Tokenizer, n_bytes: int, n_docs: int) -> None:
     if _ffi.lib().spl_reserve(tok.handle, n_bytes, n_docs) != 0:
         raise RuntimeError(_ffi.last_error())

@@ -616,10 +616,24 @@ class Tokenizer:
         UTF-8 text (unit="byte": text.encode()[start:end] is the token).  The encode and the spans (splintr_amd.device.spans_device)
         run on the device on torch's current stream; the offsets come back first (the one synchronisation), then the ids and the spans
         of exactly the tokens there are in one copy.  ValueError naming the first document whose ids do not decode to its text (a custom
-        pattern that leaves gaps, a vocabulary that lacks a byte): its spans would not index the text."""
+        pattern that leaves gaps, a vocabulary that lacks a byte): its spans would not index the text.  WordPiece and Unigram handles:
+        the spans come from the encode kernels themselves (splintr_amd.device.encode_spans_device) -- Hugging Face's Encoding.offsets,
+        from the source of a token's first character to the end of the source of its last; no such check applies."""
         if unit not in ("char", "byte"):
             raise ValueError(f"unit must be 'char' or 'byte', not {unit!r}")
         import torch
+        if self.is_wordpiece() or self.is_unigram():
+            # these modes' ids do not decode to the text: the spans come from the encode kernels (encode_spans_device) and are of the
+            # text by construction.  A document adds at most its prepended marker to an id per byte.
+            from . import device as dv
+            batch = dv.DeviceBatch(texts, torch.device("cuda", self._device))
+            batch.ids = torch.empty(batch.n_bytes + batch.n_docs + 1, dtype=torch.int32, device=batch.text.device)
+            byte_span, char_span = dv.encode_spans_device(self, batch, chars=unit == "char", bytes=unit == "byte", with_special=with_special)
+            cuts = batch.out_off.cpu().tolist()
+            n = cuts[-1]
+            flat = torch.cat([batch.ids[:n].reshape(n, 1), (char_span if unit == "char" else byte_span)[:n]], dim=1).cpu().numpy()
+            ids, spans = flat[:, 0].view(np.uint32).tolist(), list(zip(flat[:, 1].tolist(), flat[:, 2].tolist()))
+            return [ids[a:b] for a, b in zip(cuts, cuts[1:])], [spans[a:b] for a, b in zip(cuts, cuts[1:])]
         dv, batch = self._encode_on_device(texts, with_special)
         byte_span, char_span, byte_off, _ = dv.spans_device(self, batch.ids, batch.out_off, chars=unit == "char")
         off = torch.stack([batch.out_off, byte_off]).cpu().numpy()

@@ -25,7 +25,7 @@ import torch  # noqa: E402
 
 from splintr_amd import Tokenizer, _ffi, corpus  # noqa: E402
 from splintr_amd.device import DeviceBatch, encode_device  # noqa: E402
-from wordpiece_bench import burst_ms, vocab as wordpiece_vocab  # noqa: E402
+from wordpiece_bench import burst_ms, span_legs, vocab as wordpiece_vocab  # noqa: E402
 
 PHASES = ["k_uni_match<count>", "k_uni_long<count>+k_decode_scan", "k_uni_match<write>", "k_uni_long<write>"]
 
@@ -87,7 +87,9 @@ def main():
         for name, t in (("device encode, Unigram", uni), ("device encode, WordPiece", wp)):
             got[name] = burst_ms(lambda: encode_device(t, batch, False), dev)
             lines.append(f"   {name:34s} {got[name]:8.4f}   {nb / got[name] / 1e6:.2f} GB/s")
-        u = got["device encode, Unigram"]
+            if t is uni:
+                lines += span_legs(uni, batch, dev, got[name])
+        u =got["device encode, Unigram"]
         lines.append(f"   Unigram / WordPiece on the same bytes: {u / got['device encode, WordPiece']:.2f}x the time; / the copy: {u / copy:.1f}x")
         try:
             import tokenizers as tk

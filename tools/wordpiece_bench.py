@@ -4,7 +4,8 @@
     python tools/wordpiece_bench.py [--out profiles/wordpiece.txt]
 
 For corpus.c2 (1 000 documents of about 1 KB) and 8 000 documents of the same text (about 8 MB): the normaliser's two passes and the
-matcher's two passes (the library's own per-kernel profile), the whole device encode (spl_encode_batch_device) on the WordPiece handle,
+matcher's two passes (the library's own per-kernel profile), the whole device encode (spl_encode_batch_device) on the WordPiece handle, the same
+encode with token spans (spl_encode_batch_spans_device: bytes only, bytes and characters; tools/unigram_bench.py has the same leg),
 the same text on a cl100k_base handle, and a device-to-device copy of the same bytes; Hugging Face's tokenizers.encode_batch (wall time)
 where that module imports.  The vocabulary is GENERATED -- no real vocab.txt is shipped or needed: up to 30 000 keys (about 21 000 from this corpus), the corpus's
 commonest words and word pieces, every character both word-initial and continued."""
@@ -52,6 +53,23 @@ def burst_ms(fn, dev, bursts=11, per=8):
     return statistics.median(out[1:])
 
 
+def span_legs(tok, batch, dev, plain_ms):
+    """The span leg (spl_encode_batch_spans_device into buffers made once): byte spans alone, then byte and character spans, beside the
+    plain device encode of the same run."""
+    span = [torch.empty((batch.ids.numel(), 2), dtype=torch.int32, device=dev) for _ in range(2)]
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    lines = []
+    for name, c in (("  + byte spans", None), ("  + byte and character spans", span[1].data_ptr())):
+        def call():
+            rc = _ffi.lib().spl_encode_batch_spans_device(tok.handle, batch.text.data_ptr(), batch.n_bytes, batch.doc_off.data_ptr(), batch.n_docs, 0,
+                                                          batch.ids.data_ptr(), batch.ids.numel(), batch.out_off.data_ptr(), span[0].data_ptr(), c, stream)
+            assert rc == 0, _ffi.last_error()
+        call()
+        m = burst_ms(call, dev)
+        lines.append(f"   {name:34s} {m:8.4f}   {batch.n_bytes / m / 1e6:.2f} GB/s   {m - plain_ms:+.4f} ms, {m / plain_ms:.2f}x the plain encode")
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -89,6 +107,8 @@ def main():
         for name, t in (("device encode, WordPiece", wp), ("device encode, cl100k_base", cl)):
             m = burst_ms(lambda: encode_device(t, batch, False), dev)
             lines.append(f"   {name:34s} {m:8.4f}   {nb / m / 1e6:.2f} GB/s")
+            if t is wp:
+                lines += span_legs(wp, batch, dev, m)
         lines.append(f"   ({n_tok} cl100k tokens; every call encodes the same batch again)")
         try:
             import tokenizers as tk
